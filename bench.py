@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- seam-carving throughput on MI355X (metric of BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps and prints one JSON line
+with the headline (metric, value, unit, higher_is_better, dtype, ms_per_step,
+config).  Everything else below -- roofline, per-kernel times, phases, output
+checksum, CPU baseline and parity, the strong leg and the gather for N > 1, the
+config legs -- is measured only with --full.  --dump-outputs DIR writes what the
+last timed step computed (dump_outputs: per-image channel sums and a fixed,
+seeded sample of the carved pixels) as .npy; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 One "step" = one pass of the hot path (lqr_carver_resize: energy -> DP -> seam
 pick/backtrack -> carve) over one batch of synthetic
@@ -9,7 +18,7 @@ images that are already resident in HBM.  Default workload = config 4 of
 BASELINE.json ("batch of 64 independent 4K RGBA images, 200 seams each"): every
 rank carves its own batch of 64 images of 3840x2160 RGBA by 200 vertical seams as
 one lock-step batch; images are independent, so there is no data-path collective
-and scaling is weak.  With N > 1 the same invocation afterwards also runs config 4
+and scaling is weak.  With N > 1 and --full the same invocation afterwards also runs config 4
 AS STATED -- 64 images in total, 64 / N per GPU -- and reports it as `strong` on the
 same JSON line (--strong makes that the timed workload itself).
 --workload single4k | fhd | 8k run configs 3 / 2 / 5's geometry; --workload config5
@@ -38,7 +47,7 @@ never `value`.
 Run with --gpus N > 1 and no RANK in the environment, the script re-executes
 itself under torch.distributed.run with N ranks (one per GPU, RCCL).
 
-Also on the JSON line:
+Also on the JSON line with --full:
   roofline      the dominant HBM kernel (k_carve), HIP-event timed per launch on its own stream(s) inside the timed
                 region.  achieved = algorithmic bytes per launch (8 B x W*H/2 per image) / the average
                 launch duration, or -- when smaller -- the bytes on the side of the seam the carve really moves (18 B per
@@ -113,7 +122,18 @@ def parse():
                     help="skip the extra legs after the headline: BASELINE configs 2, 3 and 5 (fhd, single4k, config5), 3 steps each")
     ap.add_argument("--no-kernel-breakdown", action="store_true", help="skip the extra untimed step that HIP-event times every kernel")
     ap.add_argument("--switch-freq", type=int, default=2, help="lqr side switch frequency (plug-in: 2, render.c:237)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline and per-kernel figures, phases, output checksum, CPU baseline and "
+                         "parity, the strong leg and the gather (N > 1), the config legs; the --no-* switches and --kernel-times "
+                         "act on these.  Without it a run sets up, warms up, times the K steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.kernel_times and not args.full:
+        ap.error("--kernel-times is a per-kernel figure: it needs --full")
+    return args
 
 
 WORKLOADS = {
@@ -244,6 +264,26 @@ def strong_images_per_gpu(world, total=64):
     return max(1, total // max(world, 1))
 
 
+DUMP_SAMPLE_PX = 1 << 21       # pixels sampled over the whole batch: 2 M x 4 channels x 4 B = 32 MB
+
+
+def dump_outputs(out_dir, outs, suffix=""):
+    """what a caller of the timed path receives -- the carved images, u8 [n, h, w, 4] on the device -- as
+    images_channel_sum.npy  [n, 4] float64: every pixel of every image, summed per channel (exact)
+    images_sample.npy       [n, k, 4] float32: the same k pixels of every image, k = min(h * w, DUMP_SAMPLE_PX / n), at
+                            positions drawn with a fixed seed (the same for every run of the same geometry)"""
+    import numpy as np
+    import torch
+    n, h, w, ch = outs.shape
+    os.makedirs(out_dir, exist_ok=True)
+    sums = np.stack([outs[i].to(torch.int64).sum(dim=(0, 1)).cpu().numpy() for i in range(n)]).astype(np.float64)
+    k = min(h * w, max(1, DUMP_SAMPLE_PX // n))
+    idx = np.sort(np.random.default_rng(20240611).choice(h * w, size=k, replace=False))
+    sample = outs.view(n, h * w, ch)[:, torch.from_numpy(idx).to(outs.device)].to(torch.float32).cpu().numpy()
+    np.save(os.path.join(out_dir, "images_channel_sum%s.npy" % suffix), sums)
+    np.save(os.path.join(out_dir, "images_sample%s.npy" % suffix), sample)
+
+
 def cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -319,11 +359,12 @@ def main():
             dist.init_process_group(backend="nccl", device_id=dev)
         else:
             dist.init_process_group(backend=backend)
+    full = args.full
 
     def measure(wl, steps, warmup, headline, n_images=None, delta=None):
         """one workload: set-up, `warmup` untimed + exactly `steps` timed steps, per-kernel breakdown, phases, CPU baseline;
         `headline`: also the gather / strong / all-cores legs; `n_images`: images per GPU of a batch workload other than the
-        command line's.  Returns the JSON object of the workload."""
+        command line's.  Without --full only the set-up and the steps.  Returns the JSON object of the workload."""
         W, H, NW, NH = WORKLOADS[wl]
         dlt = delta if delta is not None else args.delta
         batch = wl == "batch4k"
@@ -419,19 +460,33 @@ def main():
             timed.moved_bytes = mv.value
             return max_over_ranks(t1 - t0)
 
-        # ---- phase "resize" (render.c:314-316): W warm-up steps, then exactly K timed steps
-        elapsed = timed(carvers, ptrs, steps, warmup, 1 if args.kernel_times else 2)
+        # ---- phase "resize" (render.c:314-316): W warm-up steps, then exactly K timed steps (HIP events around k_carve -- or
+        # every kernel with --kernel-times -- only for the --full figures)
+        elapsed = timed(carvers, ptrs, steps, warmup, (1 if args.kernel_times else 2) if full else 0)
         moved_total = timed.moved_bytes            # bytes the timed steps' carves had to move (k_vpath*'s count of the side that moves)
         used_gb, total_gb = mem_used_gb()
         streams = lib.lqrhip_sub_batches(nimg) if nimg > 1 else 1
+
+        # ---- the results of the last timed step, read before anything else runs on the carvers
+        outs = None
+        if full or (headline and args.dump_outputs):
+            outs = torch.empty((nimg, NH, NW, 4), dtype=torch.uint8, device=dev)
+            if carvers[0].getters()["orientation"] == 0:
+                for i, c in enumerate(carvers):
+                    assert eng.lqrx_carver_read_image_device(c.p, outs[i].data_ptr()) == L.LQR_OK
+            else:       # transposed carver frame: go through the host image-orientation read-out
+                for i, c in enumerate(carvers):
+                    outs[i].copy_(torch.from_numpy(c.read_image()))
+            if headline and args.dump_outputs:
+                dump_outputs(args.dump_outputs, outs, "_rank%d" % rank if world > 1 else "")
 
         # ---- per-kernel HIP-event times collected inside the timed region
         def prof(name):
             ms, n, by = C.c_double(0), C.c_longlong(0), C.c_double(0)
             lib.lqrhip_prof_get(name.encode(), C.byref(ms), C.byref(n), C.byref(by))
             return ms.value, n.value, by.value
-        kern = {k: prof(k) for k in KERNEL_NAMES}
-        c_ms, c_n, c_bytes = kern["carve"]
+        kern = {k: prof(k) for k in KERNEL_NAMES} if full else {}
+        c_ms, c_n, c_bytes = kern.get("carve", (0.0, 0, 0.0))
         work_rank = work_seam_px(W, H, NW, NH) * nimg * steps       # seam*px per rank
         value = work_rank * world / elapsed / 1e6
         roofline = None
@@ -481,7 +536,7 @@ def main():
 
         # ---- where the step's time goes: ONE extra, untimed step with every kernel of the seam loop HIP-event timed (the
         # events cost queue time, which is why the timed region times k_carve only)
-        if not args.no_kernel_breakdown and not args.kernel_times:
+        if full and not args.no_kernel_breakdown and not args.kernel_times:
             timed(carvers, ptrs, 1, 0, 1)
             kern = {k: prof(k) for k in KERNEL_NAMES}
         tot_ms = sum(v[0] for v in kern.values()) or 1.0
@@ -519,7 +574,7 @@ def main():
         # (device compaction of the visible pixels + D2H; the scan-line loop of io_functions.c:155-164 is served from that
         # host copy), then -- N > 1 -- the gather to rank 0 over RCCL
         readout_ms = None
-        if not args.no_phases:
+        if full and not args.no_phases:
             sync()
             tr = time.perf_counter()
             host_out = [c.read_image() for c in carvers]
@@ -527,15 +582,8 @@ def main():
             assert host_out[0].shape == (NH, NW, 4)
             del host_out
             upload_ms = max_over_ranks(upload_ms)
-        gather_ms = gathered_checksums = None
-        outs = torch.empty((nimg, NH, NW, 4), dtype=torch.uint8, device=dev)
-        if carvers[0].getters()["orientation"] == 0:
-            for i, c in enumerate(carvers):
-                assert eng.lqrx_carver_read_image_device(c.p, outs[i].data_ptr()) == L.LQR_OK
-        else:       # transposed carver frame: go through the host image-orientation read-out
-            for i, c in enumerate(carvers):
-                outs[i].copy_(torch.from_numpy(c.read_image()))
-        if dist is not None and not args.no_gather:
+        gather_ms = gathered_checksums = checksum = None
+        if full and dist is not None and not args.no_gather:
             sync(); barrier()
             tg = time.perf_counter()
             src = outs if backend == "nccl" else outs.cpu()
@@ -545,7 +593,8 @@ def main():
             gather_ms = (time.perf_counter() - tg) * 1e3
             gathered_checksums = [int(g.to(torch.int64).sum().item()) for g in gathered] if rank == 0 else None       # what arrived from each rank
             del gathered, src
-        checksum = int(outs.to(torch.int64).sum().item())
+        if full:
+            checksum = int(outs.to(torch.int64).sum().item())
         g = carvers[0].getters()
         assert (g["width"], g["height"]) == (NW, NH), g
 
@@ -575,6 +624,9 @@ def main():
             "hbm_used_gb": round(used_gb, 1), "hbm_total_gb": round(total_gb, 1),
             "output_checksum": checksum,
         }
+        if not full:
+            for k in ("roofline", "kernels_ms", "gather_ms", "gathered_checksums", "output_checksum"):
+                del result[k]
         if readout_ms is not None:
             e2e_ms = upload_ms + ms_per_step + readout_ms
             result["phases"] = {
@@ -585,7 +637,7 @@ def main():
                         "upload + resize + readout; `value` itself is the HBM-resident rate"}
 
         # ---- config 4 as stated, on the same line when N > 1: 64 images in total = 64 // N per GPU (strong scaling)
-        if headline and batch and world > 1 and not args.strong:
+        if full and headline and batch and world > 1 and not args.strong:
             ns = min(strong_images_per_gpu(world), nimg)
             el = timed(carvers[:ns], ptrs[:ns], steps, 1, 0)
             result["strong"] = {"images_total": ns * world, "images_per_gpu": ns, "scaling": "strong",
@@ -595,7 +647,7 @@ def main():
 
         # ---- CPU baseline: the oracle (a port of the algorithm; test infrastructure, loaded here only as the
         # reported baseline and the spot checker) on this host's cores
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             from concurrent.futures import ThreadPoolExecutor
             orc = L.Api(os.path.join(ROOT, "oracle", "liblqr_oracle.so"), "o")
             ncores = os.cpu_count() or 1
@@ -676,7 +728,7 @@ def main():
             result["band_levels_stats"] = {"images_stopped_by_a_collision": st[0], "synchronous_loads": st[1], "tile_levels_processed": st[2], "slot_levels_idle": st[3]}
     # ---- on the same line: config 4's LITERAL per-GPU shard (64 images over 8 GPUs = 8 per GPU: the strong-scaling end nobody
     # can measure without the node), then BASELINE configs 2, 3 and 5 -- the plug-in's own call shape, one carver (render.c:318)
-    if args.workload == "batch4k" and world == 1 and not args.no_configs and args.seams is None and not args.strong:
+    if full and args.workload == "batch4k" and world == 1 and not args.no_configs and args.seams is None and not args.strong:
         result["configs"] = {}
         keep = ("value", "unit", "ms_per_step", "steps", "warmup", "config", "roofline", "kernels_ms", "phases", "cpu_baseline", "parity_vs_oracle", "hbm_used_gb")
         # (batch4k_96img: the headline's 64 images are four chains of 16 in flight and the chain's latency, not the chip, bounds

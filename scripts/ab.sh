@@ -15,7 +15,7 @@ if [ -n "$GATE" ]; then
 fi
 P='import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d["value"]), d["ms_per_step"], {k: round(v["ms"]/v["launches"]*1000) for k,v in d.get("kernels_ms", {}).items()})'
-run() { side=$1; lib=$2; shift; shift; echo -n "$side [$*] : "; LQR_HIP_LIB=$lib timeout 600 python bench.py --steps ${STEPS:-3} --warmup ${WARMUP:-1} --no-configs --no-cpu-baseline --no-phases --kernel-times "$@" 2>>$O/bench.err | python3 -c "$P"; }
+run() { side=$1; lib=$2; shift; shift; echo -n "$side [$*] : "; LQR_HIP_LIB=$lib timeout 600 python bench.py --full --steps ${STEPS:-3} --warmup ${WARMUP:-1} --no-configs --no-cpu-baseline --no-phases --kernel-times "$@" 2>>$O/bench.err | python3 -c "$P"; }
 for n in $images; do for r in $(seq $reps); do
   run A "$LIB_A" --images-per-gpu $n $A
   run B "$LIB_B" --images-per-gpu $n $B

@@ -13,7 +13,7 @@ mkdir -p $O
 cd $R
 stats() {   # stats NAME bench-args...
   name=$1; shift
-  timeout -s KILL 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -- python $R/bench.py --no-cpu-baseline --no-phases --no-configs --no-kernel-breakdown "$@" > $O/${name}_prof.log 2>&1
+  timeout -s KILL 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -- python $R/bench.py --full --no-cpu-baseline --no-phases --no-configs --no-kernel-breakdown "$@" > $O/${name}_prof.log 2>&1
   find /tmp/prof_$name -name "*kernel_stats.csv" -exec cp {} $O/${name}_kernel_stats.csv \;
   grep '^{' $O/${name}_prof.log | tail -1 > $O/${name}_bench_under_rocprof.json
   rm -rf /tmp/prof_$name $O/${name}_prof.log
@@ -55,16 +55,16 @@ PY
 for w in $what; do
 case $w in
 batch)
-  timeout -s KILL 900 python $R/bench.py --steps 20 --warmup 5 > $O/driver_cmd_bench.json 2> $O/driver_cmd_bench.err
+  timeout -s KILL 900 python $R/bench.py --full --steps 20 --warmup 5 > $O/driver_cmd_bench.json 2> $O/driver_cmd_bench.err
   cut -c1-1200 $O/driver_cmd_bench.json; echo
-  timeout -s KILL 400 python $R/bench.py --steps 5 --warmup 2 --sub-batches 1 --no-cpu-baseline --no-phases --no-configs > $O/batch4k_one_stream_bench.json 2>> $O/driver_cmd_bench.err
-  timeout -s KILL 400 python $R/bench.py --steps 5 --warmup 2 --images-per-gpu 8 --no-cpu-baseline --no-phases --no-configs > $O/batch4k_8img_bench.json 2>> $O/driver_cmd_bench.err
-  timeout -s KILL 400 python $R/bench.py --steps 5 --warmup 2 --images-per-gpu 16 --no-cpu-baseline --no-phases --no-configs > $O/batch4k_16img_bench.json 2>> $O/driver_cmd_bench.err
-  timeout -s KILL 600 python $R/bench.py --steps 2 --warmup 1 --images-per-gpu 16 --delta 2 --no-cpu-baseline --no-phases --no-configs > $O/batch4k_16img_delta2_bench.json 2>> $O/driver_cmd_bench.err
-  timeout -s KILL 600 python $R/bench.py --steps 2 --warmup 1 --images-per-gpu 16 --delta 3 --no-cpu-baseline --no-phases --no-configs > $O/batch4k_16img_delta3_bench.json 2>> $O/driver_cmd_bench.err
-  timeout -s KILL 400 python $R/bench.py --steps 5 --warmup 2 --images-per-gpu 32 --no-cpu-baseline --no-phases --no-configs > $O/batch4k_32img_bench.json 2>> $O/driver_cmd_bench.err
-  timeout -s KILL 600 python $R/bench.py --workload config5 --delta 2 --steps 1 --warmup 1 --no-cpu-baseline --no-configs > $O/config5_delta2_bench.json 2>> $O/driver_cmd_bench.err
-  timeout -s KILL 600 python $R/bench.py --workload config5 --rigmask --steps 1 --warmup 1 --no-cpu-baseline --no-configs > $O/config5_rigmask_bench.json 2>> $O/driver_cmd_bench.err
+  timeout -s KILL 400 python $R/bench.py --full --steps 5 --warmup 2 --sub-batches 1 --no-cpu-baseline --no-phases --no-configs > $O/batch4k_one_stream_bench.json 2>> $O/driver_cmd_bench.err
+  timeout -s KILL 400 python $R/bench.py --full --steps 5 --warmup 2 --images-per-gpu 8 --no-cpu-baseline --no-phases --no-configs > $O/batch4k_8img_bench.json 2>> $O/driver_cmd_bench.err
+  timeout -s KILL 400 python $R/bench.py --full --steps 5 --warmup 2 --images-per-gpu 16 --no-cpu-baseline --no-phases --no-configs > $O/batch4k_16img_bench.json 2>> $O/driver_cmd_bench.err
+  timeout -s KILL 600 python $R/bench.py --full --steps 2 --warmup 1 --images-per-gpu 16 --delta 2 --no-cpu-baseline --no-phases --no-configs > $O/batch4k_16img_delta2_bench.json 2>> $O/driver_cmd_bench.err
+  timeout -s KILL 600 python $R/bench.py --full --steps 2 --warmup 1 --images-per-gpu 16 --delta 3 --no-cpu-baseline --no-phases --no-configs > $O/batch4k_16img_delta3_bench.json 2>> $O/driver_cmd_bench.err
+  timeout -s KILL 400 python $R/bench.py --full --steps 5 --warmup 2 --images-per-gpu 32 --no-cpu-baseline --no-phases --no-configs > $O/batch4k_32img_bench.json 2>> $O/driver_cmd_bench.err
+  timeout -s KILL 600 python $R/bench.py --full --workload config5 --delta 2 --steps 1 --warmup 1 --no-cpu-baseline --no-configs > $O/config5_delta2_bench.json 2>> $O/driver_cmd_bench.err
+  timeout -s KILL 600 python $R/bench.py --full --workload config5 --rigmask --steps 1 --warmup 1 --no-cpu-baseline --no-configs > $O/config5_rigmask_bench.json 2>> $O/driver_cmd_bench.err
   for f in batch4k_one_stream batch4k_8img batch4k_16img batch4k_32img batch4k_16img_delta2 batch4k_16img_delta3 config5_delta2 config5_rigmask; do python -c "
 import json; d=json.load(open('$O/${f}_bench.json')); print('$f', d['value'], d['ms_per_step'])"; done ;;
 stats)

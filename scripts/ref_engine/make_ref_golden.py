@@ -178,9 +178,13 @@ def planes():
         index.append(dict(key="dp_" + name, kind="dp", variant=name, updates=k, stale=int((dx == -999).sum())))
         c.destroy()
     a.close()
-    arrays["index"] = np.array(json.dumps(index))
-    np.savez_compressed(os.path.join(OUT, "planes.npz"), **arrays)
-    return dict(group="planes", name="planes", file="planes.npz", entries=len(index))
+    entries = []
+    for part in ("energy", "dp"):           # two files, each under the 1 MiB a committed file may have
+        idx = [e for e in index if e["kind"] == part]
+        keys = [k for k in arrays if k.startswith(("en_", "dp_")[part == "dp"])]
+        np.savez_compressed(os.path.join(OUT, "planes_%s.npz" % part), index=np.array(json.dumps(idx)), **{k: arrays[k] for k in keys})
+        entries.append(dict(group="planes", name="planes_" + part, file="planes_%s.npz" % part, entries=len(idx)))
+    return entries
 
 
 def main():
@@ -219,7 +223,7 @@ def main():
         new = [dict(group="interactive", name=e["name"], file="interactive.json", genuine_defect=e["genuine_defect"], same_as_shipped=e["same_as_shipped"])
                if e["group"] == "interactive" else e for e in new]
     if "planes" in groups:
-        new.append(planes())
+        new += planes()
     exe = R.exe_bytes()
     manifest = dict(source="gimp-lqr-plugin.exe inside /root/reference/windows_installer_files/lqr-pack4win/.zip (liblqr 0.4.1 statically linked, "
                            "winpack.sh:8,52-57), executed by scripts/ref_engine/refrun.c",

@@ -12,7 +12,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "1", "--warmup", "0", "--images-per-gpu", "3", "--seams", "40", "--no-configs", "--no-cpu-baseline", "--no-phases", "--no-kernel-breakdown"]
+COMMON = ["--full", "--steps", "1", "--warmup", "0", "--images-per-gpu", "3", "--seams", "40", "--no-configs", "--no-cpu-baseline", "--no-phases", "--no-kernel-breakdown"]
 
 
 def run(cmd, env=None):

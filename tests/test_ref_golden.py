@@ -204,8 +204,14 @@ def test_oracle_reproduces_the_genuine_engine_interactive(oracle, entry):
 
 
 def planes_index():
-    z = np.load(os.path.join(REF, "planes.npz"))
-    return z, json.loads(str(z["index"]))
+    """the planes fixture, kept in two files of its own index each (energies, DP planes): every array and the whole index"""
+    z, index = {}, []
+    for v in vectors("planes"):
+        with np.load(os.path.join(REF, v["file"])) as part:
+            z.update((k, part[k]) for k in part.files if k != "index")
+            index += json.loads(str(part["index"]))
+    assert len(index) == 67, len(index)
+    return z, index
 
 
 def check_planes(api):
