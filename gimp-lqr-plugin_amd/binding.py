@@ -105,6 +105,32 @@ SYMBOLS = {
 # liblqr-1 proper exports only the lqr_* part
 LIBLQR_SYMBOLS = [s for s in SYMBOLS if s.startswith("lqr_")]
 
+# include/lqr_coldepth.h: the colour-depth surface (liblqr 0.4's lqr_carver_new_ext and its read-out), kept apart from SYMBOLS,
+# which is exactly what lqr.h declares
+LQR_COLDEPTH_8I, LQR_COLDEPTH_16I, LQR_COLDEPTH_32F, LQR_COLDEPTH_64F = range(4)
+COLDEPTH_DTYPES = {LQR_COLDEPTH_8I: np.uint8, LQR_COLDEPTH_16I: np.uint16, LQR_COLDEPTH_32F: np.float32, LQR_COLDEPTH_64F: np.float64}
+COLDEPTH_SYMBOLS = {
+    "lqr_carver_new_ext": (_P, [_P, _I, _I, _I, _I]),
+    "lqr_carver_set_preserve_input_image": (None, [_P]),
+    "lqr_carver_scan": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_P)]),
+    "lqr_carver_scan_ext": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_P)]),
+    "lqr_carver_scan_line_ext": (_I, [_P, C.POINTER(_I), C.POINTER(_P)]),
+    "lqr_carver_get_col_depth": (_I, [_P]),
+    "lqr_carver_get_image_type": (_I, [_P]),
+    "lqr_carver_get_bpp": (_I, [_P]),
+}
+
+
+def bind_coldepth(api):
+    """add COLDEPTH_SYMBOLS to a bound Api (the engine, or a genuine liblqr-1); returns it"""
+    if not getattr(api, "has_coldepth", False):
+        for name, (res, args) in COLDEPTH_SYMBOLS.items():
+            fn = getattr(api.lib, api.prefix + name)      # AttributeError = missing export
+            fn.restype, fn.argtypes = res, args
+            setattr(api, name, fn)
+        api.has_coldepth = True
+    return api
+
 
 class Api:
     """Resolved function table of one library exporting the ABI."""
@@ -129,6 +155,11 @@ def engine_api():
             raise RuntimeError("HIP engine library missing: %s (run python -c 'import __graft_entry__ as g; g.build()')" % ENGINE_LIB)
         _apis["engine"] = Api(ENGINE_LIB, "")
     return _apis["engine"]
+
+
+def engine_coldepth_api():
+    """the engine with the colour-depth surface bound"""
+    return bind_coldepth(engine_api())
 
 
 def _malloc_copy(arr):
@@ -176,6 +207,132 @@ class Carver:
         ret = api.lqr_carver_init(self.p, delta_x, float(rigidity))
         assert ret == LQR_OK, ret
         return self
+
+    @classmethod
+    def from_ext(cls, api, array, depth=None, init=True, delta_x=1, rigidity=0.0, preserve=False):
+        """lqr_carver_new_ext on an h x w (x ch) array of the depth's dtype (depth: LqrColDepth, by default from the dtype).
+        preserve=False: the library owns a malloc'ed copy, as liblqr callers hand theirs over.  preserve=True: the carver reads
+        the caller's buffer (self.buffer, a numpy array kept alive here) under lqr_carver_set_preserve_input_image"""
+        bind_coldepth(api)
+        array = np.asarray(array)
+        if depth is None:
+            depth = {np.dtype(v): k for k, v in COLDEPTH_DTYPES.items()}[array.dtype]
+        array = np.ascontiguousarray(array, dtype=COLDEPTH_DTYPES[depth])
+        if array.ndim == 2:
+            array = array[:, :, None]
+        self = cls.__new__(cls)
+        self.api = api
+        self.h0, self.w0, self.ch = array.shape
+        self.depth = depth
+        self._cbs, self.events, self.aux = [], [], []
+        if preserve:
+            self.buffer = array.copy()
+            ptr = self.buffer.ctypes.data
+        else:
+            self.buffer = None
+            ptr = _malloc_copy(array.view(np.uint8))
+        self.p = api.lqr_carver_new_ext(ptr, self.w0, self.h0, self.ch, depth)
+        if not self.p:
+            raise MemoryError("lqr_carver_new_ext returned NULL")
+        if preserve:
+            api.lqr_carver_set_preserve_input_image(self.p)
+        if init:
+            ret = api.lqr_carver_init(self.p, delta_x, float(rigidity))
+            assert ret == LQR_OK, ret
+        return self
+
+    def attach_ext(self, array, depth=None):
+        """an attached carver of any depth"""
+        aux = Carver.from_ext(self.api, array, depth, init=False)
+        ret = self.api.lqr_carver_attach(self.p, aux.p)
+        assert ret == LQR_OK, ret
+        self.aux.append(aux)
+        return aux
+
+    def _px(self):
+        depth = getattr(self, "depth", LQR_COLDEPTH_8I)
+        dt = np.dtype(COLDEPTH_DTYPES[depth])
+        return dt, self.ch * dt.itemsize
+
+    def scan_partial(self):
+        """a lqr_carver_scan_ext loop given up part-way: all but the last pixel of the first line; returns the pixels visited"""
+        a = self.api
+        W, H = a.lqr_carver_get_width(self.p), a.lqr_carver_get_height(self.p)
+        n = (W if a.lqr_carver_scan_by_row(self.p) else H) - 1
+        x, y, px = C.c_int(0), C.c_int(0), C.c_void_p()
+        a.lqr_carver_scan_reset(self.p)
+        for _ in range(n):
+            assert a.lqr_carver_scan_ext(self.p, C.byref(x), C.byref(y), C.byref(px))
+        return n
+
+    def scan_ext(self, reset=True):
+        """the lqr_carver_scan_ext loop: (image, [(x, y) in visiting order]); reset=False: from wherever the cursor is"""
+        a = self.api
+        dt, nb = self._px()
+        W, H = a.lqr_carver_get_width(self.p), a.lqr_carver_get_height(self.p)
+        out = np.zeros((H, W, self.ch), dt)
+        x, y, px = C.c_int(0), C.c_int(0), C.c_void_p()
+        order = []
+        if reset:
+            a.lqr_carver_scan_reset(self.p)
+        while a.lqr_carver_scan_ext(self.p, C.byref(x), C.byref(y), C.byref(px)):
+            out[y.value, x.value] = np.frombuffer(C.string_at(px.value, nb), dt)
+            order.append((x.value, y.value))
+        return out, order
+
+    def scan_line_ext(self):
+        """the lqr_carver_scan_line_ext loop: (image, [line numbers in order])"""
+        a = self.api
+        dt, nb = self._px()
+        W, H = a.lqr_carver_get_width(self.p), a.lqr_carver_get_height(self.p)
+        out = np.zeros((H, W, self.ch), dt)
+        n, line = C.c_int(0), C.c_void_p()
+        lines = []
+        a.lqr_carver_scan_reset(self.p)
+        while a.lqr_carver_scan_line_ext(self.p, C.byref(n), C.byref(line)):
+            by_row = a.lqr_carver_scan_by_row(self.p)
+            length = W if by_row else H
+            buf = np.frombuffer(C.string_at(line.value, length * nb), dt).reshape(length, self.ch)
+            if by_row:
+                out[n.value] = buf
+            else:
+                out[:, n.value] = buf
+            lines.append(n.value)
+        return out, lines
+
+    def read_image_ext(self):
+        """lqrx_carver_read_image at the carver's depth (engine only)"""
+        a = self.api
+        dt, _ = self._px()
+        W, H = a.lqr_carver_get_width(self.p), a.lqr_carver_get_height(self.p)
+        out = np.zeros((H, W, self.ch), dt)
+        assert a.lqrx_carver_read_image(self.p, out.ctypes.data) == LQR_OK
+        return out
+
+    def input_bytes(self):
+        """the caller's buffer as it is now (preserve=True only)"""
+        return self.buffer.tobytes()
+
+    def free_input(self):
+        """(preserve=True: the buffer is self.buffer, numpy's; nothing to hand back)"""
+
+    def scan_rets(self):
+        """what the 8-bit scans return on this carver (first call after a reset)"""
+        a = self.api
+        x, y, px = C.c_int(0), C.c_int(0), C.c_void_p()
+        a.lqr_carver_scan_reset(self.p)
+        r1 = a.lqr_carver_scan(self.p, C.byref(x), C.byref(y), C.byref(px))
+        a.lqr_carver_scan_reset(self.p)
+        r2 = a.lqr_carver_scan_line(self.p, C.byref(x), C.byref(px))
+        a.lqr_carver_scan_reset(self.p)
+        return [r1, r2]
+
+    def getters_ext(self):
+        a = self.api
+        g = self.getters()
+        g.update(col_depth=a.lqr_carver_get_col_depth(self.p), image_type=a.lqr_carver_get_image_type(self.p),
+                 bpp=a.lqr_carver_get_bpp(self.p))
+        return g
 
     # -- configuration, in the order of render.c:225-248 ------------------
     def bias_add(self, mask, factor, x_off=0, y_off=0):

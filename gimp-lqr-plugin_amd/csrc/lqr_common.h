@@ -540,6 +540,11 @@ struct InflateDev {
     float *nbias, *nrig;
     int ch;
 };
+// a job of k_inflate_deep: the carver's depth (LqrColDepth 1 .. 3) beside its planes; j.ch = channels
+struct InflateDevX {
+    InflateDev j;
+    int depth;
+};
 #define EU_ROWS 62          // k_emap_update: rows per block (+2 halo rows)
 #ifndef EU_LOGB
 #define EU_LOGB 8           // k_emap_update / k_carve_e: log entries fetched per round of the walk back to the frozen frame

@@ -51,3 +51,14 @@ __global__ __launch_bounds__(256) void k_compact(const uint8_t *rgb, const int32
 __global__ __launch_bounds__(256) void k_compact_jobs(const InflateDev *jobs, int w0, int w, int level);
 __global__ void k_transpose(const InflateDev *jobs, int w, int h);
 __global__ __launch_bounds__(256) void k_mask_line_max(const uint8_t *mask, int channels, int width, int a0, int b0, int line_len, int direction, int *out);
+
+// k_deep.hip (carvers of depth 16I / 32F / 64F; `pix` holds one double per pixel)
+template <int DEPTH> __global__ void k_wk_init_deep(const DevCarver *cs, int w, int h, int stride, int ch, int luma);
+template <int DEPTH> __global__ __launch_bounds__(256) void k_wk_init_visible_deep(const DevCarver *cs, int w0, int h, int stride, int ch, int luma);
+template <int NRG> __global__ void k_emap_full_deep(const DevCarver *cs, DpK p, int w, int h, int stride);
+template <int NRG, int EU_NT> __global__ __launch_bounds__(64) void k_emap_update_deep(const DevCarver *cs, DpK p, int w, int h, int stride, int k, int epoch);
+__global__ __launch_bounds__(256) void k_frozen_catchup_deep(const DevCarver *cs, int from, int to, int w_from, int h, int stride);
+__global__ __launch_bounds__(256) void k_inflate_deep(const InflateDevX *jobs, int w0, int w1, int l, int max_level, int *dev_err);
+__global__ void k_transpose_px(const InflateDev *jobs, int w, int h);
+__global__ __launch_bounds__(256) void k_compact_wide(const uint8_t *rgb, const int32_t *vs, uint8_t *nrgb, int w0, int w, int bytes, int level);
+__global__ __launch_bounds__(256) void k_compact_jobs_wide(const InflateDev *jobs, int w0, int w, int level);

@@ -35,6 +35,8 @@ static int g_n_cu = 0;
 // ===========================================================================
 struct LqrHipCarver {
     int ch = 0;
+    int depth = 0;                   // LqrColDepth: 0 8I (pixels packed in `pix`), 1 .. 3 16I / 32F / 64F (`pix` holds a double per pixel, k_deep.hip)
+    int luma = 0;                    // (depth > 0) the value in `pix` is luma, not brightness
     int w0 = 0, h0 = 0;              // base layout dims
     // base planes
     uint8_t *rgb0 = nullptr;
@@ -528,6 +530,9 @@ static int d2h_staged(void *dst, const void *src, size_t bytes)
     return rc;
 }
 
+// bytes per pixel of the base layout
+static inline size_t px_bytes(const LqrHipCarver *c) { return (size_t) c->ch << (c->depth == 0 ? 0 : c->depth == 1 ? 1 : c->depth == 2 ? 2 : 3); }
+
 static int batch_sync_of(LqrHipCarver *c)
 {
     LqrHipCarver *r = c->root ? c->root : c;
@@ -535,20 +540,34 @@ static int batch_sync_of(LqrHipCarver *c)
     return 0;
 }
 
-extern "C" LqrHipCarver *lqrhip_carver_create(const unsigned char *rgb, int w, int h, int channels)
+// the base layout: w x h pixels of `channels` values of `depth` (LqrColDepth: 1 / 2 / 4 / 8 bytes each)
+extern "C" LqrHipCarver *lqrhip_carver_create_ext(const void *rgb, int w, int h, int channels, int depth)
 {
+    if (depth < 0 || depth > 3 || channels < 1 || channels > 4) { g_err = "unsupported colour depth / channels"; return nullptr; }
     if (lqrhip_init() < 0) return nullptr;
     LqrHipCarver *c = new LqrHipCarver();
-    c->ch = channels; c->w0 = w; c->h0 = h;
-    size_t n = (size_t) w * h;
-    if (dmalloc(&c->rgb0, n * channels) || dmalloc(&c->vs, n)) { lqrhip_carver_destroy(c); return nullptr; }
+    c->ch = channels; c->depth = depth; c->w0 = w; c->h0 = h;
+    const size_t n = (size_t) w * h, bytes = n * px_bytes(c);
+    if (dmalloc(&c->rgb0, bytes) || dmalloc(&c->vs, n)) { lqrhip_carver_destroy(c); return nullptr; }
     // the visibility map is cleared on the same stream, under the upload: one synchronisation for both
-    if (hipMemsetAsync(c->vs, 0, n * sizeof(int32_t), g_stream0) != hipSuccess || h2d_staged(c->rgb0, rgb, n * channels) != 0) {
+    if (hipMemsetAsync(c->vs, 0, n * sizeof(int32_t), g_stream0) != hipSuccess || h2d_staged(c->rgb0, rgb, bytes) != 0) {
         g_err = "upload failed";
         lqrhip_carver_destroy(c);
         return nullptr;
     }
     return c;
+}
+
+extern "C" LqrHipCarver *lqrhip_carver_create(const unsigned char *rgb, int w, int h, int channels)
+{
+    return lqrhip_carver_create_ext(rgb, w, h, channels, 0);
+}
+
+extern "C" int lqrhip_carver_set_read_luma(LqrHipCarver *c, int luma)
+{
+    const int changed = c->depth != 0 && (luma != 0) != (c->luma != 0);
+    c->luma = luma != 0;
+    return changed;
 }
 
 static void free_working(LqrHipCarver *c)
@@ -598,8 +617,9 @@ static int ensure_working(LqrHipCarver *c, int w, int h)
     free_working(c);
     c->stride = 0; c->wk_h = 0;
     size_t n = (size_t) stride * (h + 1) + 1024;
+    const size_t npix = c->depth ? 2 * n : n;          // a deep carver's plane holds a double per pixel
     int rc;
-    if ((rc = dmalloc(&c->pix, n)) || (rc = dmalloc(&c->en, n)) || (rc = dmalloc(&c->m, n)) || (rc = dmalloc(&c->least, n)) ||
+    if ((rc = dmalloc(&c->pix, npix)) || (rc = dmalloc(&c->en, n)) || (rc = dmalloc(&c->m, n)) || (rc = dmalloc(&c->least, n)) ||
         (rc = dmalloc(&c->seam_x, (size_t) h + 8)) || (rc = dmalloc(&c->flags, (size_t) FLAG_WORDS)) ||
         (need_bias && (rc = dmalloc(&c->bias, n))) || (need_rig && (rc = dmalloc(&c->rig, n)))) {
         free_working(c);            // never leave a half-allocated set behind: a retry must not pass the early-out above
@@ -609,7 +629,7 @@ static int ensure_working(LqrHipCarver *c, int w, int h)
     hipError_t e = hipMemsetAsync(c->least, 0, n, g_stream0);
     if (e == hipSuccess) e = hipMemsetAsync(c->m, 0, n * sizeof(float), g_stream0);
     if (e == hipSuccess) e = hipMemsetAsync(c->en, 0, n * sizeof(float), g_stream0);
-    if (e == hipSuccess) e = hipMemsetAsync(c->pix, 0, n * sizeof(uint32_t), g_stream0);
+    if (e == hipSuccess) e = hipMemsetAsync(c->pix, 0, npix * sizeof(uint32_t), g_stream0);
     if (e == hipSuccess) e = hipMemsetAsync(c->flags, 0, (size_t) FLAG_WORDS * sizeof(int32_t), g_stream0);
     if (e == hipSuccess) e = hipStreamSynchronize(g_stream0);
     if (e != hipSuccess) { free_working(c); HIPCK(e); }
@@ -884,12 +904,18 @@ extern "C" int lqrhip_wk_init(LqrHipBatch *b, int from_visible)
     LqrHipCarver *c0 = b->cs[0];
     int w = c0->w0, h = c0->h0, rc;
     for (auto *c : b->cs) {
-        if (c->w0 != w || c->h0 != h || c->ch != c0->ch) return LQRHIP_EARG;
+        if (c->w0 != w || c->h0 != h || c->ch != c0->ch || c->depth != c0->depth || c->luma != c0->luma) return LQRHIP_EARG;
         if ((rc = ensure_working(c, w, h))) return rc;
     }
     if ((rc = batch_upload(b))) return rc;
     for (auto *c : b->cs) c->frozen_epoch = 0;
-    if (from_visible) {
+    if (c0->depth) {
+        const dim3 grid((c0->stride + 255) / 256, h, (unsigned) b->cs.size()), grid_v(h, (unsigned) b->cs.size());
+#define LAUNCH_WKD(D) do { if (from_visible) hipLaunchKernelGGL(k_wk_init_visible_deep<D>, grid_v, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, c0->ch, c0->luma); \
+                           else hipLaunchKernelGGL(k_wk_init_deep<D>, grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, c0->ch, c0->luma); } while (0)
+        if (c0->depth == 1) LAUNCH_WKD(1); else if (c0->depth == 2) LAUNCH_WKD(2); else LAUNCH_WKD(3);
+#undef LAUNCH_WKD
+    } else if (from_visible) {
         hipLaunchKernelGGL(k_wk_init_visible, dim3(h, (unsigned) b->cs.size()), dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, c0->ch);
     } else {
         dim3 grid((c0->stride + 255) / 256, h, (unsigned) b->cs.size());
@@ -906,9 +932,15 @@ extern "C" int lqrhip_emap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w,
     LqrHipCarver *c0 = b->cs[0];
     dim3 grid((w + 255) / 256, h, (unsigned) b->cs.size());
     DpK k = make_dpk(p, c0->ch);
+    if (c0->depth) {
+#define LAUNCH_EMAP(N) hipLaunchKernelGGL((k_emap_full_deep<N>), grid, dim3(256), 0, b->stream, b->d_desc, k, w, h, c0->stride)
+        NRG_DISPATCH(p->nrg_func, LAUNCH_EMAP)
+#undef LAUNCH_EMAP
+    } else {
 #define LAUNCH_EMAP(N) hipLaunchKernelGGL((k_emap_full<N>), grid, dim3(256), 0, b->stream, b->d_desc, k, w, h, c0->stride)
     NRG_DISPATCH(p->nrg_func, LAUNCH_EMAP)
 #undef LAUNCH_EMAP
+    }
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -1149,6 +1181,10 @@ static int frozen_catchup(LqrHipBatch *b, int to, int w_at_to, int h)
     if (to <= from) return 0;
     const int w_from = w_at_to + (to - from);
     size_t lds = (size_t) (to - from) * sizeof(int) + (size_t) w_from + 16;
+    if (c0->depth)
+        hipLaunchKernelGGL(k_frozen_catchup_deep, dim3(h, (unsigned) b->cs.size()), dim3(256), lds, b->stream, b->d_desc, from, to, w_from, h,
+                           c0->stride);
+    else
     hipLaunchKernelGGL(k_frozen_catchup, dim3(h, (unsigned) b->cs.size()), dim3(256), lds, b->stream, b->d_desc, from, to, w_from, h,
                        c0->stride);
     HIPCK(hipGetLastError());
@@ -1330,7 +1366,8 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
     }
     // Single images and groups up to 4: the carve and the energy update in one launch (k_carve_e, k_carve.hip) -- the wave that has moved
     // a row refreshes that row's energies; one dependent launch less per seam.  delta_x <= 2 (12 brightness samples per row).
-    const bool fuse_e = p->delta_x <= 2 && vp_group <= (size_t) g_carve_fused && wnew > 1;
+    // (deep carvers: the two kernels, k_carve and k_emap_update_deep)
+    const bool fuse_e = p->delta_x <= 2 && vp_group <= (size_t) g_carve_fused && wnew > 1 && c0->depth == 0;
     if (fuse_e) {
         const int lag_max = n <= 4 ? FROZEN_LAG_MAX / 4 : FROZEN_LAG_MAX;
         if (log_index + 1 - c0->frozen_epoch > lag_max && (rc = frozen_catchup(b, log_index + 1, wnew, h))) return rc;      // (needs the seam log only: before the carve)
@@ -1360,7 +1397,12 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
         const int epoch = c0->frozen_epoch;
 #define LAUNCH_EUPD_NT(N, NT) hipLaunchKernelGGL((k_emap_update<N, NT>), dim3((h + EU_ROWS - 1) / EU_ROWS, n), dim3(64), 0, b->stream, b->d_desc, k, wnew, h, stride, log_index, epoch)
 #define LAUNCH_EUPD(N) do { if (p->delta_x <= 2) LAUNCH_EUPD_NT(N, 12); else if (p->delta_x <= 8) LAUNCH_EUPD_NT(N, 36); else LAUNCH_EUPD_NT(N, 68); } while (0)
-        NRG_DISPATCH(p->nrg_func, LAUNCH_EUPD)
+#define LAUNCH_EUPD_NT_DEEP(N, NT) hipLaunchKernelGGL((k_emap_update_deep<N, NT>), dim3((h + EU_ROWS - 1) / EU_ROWS, n), dim3(64), 0, b->stream, b->d_desc, k, wnew, h, stride, log_index, epoch)
+#define LAUNCH_EUPD_DEEP(N) do { if (p->delta_x <= 2) LAUNCH_EUPD_NT_DEEP(N, 12); else if (p->delta_x <= 8) LAUNCH_EUPD_NT_DEEP(N, 36); else LAUNCH_EUPD_NT_DEEP(N, 68); } while (0)
+        if (c0->depth) { NRG_DISPATCH(p->nrg_func, LAUNCH_EUPD_DEEP) }
+        else { NRG_DISPATCH(p->nrg_func, LAUNCH_EUPD) }
+#undef LAUNCH_EUPD_DEEP
+#undef LAUNCH_EUPD_NT_DEEP
 #undef LAUNCH_EUPD
 #undef LAUNCH_EUPD_NT
     }
@@ -1544,10 +1586,17 @@ struct PlaneJobs {
     std::vector<InflateDev> dev;
     std::vector<int32_t *> new_vs;          // one per root (may be null)
     InflateDev *d_jobs = nullptr;
+    // the jobs split by the kernel that takes them: `dev` holds ch = bytes per pixel (compaction moves bytes); inflate and transpose
+    // keep 8-bit / narrow pixels on their 8-bit kernels and hand the others to k_deep.hip's (split())
+    std::vector<int> depth;                 // per job of `dev`
+    std::vector<InflateDev> dev8, devw;     // inflate: 8-bit jobs (ch = channels); transpose: pixels of <= 4 bytes; ...
+    std::vector<InflateDevX> devx;          // ... inflate: deep jobs (ch = channels)
+    InflateDev *d_jobs8 = nullptr, *d_jobsw = nullptr;
+    InflateDevX *d_jobsx = nullptr;
     bool committed = false;
     ~PlaneJobs()
     {
-        dfree(d_jobs);
+        dfree(d_jobs); dfree(d_jobs8); dfree(d_jobsw); dfree(d_jobsx);
         if (committed) return;
         for (auto &j : jobs) { dfree(j.nrgb); dfree(j.nbias); dfree(j.nrig); }
         for (auto *&v : new_vs) dfree(v);
@@ -1556,12 +1605,30 @@ struct PlaneJobs {
     int add(LqrHipCarver *c, const int32_t *vs_old, int32_t *nvs, size_t n1)
     {
         PlaneJob j{c, nullptr, nullptr, nullptr};
-        int rc = dmalloc(&j.nrgb, n1 * c->ch);
+        int rc = dmalloc(&j.nrgb, n1 * px_bytes(c));
         if (!rc && c->bias0) rc = dmalloc(&j.nbias, n1);
         if (!rc && c->rig0) rc = dmalloc(&j.nrig, n1);
         jobs.push_back(j);                  // owned from here on, also when rc != 0
         if (rc) return rc;
-        dev.push_back(InflateDev{c->rgb0, vs_old, c->bias0, c->rig0, j.nrgb, nvs, j.nbias, j.nrig, c->ch});
+        dev.push_back(InflateDev{c->rgb0, vs_old, c->bias0, c->rig0, j.nrgb, nvs, j.nbias, j.nrig, (int) px_bytes(c)});
+        depth.push_back(c->depth);
+        return 0;
+    }
+    // inflate (by_width = false): 8-bit jobs -> dev8, the others -> devx; transpose and flatten (by_width): pixels of up to 4 bytes ->
+    // dev8 (the 8-bit kernels move them as bytes / one dword), wider ones -> devw (k_deep.hip's kernels, 16-byte accesses where they fit)
+    int split(hipStream_t s, bool by_width)
+    {
+        for (size_t i = 0; i < dev.size(); i++) {
+            InflateDev d = dev[i];
+            if (by_width) { (d.ch <= 4 ? dev8 : devw).push_back(d); continue; }
+            if (depth[i] == 0) { dev8.push_back(d); continue; }
+            d.ch = d.ch >> (depth[i] == 1 ? 1 : depth[i] == 2 ? 2 : 3);
+            devx.push_back(InflateDevX{d, depth[i]});
+        }
+        int rc;
+        if (!dev8.empty()) { if ((rc = dmalloc(&d_jobs8, dev8.size()))) return rc; HIPCK(hipMemcpyAsync(d_jobs8, dev8.data(), dev8.size() * sizeof(InflateDev), hipMemcpyHostToDevice, s)); }
+        if (!devw.empty()) { if ((rc = dmalloc(&d_jobsw, devw.size()))) return rc; HIPCK(hipMemcpyAsync(d_jobsw, devw.data(), devw.size() * sizeof(InflateDev), hipMemcpyHostToDevice, s)); }
+        if (!devx.empty()) { if ((rc = dmalloc(&d_jobsx, devx.size()))) return rc; HIPCK(hipMemcpyAsync(d_jobsx, devx.data(), devx.size() * sizeof(InflateDevX), hipMemcpyHostToDevice, s)); }
         return 0;
     }
     int upload(hipStream_t s)
@@ -1612,9 +1679,12 @@ extern "C" int lqrhip_inflate(LqrHipBatch *b, int w0, int h0, int l, int max_lev
                 if ((rc = pj.add(a, c->vs, nullptr, (size_t) w1 * h0))) return rc;
             if ((rc = pj.add(c, c->vs, nvs, (size_t) w1 * h0))) return rc;
         }
-        if ((rc = pj.upload(b->stream))) return rc;
+        if ((rc = pj.split(b->stream, false))) return rc;
         const size_t lds = (size_t) ((l - max_level + 1 + 31) / 32 + 1) * sizeof(unsigned);      // one bit per level of the session (the fused self-check)
-        hipLaunchKernelGGL(k_inflate, dim3(h0, (unsigned) pj.dev.size()), dim3(256), lds, b->stream, pj.d_jobs, w0, w1, l, max_level, g_selfcheck ? g_dev_err : (int *) nullptr);
+        if (!pj.dev8.empty())
+            hipLaunchKernelGGL(k_inflate, dim3(h0, (unsigned) pj.dev8.size()), dim3(256), lds, b->stream, pj.d_jobs8, w0, w1, l, max_level, g_selfcheck ? g_dev_err : (int *) nullptr);
+        if (!pj.devx.empty())
+            hipLaunchKernelGGL(k_inflate_deep, dim3(h0, (unsigned) pj.devx.size()), dim3(256), lds, b->stream, pj.d_jobsx, w0, w1, l, max_level, g_selfcheck ? g_dev_err : (int *) nullptr);
         HIPCK(hipGetLastError());
         HIPCK(hipStreamSynchronize(b->stream));
         return check_dev_error();           // a failed level check: nothing is adopted, the host rolls the session back
@@ -1658,8 +1728,11 @@ extern "C" int lqrhip_flatten(LqrHipBatch *b, int w0, int h0, int w, int level)
                 if ((rc = pj.add(a, c->vs, nullptr, (size_t) w * h0))) return rc;
             if ((rc = pj.add(c, c->vs, nullptr, (size_t) w * h0))) return rc;
         }
-        if ((rc = pj.upload(b->stream))) return rc;
-        hipLaunchKernelGGL(k_compact_jobs, dim3(h0, (unsigned) pj.dev.size()), dim3(256), 0, b->stream, pj.d_jobs, w0, w, level);
+        if ((rc = pj.split(b->stream, true))) return rc;
+        if (!pj.dev8.empty())
+            hipLaunchKernelGGL(k_compact_jobs, dim3(h0, (unsigned) pj.dev8.size()), dim3(256), 0, b->stream, pj.d_jobs8, w0, w, level);
+        if (!pj.devw.empty())
+            hipLaunchKernelGGL(k_compact_jobs_wide, dim3(h0, (unsigned) pj.devw.size()), dim3(256), 0, b->stream, pj.d_jobsw, w0, w, level);
         HIPCK(hipGetLastError());
         HIPCK(hipStreamSynchronize(b->stream));
         return 0;
@@ -1680,8 +1753,11 @@ extern "C" int lqrhip_transpose(LqrHipBatch *b, int w, int h)
             if ((rc = pj.add(c, nullptr, nullptr, (size_t) w * h))) return rc;
             HIPCK(hipMemsetAsync(c->vs, 0, (size_t) w * h * sizeof(int32_t), b->stream));   // flat carver: all zero already
         }
-        if ((rc = pj.upload(b->stream))) return rc;
-        hipLaunchKernelGGL(k_transpose, dim3((w + 31) / 32, (h + 31) / 32, (unsigned) pj.dev.size()), dim3(32, 8), 0, b->stream, pj.d_jobs, w, h);
+        if ((rc = pj.split(b->stream, true))) return rc;
+        if (!pj.dev8.empty())
+            hipLaunchKernelGGL(k_transpose, dim3((w + 31) / 32, (h + 31) / 32, (unsigned) pj.dev8.size()), dim3(32, 8), 0, b->stream, pj.d_jobs8, w, h);
+        if (!pj.devw.empty())
+            hipLaunchKernelGGL(k_transpose_px, dim3((w + 31) / 32, (h + 31) / 32, (unsigned) pj.devw.size()), dim3(32, 8), 0, b->stream, pj.d_jobsw, w, h);
         HIPCK(hipGetLastError());
         HIPCK(hipStreamSynchronize(b->stream));
         return 0;
@@ -1697,11 +1773,14 @@ extern "C" int lqrhip_read_visible(LqrHipCarver *c, int w0, int h0, int w, int l
     int rc = batch_sync_of(c);
     if (rc) return rc;
     uint8_t *d = nullptr;
-    size_t n = (size_t) w * h0 * c->ch;
+    size_t n = (size_t) w * h0 * px_bytes(c);
     if ((rc = dmalloc(&d, n))) return rc;
     auto run = [&]() -> int {
+        if (px_bytes(c) > 4)
+            hipLaunchKernelGGL(k_compact_wide, dim3(h0), dim3(256), 0, g_stream0, c->rgb0, c->vs, d, w0, w, (int) px_bytes(c), level);
+        else
         hipLaunchKernelGGL(k_compact, dim3(h0), dim3(256), 0, g_stream0, c->rgb0, c->vs, (const float *) nullptr, (const float *) nullptr,
-                           d, (float *) nullptr, (float *) nullptr, (int32_t *) nullptr, w0, w, c->ch, level, 0);
+                           d, (float *) nullptr, (float *) nullptr, (int32_t *) nullptr, w0, w, (int) px_bytes(c), level, 0);
         HIPCK(hipGetLastError());
         return d2h_staged(out, d, n);
     };
@@ -1715,8 +1794,11 @@ extern "C" int lqrhip_read_visible_device(LqrHipCarver *c, int w0, int h0, int w
 {
     int rc = batch_sync_of(c);
     if (rc) return rc;
+    if (px_bytes(c) > 4)
+        hipLaunchKernelGGL(k_compact_wide, dim3(h0), dim3(256), 0, g_stream0, c->rgb0, c->vs, (uint8_t *) device_out, w0, w, (int) px_bytes(c), level);
+    else
     hipLaunchKernelGGL(k_compact, dim3(h0), dim3(256), 0, g_stream0, c->rgb0, c->vs, (const float *) nullptr, (const float *) nullptr,
-                       (uint8_t *) device_out, (float *) nullptr, (float *) nullptr, (int32_t *) nullptr, w0, w, c->ch, level, 0);
+                       (uint8_t *) device_out, (float *) nullptr, (float *) nullptr, (int32_t *) nullptr, w0, w, (int) px_bytes(c), level, 0);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(g_stream0));
     return 0;
@@ -1821,14 +1903,14 @@ extern "C" int lqrhip_carver_reset(LqrHipCarver *c, const void *device_rgb, int 
     if (c->bias || c->rig) { free_working(c); c->stride = 0; c->wk_h = 0; }
     c->w0 = w; c->h0 = h;
     c->frozen_epoch = 0;
-    if ((rc = dmalloc(&c->rgb0, n * c->ch)) || (rc = dmalloc(&c->vs, n))) return rc;
+    if ((rc = dmalloc(&c->rgb0, n * px_bytes(c))) || (rc = dmalloc(&c->vs, n))) return rc;
     // (round 6: these copies on four more streams side by side -- one 33 MB device-to-device copy runs at ~0.5 TB/s, 64 of them are 4 ms of a
     // 190-ms step -- made the 64-image step 45 % LONGER: with g_stream0 and the four sub-batch streams that is nine streams on the
     // process's eight hardware queues, and sub-batch streams that share a queue run one after the other.  One stream.)
     {
         // the runtime's device-to-device copy kernel moves a 33 MB image in 66 us (0.5 TB/s; 64 of them: 4.2 ms of a 190-ms step, one after
         // the other); the engine's own streaming copy (k_copy16, the one that measures the HBM ceiling) takes ~10
-        const size_t bytes = n * c->ch, n16 = bytes / 16;
+        const size_t bytes = n * px_bytes(c), n16 = bytes / 16;
         if (n16 && !(((uintptr_t) device_rgb | (uintptr_t) c->rgb0) & 15)) {
             hipLaunchKernelGGL(k_copy16, dim3((unsigned) ((n16 + 255) / 256)), dim3(256), 0, g_stream0, (const u32x4 *) device_rgb, (u32x4 *) c->rgb0, n16);
             HIPCK(hipGetLastError());

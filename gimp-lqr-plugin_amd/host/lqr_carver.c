@@ -21,6 +21,7 @@
 #include <math.h>
 
 #include "../../include/lqr.h"
+#include "../../include/lqr_coldepth.h"
 #include "../../include/lqr_hip.h"
 
 #define MAXI(a, b) ((a) > (b) ? (a) : (b))
@@ -55,6 +56,8 @@ struct _LqrCarver {
     int w_start, h_start, w, h, w0, h0;
     int level, max_level;
     int channels;
+    int col_depth;              /* LqrColDepth: 0 (8I, what lqr_carver_new makes) .. 3 (64F) */
+    int preserve_input;         /* lqr_carver_set_preserve_input_image: the caller's buffer is never written nor freed */
     int img_w, img_h;           /* the image handed to lqr_carver_new */
     int transposed;
     int active;
@@ -84,7 +87,7 @@ struct _LqrCarver {
     size_t ro_image_len;
     guchar *in_buffer;          /* the caller's pixel buffer (ownership passed at lqr_carver_new), kept as liblqr keeps it */
     size_t in_buffer_len;
-    int ro_valid, ro_line;
+    int ro_valid, ro_line, ro_x;    /* ro_x: the next pixel of line ro_line for lqr_carver_scan_ext */
     guchar *ro_buffer;          /* one line, the pointer scan_line hands out */
     int ro_buffer_len;
 
@@ -92,6 +95,10 @@ struct _LqrCarver {
     float *dbg_en, *dbg_m;
     int *dbg_least, dbg_w, dbg_h;
 };
+
+/* bytes per channel of each LqrColDepth */
+static const int k_depth_bytes[4] = {1, 2, 4, 8};
+#define PX_BYTES(r) ((size_t) (r)->channels * k_depth_bytes[(r)->col_depth])
 
 #define MAX_SUB 8
 typedef struct {
@@ -170,13 +177,13 @@ gint lqr_vmap_get_orientation(LqrVMap *v) { return v->orientation; }
 void lqr_vmap_destroy(LqrVMap *v) { if (v) { free(v->buffer); free(v); } }
 
 /* ======================= lifecycle ======================================= */
-LqrCarver *lqr_carver_new(guchar *buffer, gint width, gint height, gint channels)
+/* the carver of lqr_carver_new / lqr_carver_new_ext, arguments checked: pixels of `depth` (LqrColDepth) uploaded as the base
+ * layout, liblqr's defaults */
+static LqrCarver *carver_new(void *buffer, int width, int height, int channels, int depth)
 {
-    LqrCarver *r;
-    if (!buffer || width < 1 || height < 1 || channels < 1 || channels > 4) return NULL;
-    r = (LqrCarver *) calloc(1, sizeof *r);
+    LqrCarver *r = (LqrCarver *) calloc(1, sizeof *r);
     if (!r) return NULL;
-    r->dev = lqrhip_carver_create(buffer, width, height, channels);
+    r->dev = lqrhip_carver_create_ext(buffer, width, height, channels, depth);
     if (!r->dev) {
         fprintf(stderr, "liblqr-hip: lqr_carver_new failed: %s\n", lqrhip_last_error());
         free(r);
@@ -185,8 +192,9 @@ LqrCarver *lqr_carver_new(guchar *buffer, gint width, gint height, gint channels
     /* ownership passed to the carver (render.c:220-223).  The pixels now live in HBM; the block is kept, as liblqr keeps it,
      * and becomes the read-out buffer: handing 33 MB back to the C library and asking for 31 MB again costs an munmap, an
      * mmap and a page fault per 4 KiB -- more than the transfer itself (measured: 64 x 4K uploads 207 ms with the free, 62 without) */
-    r->in_buffer = buffer;
-    r->in_buffer_len = (size_t) width * height * channels;
+    r->col_depth = depth;
+    r->in_buffer = (guchar *) buffer;
+    r->in_buffer_len = (size_t) width * height * channels * k_depth_bytes[depth];
     r->level = r->max_level = 1;
     r->delta_x = 1;
     r->w = r->w0 = r->w_start = width;
@@ -200,6 +208,35 @@ LqrCarver *lqr_carver_new(guchar *buffer, gint width, gint height, gint channels
     r->progress = lqr_progress_new();
     if (!r->progress) { lqrhip_carver_destroy(r->dev); free(r); return NULL; }
     return r;
+}
+
+LqrCarver *lqr_carver_new(guchar *buffer, gint width, gint height, gint channels)
+{
+    if (!buffer || width < 1 || height < 1 || channels < 1 || channels > 4) return NULL;
+    return carver_new(buffer, width, height, channels, LQR_COLDEPTH_8I);
+}
+
+/* liblqr's entry point for pixels of any depth (lqr_coldepth.h): 8I is lqr_carver_new; a carver of another depth has a base
+ * layout of channels x {2, 4, 8} bytes per pixel */
+LqrCarver *lqr_carver_new_ext(void *buffer, gint width, gint height, gint channels, LqrColDepth colour_depth)
+{
+    const int depth = (int) colour_depth;
+    if (channels > 4 || depth < LQR_COLDEPTH_8I || depth > LQR_COLDEPTH_64F) {
+        fprintf(stderr, "liblqr-hip: lqr_carver_new_ext: %d channels at colour depth %d are not supported (1 .. 4 channels, depths 8I 16I 32F 64F)\n",
+                channels, depth);
+        return NULL;
+    }
+    if (!buffer || width < 1 || height < 1 || channels < 1) return NULL;
+    return carver_new(buffer, width, height, channels, depth);
+}
+
+void lqr_carver_set_preserve_input_image(LqrCarver *r) { r->preserve_input = 1; }
+LqrColDepth lqr_carver_get_col_depth(LqrCarver *r) { return (LqrColDepth) r->col_depth; }
+gint lqr_carver_get_bpp(LqrCarver *r) { return r->channels; }          /* liblqr: the deprecated name of get_channels */
+LqrImageType lqr_carver_get_image_type(LqrCarver *r)
+{
+    static const LqrImageType by_channels[5] = {LQR_RGB_IMAGE, LQR_GREY_IMAGE, LQR_GREYA_IMAGE, LQR_RGB_IMAGE, LQR_RGBA_IMAGE};
+    return by_channels[r->channels];
 }
 
 LqrRetVal lqr_carver_init(LqrCarver *r, gint delta_x, gfloat rigidity)
@@ -222,7 +259,8 @@ static void carver_free_host(LqrCarver *r)
     LqrVMapList *v, *vn;
     for (v = r->flushed_vs; v; v = vn) { vn = v->next; lqr_vmap_destroy(v->current); free(v); }
     free(r->progress);
-    free(r->ro_image); free(r->ro_buffer); free(r->in_buffer);
+    free(r->ro_image); free(r->ro_buffer);
+    if (!r->preserve_input) free(r->in_buffer);
     free(r->dbg_en); free(r->dbg_m); free(r->dbg_least);
     free(r);
 }
@@ -259,6 +297,11 @@ LqrRetVal lqr_carver_attach(LqrCarver *r, LqrCarver *aux)
 LqrRetVal lqr_carver_set_energy_function_builtin(LqrCarver *r, LqrEnergyFuncBuiltinType ef)
 {
     if ((int) ef < LQR_EF_GRAD_NORM || (int) ef > LQR_EF_NULL) return LQR_ERROR;
+    if (r->col_depth != LQR_COLDEPTH_8I) {
+        /* a deep carver's working planes hold the value the energy reads (brightness or luma): a change of kind rebuilds them */
+        const int luma = (int) ef >= LQR_EF_LUMA_GRAD_NORM && (int) ef <= LQR_EF_LUMA_GRAD_XABS;
+        if (lqrhip_carver_set_read_luma(r->dev, luma)) r->wk_valid = 0;
+    }
     r->nrg_func = (int) ef;
     r->nrg_radius = (ef == LQR_EF_NULL) ? 0 : 1;
     return LQR_OK;
@@ -292,7 +335,7 @@ static void set_width_one(LqrCarver *r, int w1)
     r->w = w1;
     r->level = r->w0 - w1 + 1;
     r->ro_valid = 0;
-    r->ro_line = 0;
+    r->ro_line = 0; r->ro_x = 0;
 }
 static void set_width_tree(LqrCarver *r, int w1)
 {
@@ -407,7 +450,7 @@ static LqrRetVal group_flatten(Group *g)
         r->w0 = r->w; r->h0 = r->h;
         r->w_start = r->w; r->h_start = r->h;
         r->level = 1; r->max_level = 1;
-        r->wk_valid = 0; r->ro_valid = 0; r->ro_line = 0;
+        r->wk_valid = 0; r->ro_valid = 0; r->ro_line = 0; r->ro_x = 0;
     });
     return LQR_OK;
 }
@@ -428,7 +471,7 @@ static LqrRetVal group_transpose(Group *g)
             for (x = -r->delta_x; x <= r->delta_x; x++)
                 r->rigidity_map[x + r->delta_x] = r->rigidity_map[x + r->delta_x] * r->w0 / r->h0;
         r->transposed = r->transposed ? 0 : 1;
-        r->wk_valid = 0; r->ro_valid = 0; r->ro_line = 0;
+        r->wk_valid = 0; r->ro_valid = 0; r->ro_line = 0; r->ro_x = 0;
     });
     return LQR_OK;
 }
@@ -589,7 +632,7 @@ static LqrRetVal group_build_maps(Group *g, int depth)
         for (i = 0; i < g->n; i++) {
             LqrCarver *c = g->r[i];
             c->w = snap[3 * i]; c->level = snap[3 * i + 1]; c->leftright = snap[3 * i + 2];
-            c->wk_valid = 0; c->ro_valid = 0; c->ro_line = 0;
+            c->wk_valid = 0; c->ro_valid = 0; c->ro_line = 0; c->ro_x = 0;
         }
         if (!fault || !lqrhip_get_recovery() || k == 1) break;
         fprintf(stderr, "liblqr-hip: the session is carved again on the kernels without spin waits\n");
@@ -703,10 +746,10 @@ static int same_config(const LqrCarver *a, const LqrCarver *b)
         a->transposed != b->transposed || a->active != b->active || a->delta_x != b->delta_x || a->rigidity != b->rigidity ||
         a->has_bias != b->has_bias || a->has_rigmask != b->has_rigmask || a->nrg_func != b->nrg_func ||
         a->leftright != b->leftright || a->lr_switch_frequency != b->lr_switch_frequency || a->enl_step != b->enl_step ||
-        a->resize_order != b->resize_order || a->wk_valid != b->wk_valid)
+        a->resize_order != b->resize_order || a->wk_valid != b->wk_valid || a->col_depth != b->col_depth)
         return 0;
     for (; la && lb; la = la->next, lb = lb->next)
-        if (la->current->channels != lb->current->channels) return 0;
+        if (la->current->channels != lb->current->channels || la->current->col_depth != lb->current->col_depth) return 0;
     return !la && !lb;
 }
 
@@ -729,7 +772,7 @@ static LqrRetVal group_resize(LqrCarver **rs, int n, int w1, int h1)
         for (k = 0; k < g.nb; k++) { LqrRetVal rk = hip_ret(lqrhip_batch_sync(g.b[k])); if (ret == LQR_OK) ret = rk; }
     }
     if (ret != LQR_OK) { int k; for (k = 0; k < g.nb; k++) lqrhip_batch_abort(g.b[k]); }      /* nothing of this resize may surface in the next one */
-    FOR_TREE(&g, i, r, { r->ro_valid = 0; r->ro_line = 0; });
+    FOR_TREE(&g, i, r, { r->ro_valid = 0; r->ro_line = 0; r->ro_x = 0; });
     group_close(&g);
     return ret;
 }
@@ -770,9 +813,9 @@ LqrRetVal lqrx_carver_resize_batch(LqrCarver **carvers, gint n, gint w1, gint h1
 /* ======================= readout (E12) =================================== */
 static LqrRetVal fetch_visible(LqrCarver *r)
 {
-    size_t n = (size_t) r->w * r->h * r->channels;
+    size_t n = (size_t) r->w * r->h * PX_BYTES(r);
     if (r->ro_valid) return LQR_OK;
-    if (!r->ro_image && r->in_buffer && r->in_buffer_len >= n) {     /* the block the image arrived in */
+    if (!r->ro_image && r->in_buffer && !r->preserve_input && r->in_buffer_len >= n) {     /* the block the image arrived in */
         r->ro_image = r->in_buffer; r->ro_image_len = r->in_buffer_len;
         r->in_buffer = NULL;
     }
@@ -783,17 +826,17 @@ static LqrRetVal fetch_visible(LqrCarver *r)
         r->ro_image_len = n;
     }
     HIP_CATCH(lqrhip_read_visible(r->dev, r->w0, r->h0, r->w, r->level, r->ro_image));
-    if (r->ro_buffer_len < r->w * r->channels) {
+    if ((size_t) r->ro_buffer_len < r->w * PX_BYTES(r)) {
         free(r->ro_buffer);
-        r->ro_buffer = (guchar *) malloc((size_t) r->w * r->channels);
+        r->ro_buffer = (guchar *) malloc(r->w * PX_BYTES(r));
         if (!r->ro_buffer) return LQR_NOMEM;
-        r->ro_buffer_len = r->w * r->channels;
+        r->ro_buffer_len = (int) (r->w * PX_BYTES(r));
     }
     r->ro_valid = 1;
     return LQR_OK;
 }
 
-void lqr_carver_scan_reset(LqrCarver *r) { r->ro_line = 0; }
+void lqr_carver_scan_reset(LqrCarver *r) { r->ro_line = 0; r->ro_x = 0; }
 gboolean lqr_carver_scan_by_row(LqrCarver *r) { return r->transposed ? FALSE : TRUE; }
 
 /* One packed device->host transfer feeds the whole scan (io_functions.c:155-164
@@ -801,18 +844,49 @@ gboolean lqr_carver_scan_by_row(LqrCarver *r) { return r->transposed ? FALSE : T
  * when the carver is transposed. */
 gboolean lqr_carver_scan_line(LqrCarver *r, gint *n, guchar **rgb)
 {
-    if (r->ro_line >= r->h) { r->ro_line = 0; return FALSE; }
+    if (r->col_depth != LQR_COLDEPTH_8I) return FALSE;        /* liblqr: the 8-bit form only */
+    return lqr_carver_scan_line_ext(r, n, (void **) rgb);
+}
+
+/* liblqr's cursor: a line scan starts over at the beginning of the line a pixel scan is in */
+gboolean lqr_carver_scan_line_ext(LqrCarver *r, gint *n, void **rgb)
+{
+    const size_t line = r->w * PX_BYTES(r);
+    if (r->ro_line >= r->h) { r->ro_line = 0; r->ro_x = 0; return FALSE; }
     if (fetch_visible(r) != LQR_OK) return FALSE;
-    memcpy(r->ro_buffer, r->ro_image + (size_t) r->ro_line * r->w * r->channels, (size_t) r->w * r->channels);
+    memcpy(r->ro_buffer, r->ro_image + (size_t) r->ro_line * line, line);
     *n = r->ro_line;
     *rgb = r->ro_buffer;
     r->ro_line++;
+    r->ro_x = 0;
     return TRUE;
+}
+
+/* one pixel at a time, carver-frame rows in order; (x, y) in image coordinates */
+gboolean lqr_carver_scan_ext(LqrCarver *r, gint *x, gint *y, void **rgb)
+{
+    const size_t px = PX_BYTES(r);
+    if (r->ro_x >= r->w) r->ro_x = 0;          /* (never left outside the frame: every reset of ro_line resets it too) */
+    if (r->ro_line >= r->h) { r->ro_line = 0; r->ro_x = 0; return FALSE; }
+    if (fetch_visible(r) != LQR_OK) return FALSE;
+    *x = r->transposed ? r->ro_line : r->ro_x;
+    *y = r->transposed ? r->ro_x : r->ro_line;
+    memcpy(r->ro_buffer, r->ro_image + ((size_t) r->ro_line * r->w + r->ro_x) * px, px);
+    *rgb = r->ro_buffer;
+    if (++r->ro_x == r->w) { r->ro_x = 0; r->ro_line++; }
+    return TRUE;
+}
+
+gboolean lqr_carver_scan(LqrCarver *r, gint *x, gint *y, guchar **rgb)
+{
+    if (r->col_depth != LQR_COLDEPTH_8I) return FALSE;
+    return lqr_carver_scan_ext(r, x, y, (void **) rgb);
 }
 
 LqrRetVal lqrx_carver_read_image(LqrCarver *r, guchar *out)
 {
-    int x, y, ch = r->channels;
+    int x, y;
+    const size_t ch = PX_BYTES(r);     /* bytes per pixel */
     if (!r->transposed && !r->ro_valid) {      /* straight into the caller's buffer: no second host copy */
         HIP_CATCH(lqrhip_read_visible(r->dev, r->w0, r->h0, r->w, r->level, out));
         return LQR_OK;
@@ -861,7 +935,7 @@ LqrRetVal lqrx_carver_reload_device_batch(LqrCarver **rs, gint n, void *const *d
         r->leftright = 0;
         r->has_bias = r->has_rigmask = 0;
         r->wk_valid = 0;
-        r->ro_valid = 0; r->ro_line = 0;
+        r->ro_valid = 0; r->ro_line = 0; r->ro_x = 0;
         if (r->active)      /* as lqr_carver_init */
             for (x = -r->delta_x; x <= r->delta_x; x++)
                 r->rigidity_map[x + r->delta_x] = r->rigidity * powf(fabsf((float) x), 1.5f) / r->h;

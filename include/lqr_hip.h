@@ -60,6 +60,12 @@ const char *lqrhip_last_error(void);
 /* E1 lqr_carver_new (render.c:222,894): upload the interleaved u8 image as the
  * base layout.  The host buffer is not retained. */
 LqrHipCarver *lqrhip_carver_create(const unsigned char *rgb, int w, int h, int channels);
+/* lqr_carver_new_ext (lqr_coldepth.h): the same for pixels of `depth` (LqrColDepth 0 .. 3: channels x 1 / 2 / 4 / 8 bytes).
+ * Every call below that moves base-layout pixels (read-out, reset) moves w x h x channels x that many bytes. */
+LqrHipCarver *lqrhip_carver_create_ext(const void *rgb, int w, int h, int channels, int depth);
+/* a carver of depth 16I / 32F / 64F keeps the value its energy reads (brightness, or luma with `luma`) in its working
+ * planes: returns 1 if that kind changed, i.e. the working planes must be laid out again (lqrhip_wk_init) */
+int lqrhip_carver_set_read_luma(LqrHipCarver *c, int luma);
 void lqrhip_carver_destroy(LqrHipCarver *c);
 /* Start over on an existing carver, as lqr_carver_destroy + lqr_carver_new + lqr_carver_init would
  * (render.c:376,222,224), but from an image that is already in HBM: the base layout becomes the

@@ -5,7 +5,11 @@ Evaluation mode of the x87 code: "sse" (control word 0x27f, the float-only DP fu
 x86-64 / SSE2 build of the same source performs it -- the platform this repository's "bit-exact" refers to.  For every
 vector the manifest also records whether the build AS SHIPPED (control word 0x37f) produces the same result.
 
-    python scripts/ref_engine/make_ref_golden.py [group ...]     groups: fixtures fuzz extras interactive planes configs config4 config5half deltawide
+    python scripts/ref_engine/make_ref_golden.py [group ...]     groups: fixtures fuzz extras interactive planes configs config4 config5half deltawide coldepth
+
+coldepth (lqr_carver_new_ext: 16I / 32F / 64F carvers, tests/coldepth_cases.py) writes to tests/golden/coldepth/ with a manifest of
+its own.  64F: lqr_carver_inflate averages doubles there (fld / fadd / fmul 0.5 / fstp), so under "sse" it runs under the 53-bit
+control word, not the 24-bit one of the float-only functions -- double arithmetic as an SSE2 build performs it.
 """
 import hashlib, json, os, sys, time
 from concurrent.futures import ProcessPoolExecutor
@@ -122,6 +126,60 @@ def make_input(spec):
     raise ValueError(k)
 
 
+COLDEPTH_OUT = os.path.join(ROOT, "tests", "golden", "coldepth")
+
+
+def coldepth_api(mode, spec):
+    if mode != "sse":
+        return R.RefApi(0x37f)
+    deep64 = spec["depth"] == 3 or spec.get("aux_depth") == 3
+    only = tuple(f for f in R.FLOAT_ONLY if not (deep64 and f == "lqr_carver_inflate"))
+    return R.RefApi(0x27f, float24_only=only)
+
+
+def coldepth_one(task):
+    import coldepth_cases as CD
+    name, spec = task
+    img, extra = CD.make_input(spec)
+    res = {}
+    for mode in ("sse", "shipped"):
+        a = coldepth_api(mode, spec)
+        try:
+            t0 = time.time()
+            out = CD.run(a, R.RefCarver, spec, img, extra)
+            res[mode] = (out, a.r.heap_check(), time.time() - t0)
+        finally:
+            a.close()
+    out, heap, secs = res["sse"]
+    same = all(np.array_equal(np.asarray(out[k]).view(np.uint8) if np.asarray(out[k]).dtype.kind == "f" else out[k], np.asarray(res["shipped"][0][k]).view(np.uint8) if np.asarray(out[k]).dtype.kind == "f" else res["shipped"][0][k])
+               for k in out) and out.keys() == res["shipped"][0].keys()
+    arrays = dict(out, img=img, spec=np.array(json.dumps(spec, sort_keys=True)))
+    for k, v in extra.items():
+        arrays["in_" + k] = v
+    fn = "coldepth_%s.npz" % name
+    np.savez_compressed(os.path.join(COLDEPTH_OUT, fn), **arrays)
+    rec = json.loads(str(out["record"]))
+    return dict(group="coldepth", name=name, spec=spec, heap=[heap["bad"], heap["freed_bad"]], same_as_shipped=bool(same),
+                input_unchanged=rec.get("input_unchanged"), rets=rec["rets"], seconds=round(secs, 2), file=fn)
+
+
+def coldepth_group(jobs=8):
+    import coldepth_cases as CD
+    os.makedirs(COLDEPTH_OUT, exist_ok=True)
+    with ProcessPoolExecutor(jobs) as ex:
+        entries = list(ex.map(coldepth_one, CD.cases()))
+    for e in entries:
+        with open(os.path.join(COLDEPTH_OUT, e["file"]), "rb") as f:
+            e["sha256"] = hashlib.sha256(f.read()).hexdigest()
+    man = dict(source="gimp-lqr-plugin.exe (liblqr 0.4.1 statically linked), executed by scripts/ref_engine/refrun.c",
+               exe_sha256=hashlib.sha256(R.exe_bytes()).hexdigest(),
+               mode="sse: x87 control word 0x27f, float-only DP functions under 0x07f (64F cases: lqr_carver_inflate under 0x27f)",
+               vectors=entries)
+    with open(os.path.join(COLDEPTH_OUT, "MANIFEST.json"), "w") as f:
+        json.dump(man, f, indent=1)
+    return entries
+
+
 def interactive(seed):
     img, kw, mk, steps, what = C.interactive_case(np.random.default_rng(seed))
     h, w = img.shape[:2]
@@ -189,6 +247,11 @@ def planes():
 
 def main():
     groups = set(sys.argv[1:]) or {"fixtures", "fuzz", "extras", "interactive", "planes", "configs", "config4"}
+    if groups == {"coldepth"}:          # its own directory and manifest: tests/golden/ref/ is not touched
+        entries = coldepth_group()
+        print("coldepth: %d vectors, heap clean %d, same as shipped %d" % (len(entries), sum(e["heap"] == [0, 0] for e in entries),
+                                                                         sum(e["same_as_shipped"] for e in entries)))
+        return
     os.makedirs(OUT, exist_ok=True)
     mpath = os.path.join(OUT, "MANIFEST.json")
     manifest = json.load(open(mpath)) if os.path.exists(mpath) else dict(vectors=[])

@@ -324,6 +324,121 @@ class RefCarver:
             ret = r.call("lqr_carver_init", self.p, delta_x, ("f", float(rigidity)))
             assert ret == LQR_OK, ret
 
+    # -- the colour-depth surface (include/lqr_coldepth.h), as binding.Carver's ---------------------------
+    DTYPES = {0: np.uint8, 1: np.uint16, 2: np.float32, 3: np.float64}
+
+    @classmethod
+    def from_ext(cls, api, array, depth=None, init=True, delta_x=1, rigidity=0.0, preserve=False):
+        array = np.asarray(array)
+        if depth is None:
+            depth = {np.dtype(v): k for k, v in cls.DTYPES.items()}[array.dtype]
+        array = np.ascontiguousarray(array, dtype=cls.DTYPES[depth])
+        if array.ndim == 2:
+            array = array[:, :, None]
+        self = cls.__new__(cls)
+        self.api, self.r = api, api.r
+        r = self.r
+        self.h0, self.w0, self.ch = array.shape
+        self.depth = depth
+        self.events, self.aux = [], []
+        self._recording = False
+        self.nbytes = array.nbytes
+        self.buf = r.alloc(max(array.nbytes, 1))
+        r.write(self.buf, array.tobytes())
+        self.p = r.call("lqr_carver_new_ext", self.buf, self.w0, self.h0, self.ch, depth)
+        if not self.p:
+            raise MemoryError("lqr_carver_new_ext returned NULL")
+        if preserve:
+            r.call("lqr_carver_set_preserve_input_image", self.p)
+        if init:
+            ret = r.call("lqr_carver_init", self.p, delta_x, ("f", float(rigidity)))
+            assert ret == LQR_OK, ret
+        return self
+
+    def input_bytes(self):
+        """the input buffer as it is now (meaningful while the carver or the caller still owns it)"""
+        return self.r.read(self.buf, self.nbytes)
+
+    def free_input(self):
+        self.r.free(self.buf)
+
+    def attach_ext(self, array, depth=None):
+        aux = RefCarver.from_ext(self.api, array, depth, init=False)
+        ret = self.r.call("lqr_carver_attach", self.p, aux.p)
+        assert ret == LQR_OK, ret
+        self.aux.append(aux)
+        return aux
+
+    def _px(self):
+        dt = np.dtype(self.DTYPES[getattr(self, "depth", 0)])
+        return dt, self.ch * dt.itemsize
+
+    def scan_partial(self):
+        r = self.r
+        W, H = r.call("lqr_carver_get_width", self.p), r.call("lqr_carver_get_height", self.p)
+        n = (W if r.call("lqr_carver_scan_by_row", self.p) else H) - 1
+        cell = r.alloc(12)
+        r.call("lqr_carver_scan_reset", self.p)
+        for _ in range(n):
+            assert r.call("lqr_carver_scan_ext", self.p, cell, cell + 4, cell + 8)
+        r.free(cell)
+        return n
+
+    def scan_ext(self, reset=True):
+        r = self.r
+        dt, nb = self._px()
+        W, H = r.call("lqr_carver_get_width", self.p), r.call("lqr_carver_get_height", self.p)
+        out = np.zeros((H, W, self.ch), dt)
+        cell = r.alloc(12)
+        order = []
+        if reset:
+            r.call("lqr_carver_scan_reset", self.p)
+        while r.call("lqr_carver_scan_ext", self.p, cell, cell + 4, cell + 8):
+            x, y, px = struct.unpack("<iiI", r.read(cell, 12))
+            out[y, x] = np.frombuffer(r.read(px, nb), dt)
+            order.append((x, y))
+        r.free(cell)
+        return out, order
+
+    def scan_line_ext(self):
+        r = self.r
+        dt, nb = self._px()
+        W, H = r.call("lqr_carver_get_width", self.p), r.call("lqr_carver_get_height", self.p)
+        out = np.zeros((H, W, self.ch), dt)
+        cell = r.alloc(8)
+        lines = []
+        r.call("lqr_carver_scan_reset", self.p)
+        while r.call("lqr_carver_scan_line_ext", self.p, cell, cell + 4):
+            n, px = struct.unpack("<iI", r.read(cell, 8))
+            by_row = r.call("lqr_carver_scan_by_row", self.p)
+            length = W if by_row else H
+            buf = np.frombuffer(r.read(px, length * nb), dt).reshape(length, self.ch)
+            if by_row:
+                out[n] = buf
+            else:
+                out[:, n] = buf
+            lines.append(n)
+        r.free(cell)
+        return out, lines
+
+    def scan_rets(self):
+        """what the 8-bit scans return on this carver (first call after a reset)"""
+        r = self.r
+        cell = r.alloc(12)
+        r.call("lqr_carver_scan_reset", self.p)
+        a = r.call("lqr_carver_scan", self.p, cell, cell + 4, cell + 8)
+        r.call("lqr_carver_scan_reset", self.p)
+        b = r.call("lqr_carver_scan_line", self.p, cell, cell + 4)
+        r.call("lqr_carver_scan_reset", self.p)
+        r.free(cell)
+        return [a, b]
+
+    def getters_ext(self):
+        g = self.getters()
+        g.update(col_depth=self.r.calls("lqr_carver_get_col_depth", self.p), image_type=self.r.calls("lqr_carver_get_image_type", self.p),
+                 bpp=self.r.calls("lqr_carver_get_bpp", self.p))
+        return g
+
     def _mask(self, mask):
         mask = np.ascontiguousarray(mask, dtype=np.uint8)
         if mask.ndim == 2:
