@@ -362,6 +362,10 @@ class Carver:
             a.lqr_carver_set_dump_vmaps(self.p)
         return self
 
+    def set_energy(self, nrg_func):
+        """change the built-in energy function of a carver that may already have been resized"""
+        return self.api.lqr_carver_set_energy_function_builtin(self.p, nrg_func)
+
     def set_progress_recorder(self):
         a = self.api
         prog = a.lqr_progress_new()

@@ -5,7 +5,10 @@ Evaluation mode of the x87 code: "sse" (control word 0x27f, the float-only DP fu
 x86-64 / SSE2 build of the same source performs it -- the platform this repository's "bit-exact" refers to.  For every
 vector the manifest also records whether the build AS SHIPPED (control word 0x37f) produces the same result.
 
-    python scripts/ref_engine/make_ref_golden.py [group ...]     groups: fixtures fuzz extras interactive planes configs config4 config5half deltawide coldepth
+    python scripts/ref_engine/make_ref_golden.py [group ...]     groups: fixtures fuzz extras interactive planes configs config4 config5half deltawide coldepth coldepth_mid
+
+coldepth_mid (tests/coldepth_cases.py mid_cases() and plane_cases(): the same at sizes past the deep kernels' chunk, block and lag
+boundaries, plus planes read out of the engine's memory by stepper.py) writes to tests/golden/coldepth_mid/, or to $COLDEPTH_MID_OUT.
 
 coldepth (lqr_carver_new_ext: 16I / 32F / 64F carvers, tests/coldepth_cases.py) writes to tests/golden/coldepth/ with a manifest of
 its own.  64F: lqr_carver_inflate averages doubles there (fld / fadd / fmul 0.5 / fstp), so under "sse" it runs under the 53-bit
@@ -137,9 +140,10 @@ def coldepth_api(mode, spec):
     return R.RefApi(0x27f, float24_only=only)
 
 
-def coldepth_one(task):
+def coldepth_one(task, out_dir=None, group="coldepth"):
     import coldepth_cases as CD
     name, spec = task
+    out_dir = out_dir or COLDEPTH_OUT
     img, extra = CD.make_input(spec)
     res = {}
     for mode in ("sse", "shipped"):
@@ -156,10 +160,10 @@ def coldepth_one(task):
     arrays = dict(out, img=img, spec=np.array(json.dumps(spec, sort_keys=True)))
     for k, v in extra.items():
         arrays["in_" + k] = v
-    fn = "coldepth_%s.npz" % name
-    np.savez_compressed(os.path.join(COLDEPTH_OUT, fn), **arrays)
+    fn = "%s_%s.npz" % (group, name)
+    np.savez_compressed(os.path.join(out_dir, fn), **arrays)
     rec = json.loads(str(out["record"]))
-    return dict(group="coldepth", name=name, spec=spec, heap=[heap["bad"], heap["freed_bad"]], same_as_shipped=bool(same),
+    return dict(group=group, name=name, spec=spec, heap=[heap["bad"], heap["freed_bad"]], same_as_shipped=bool(same),
                 input_unchanged=rec.get("input_unchanged"), rets=rec["rets"], seconds=round(secs, 2), file=fn)
 
 
@@ -178,6 +182,62 @@ def coldepth_group(jobs=8):
     with open(os.path.join(COLDEPTH_OUT, "MANIFEST.json"), "w") as f:
         json.dump(man, f, indent=1)
     return entries
+
+
+COLDEPTH_MID_OUT = os.environ.get("COLDEPTH_MID_OUT") or os.path.join(ROOT, "tests", "golden", "coldepth_mid")
+
+
+def coldepth_mid_one(task):
+    return coldepth_one(task, COLDEPTH_MID_OUT, "coldepth_mid")
+
+
+def coldepth_mid_planes(task):
+    """the genuine engine stepped one seam at a time (stepper.py) on a deep carver: en after the full build, en / m / back pointers
+    after each count of coldepth_cases.PLANE_SEAMS incremental seams"""
+    import coldepth_cases as CD
+    name, spec = task
+    img, _ = CD.make_input(dict(spec, steps=[]))
+    a = coldepth_api("sse", spec)
+    try:
+        t0 = time.time()
+        c = R.RefCarver.from_ext(a, img, spec["depth"], delta_x=spec.get("delta", 1), rigidity=spec.get("rigidity", 0.0))
+        c.configure(nrg_func=spec["nrg"], switch_freq=0)
+        st = S.Stepper(c)
+        st.begin(max(CD.PLANE_SEAMS) + 1)
+        arrays = dict(build_en=st.planes()[0], spec=np.array(json.dumps(spec, sort_keys=True)), input_sha1=np.array(sha(img)))
+        stale = {}
+        for k in range(1, max(CD.PLANE_SEAMS) + 1):
+            st.seam()
+            if k in CD.PLANE_SEAMS:
+                en, m, dx = st.planes()
+                arrays["en%d" % k], arrays["m%d" % k], arrays["dx%d" % k] = en, m, dx.astype(np.int16)
+                stale[str(k)] = int((dx == -999).sum())
+        c.destroy()
+        heap = a.r.heap_check()
+    finally:
+        a.close()
+    fn = "coldepth_mid_%s.npz" % name
+    np.savez_compressed(os.path.join(COLDEPTH_MID_OUT, fn), **arrays)
+    return dict(group="coldepth_mid_planes", name=name, spec=spec, heap=[heap["bad"], heap["freed_bad"]], stale=stale,
+                seconds=round(time.time() - t0, 2), file=fn)
+
+
+def coldepth_mid_group(jobs=8):
+    import coldepth_cases as CD
+    os.makedirs(COLDEPTH_MID_OUT, exist_ok=True)
+    with ProcessPoolExecutor(jobs) as ex:
+        entries = list(ex.map(coldepth_mid_one, CD.mid_cases()))
+        planes = list(ex.map(coldepth_mid_planes, CD.plane_cases()))
+    for e in entries + planes:
+        with open(os.path.join(COLDEPTH_MID_OUT, e["file"]), "rb") as f:
+            e["sha256"] = hashlib.sha256(f.read()).hexdigest()
+    man = dict(source="gimp-lqr-plugin.exe (liblqr 0.4.1 statically linked), executed by scripts/ref_engine/refrun.c",
+               exe_sha256=hashlib.sha256(R.exe_bytes()).hexdigest(),
+               mode="sse: x87 control word 0x27f, float-only DP functions under 0x07f (64F cases: lqr_carver_inflate under 0x27f)",
+               vectors=entries, planes=planes)
+    with open(os.path.join(COLDEPTH_MID_OUT, "MANIFEST.json"), "w") as f:
+        json.dump(man, f, indent=1)
+    return entries, planes
 
 
 def interactive(seed):
@@ -251,6 +311,12 @@ def main():
         entries = coldepth_group()
         print("coldepth: %d vectors, heap clean %d, same as shipped %d" % (len(entries), sum(e["heap"] == [0, 0] for e in entries),
                                                                          sum(e["same_as_shipped"] for e in entries)))
+        return
+    if groups == {"coldepth_mid"}:
+        entries, planes = coldepth_mid_group()
+        print("coldepth_mid: %d vectors + %d plane sets, heap clean %d, all returns LQR_OK %d, same as shipped %d" % (
+            len(entries), len(planes), sum(e["heap"] == [0, 0] for e in entries + planes),
+            sum(all(r == 1 for r in e["rets"]) for e in entries), sum(e["same_as_shipped"] for e in entries)))
         return
     os.makedirs(OUT, exist_ok=True)
     mpath = os.path.join(OUT, "MANIFEST.json")

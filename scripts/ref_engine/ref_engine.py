@@ -471,6 +471,9 @@ class RefCarver:
             r.call("lqr_carver_set_dump_vmaps", self.p)
         return self
 
+    def set_energy(self, nrg_func):
+        return self.r.call("lqr_carver_set_energy_function_builtin", self.p, nrg_func)
+
     def _cstr(self, s):
         p = self.r.alloc(len(s) + 1)
         self.r.write(p, s + b"\0")

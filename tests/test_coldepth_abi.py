@@ -131,3 +131,91 @@ def test_a_wrong_depth_or_channel_count_is_refused_before_any_device_work():
     assert not lib.lqr_carver_new_ext(buf, 4, 4, 5, 2)
     assert not lib.lqr_carver_new_ext(buf, 4, 4, 3, 4)
     assert not lib.lqr_carver_new_ext(buf, 4, 4, 3, -1)
+
+
+# ---- the mid-size vectors (tests/golden/coldepth_mid/) and the boundaries they cross ------------------------------------------
+MID = os.path.join(ROOT, "tests", "golden", "coldepth_mid")
+CSRC = os.path.join(ROOT, "gimp-lqr-plugin_amd", "csrc")
+
+
+def test_mid_manifest_lists_every_vector_with_its_checksum_and_size_limits():
+    import coldepth_cases as CD
+    man = json.load(open(os.path.join(MID, "MANIFEST.json")))
+    listed = man["vectors"] + man["planes"]
+    files = {v["file"] for v in listed}
+    assert files == {f for f in os.listdir(MID) if f.endswith(".npz")}
+    assert len(files) == len(listed)
+    assert [v["name"] for v in man["vectors"]] == [n for n, _ in CD.mid_cases()]
+    assert [v["name"] for v in man["planes"]] == [n for n, _ in CD.plane_cases()]
+    for v, (_, spec) in zip(listed, CD.mid_cases() + CD.plane_cases()):
+        assert v["spec"] == json.loads(json.dumps(spec)), v["name"]
+        data = open(os.path.join(MID, v["file"]), "rb").read()
+        assert hashlib.sha256(data).hexdigest() == v["sha256"], v["file"]
+        assert len(data) < 1 << 20, v["file"]
+        assert v["heap"] == [0, 0], v["name"]
+        if "rets" in v:
+            assert v["rets"] == [1] * len(v["spec"]["steps"]), v["name"]
+        if v["spec"].get("preserve"):
+            assert v["input_unchanged"] is True, v["name"]
+    assert sum(os.path.getsize(os.path.join(MID, f)) for f in os.listdir(MID)) < 10 << 20
+
+
+def kernel_constants():
+    """EU_ROWS, EU_LOGB, FROZEN_LAG_MAX and the delta_x thresholds of k_emap_update_deep's instantiations, from the sources"""
+    common = open(os.path.join(CSRC, "lqr_common.h")).read()
+    shim = open(os.path.join(CSRC, "lqr_shim.hip")).read()
+    K = {}
+    for name, src in (("EU_ROWS", common), ("EU_LOGB", common), ("FROZEN_LAG_MAX", shim)):
+        (K[name],) = {int(v) for v in re.findall(r"^#define\s+%s\s+(\d+)" % name, src, re.M)}
+    m = re.search(r"#define LAUNCH_EUPD_DEEP\(N\) do \{ if \(p->delta_x <= (\d+)\) LAUNCH_EUPD_NT_DEEP\(N, (\d+)\); "
+                  r"else if \(p->delta_x <= (\d+)\) LAUNCH_EUPD_NT_DEEP\(N, (\d+)\); else LAUNCH_EUPD_NT_DEEP\(N, (\d+)\); \}", shim)
+    a, na, b, nb, nc = map(int, m.groups())
+    K["NT"] = [(a, na), (b, nb), (10 ** 9, nc)]
+    # the lag of a group: a quarter up to 4 carvers (both places the seam loop decides it)
+    assert len(re.findall(r"const int lag_max = n <= 4 \? FROZEN_LAG_MAX / 4 : FROZEN_LAG_MAX;", shim)) == 2
+    # the chunk of the rank loops of the deep one-off kernels
+    deep = open(os.path.join(CSRC, "k_deep.hip")).read()
+    assert len(re.findall(r"for \(int base = 0; base < \w+; base \+= 256\)", deep)) == 5
+    return K
+
+
+def test_kernel_constants_are_the_ones_the_cases_were_sized_for():
+    assert kernel_constants() == dict(EU_ROWS=62, EU_LOGB=8, FROZEN_LAG_MAX=128, NT=[(2, 12), (8, 36), (10 ** 9, 68)])
+
+
+def test_mid_vectors_cross_every_boundary_of_the_deep_kernels_and_the_small_ones_none():
+    import coldepth_cases as CD
+    K = kernel_constants()
+    lag1, lagn = K["FROZEN_LAG_MAX"] // 4, K["FROZEN_LAG_MAX"]
+    wide_nt = ["nt%d" % s for _, s in K["NT"][1:]]
+    sizes = {1: (6, 8), 2: (8, 12, 16), 3: (8, 16, 24, 32)}
+    fam = {n for depth in (1, 2, 3) for n in CD.family_names(depth)}
+    for depth in (1, 2, 3):
+        single, group = set(), set()
+        for name, spec in CD.mid_cases():
+            if spec["depth"] != depth:
+                continue
+            single |= CD.boundaries(spec, K)
+            if name in fam:
+                assert spec["w"] > 256 and len(CD.family_names(depth)) >= 5
+                group |= CD.boundaries(spec, K, group=5)
+        want = ["%s:c%d" % (p, n) for p in ("shrink", "enlarge", "flatten", "relayout", "readout", "catchup") for n in (2, 3)]
+        want += ["rows:b2", "rows:b3", "seams>%d" % lag1, "ragged"] + wide_nt
+        want += ["%s:b%d" % (p, b) for p in ("inflate", "compact") for b in sizes[depth]]
+        assert not [x for x in want if x not in single], (depth, [x for x in want if x not in single])
+        assert {"seams>%d" % lagn, "catchup:c2", "ragged"} <= group, (depth, group)
+    assert any("transpose:b%d" % b in CD.boundaries(s, K) for _, s in CD.mid_cases() for b in (12, 16))
+    # the statement the mid-size vectors rest on: the small ones stay inside one chunk, one block and the lag, and below delta_x 9
+    old = set()
+    for _, spec in CD.cases():
+        old |= CD.boundaries(spec, K)
+        assert spec.get("delta", 1) < 9
+    assert old and all(x.endswith(":c1") or x in ("rows:b1", "ragged", "nt12", "nt36") for x in old), old
+    # plane vectors: more than one chunk and block, both counts past the lag (so a catch-up precedes each), one not a multiple of EU_LOGB
+    for _, spec in CD.plane_cases():
+        assert spec["w"] - max(CD.PLANE_SEAMS) > 0 and spec["w"] > 256 and spec["h"] > K["EU_ROWS"]
+    assert min(CD.PLANE_SEAMS) > lag1 and max(CD.PLANE_SEAMS) > 2 * lag1 and any(k % K["EU_LOGB"] for k in CD.PLANE_SEAMS)
+    for depth in (1, 2, 3):
+        mine = [s for _, s in CD.plane_cases() if s["depth"] == depth]
+        assert any(s["nrg"] in (0, 1, 2) and s["ch"] >= 3 for s in mine) and any(s["nrg"] in (3, 4, 5) and s["ch"] >= 3 for s in mine)
+        assert any(s.get("delta", 1) >= 9 and s.get("rigidity") for s in mine)

@@ -41,20 +41,7 @@ def load(name):
     return spec, z["img"], extra, z
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint8) if a.dtype.kind == "f" else a
-
-
-def assert_same_record(got, z, what):
-    want_keys = sorted(k for k in z.files if k not in ("img", "spec") and not k.startswith("in_"))
-    assert sorted(got) == want_keys, what
-    for k in want_keys:
-        if k == "record":
-            assert json.loads(str(got[k])) == json.loads(str(z[k])), "%s: %s" % (what, k)
-        else:
-            assert got[k].dtype == z[k].dtype and got[k].shape == z[k].shape, "%s: %s" % (what, k)
-            assert np.array_equal(bits(got[k]), bits(z[k])), "%s: %s differs" % (what, k)
+bits, assert_same_record = CD.bits, CD.assert_same_record
 
 
 @pytest.mark.parametrize("name", sorted(VECTORS))
@@ -67,18 +54,7 @@ def test_genuine_vector_is_reproduced(eng, name):
 
 
 # ---- lift identities ------------------------------------------------------------------------------------------------------
-def lift_case(seed, nrg):
-    rng = np.random.default_rng(70000 + 100 * nrg + seed)
-    ch = 1 + seed % 4
-    w, h = int(rng.integers(20, 44)), int(rng.integers(16, 34))
-    img = CD.base_image(rng, w, h, ch)
-    enlarge = seed % 5 == 4
-    nw = w + int(rng.integers(1, w // 2)) if enlarge else w - int(rng.integers(1, w // 3))
-    # an enlargement is carved in one direction and one step only: a second pass would read the pixels the first one inserted,
-    # which each depth averages with its own rounding
-    nh = h if enlarge else h - int(rng.integers(0, h // 4))
-    kw = dict(nrg_func=nrg, res_order=int(seed % 2), switch_freq=int(rng.integers(0, 4)), enl_step=1.5)
-    return img, nw, nh, kw, enlarge
+lift_case = CD.lift_case
 
 
 def carve(c, nw, nh, kw):
@@ -201,22 +177,34 @@ def test_float_replay_c_reproduces_its_vector(tmp_path):
     assert np.array_equal(order, z["order0"])
 
 
-@pytest.mark.parametrize("first,second", [(0, 3), (4, 1), (2, 5)])
-def test_energy_function_changed_between_resizes(eng, first, second):
+SMALL, WIDE = (44, 30, 38, 31, 26), (300, 70, 262, 225, 64)
+
+
+@pytest.mark.parametrize("first,second,size", [pytest.param(0, 3, SMALL, id="0-3"), pytest.param(4, 1, SMALL, id="4-1"), pytest.param(2, 5, SMALL, id="2-5"),
+                                               pytest.param(0, 3, WIDE, id="0-3-wide"), pytest.param(4, 1, WIDE, id="4-1-wide"), pytest.param(2, 5, WIDE, id="2-5-wide")])
+def test_energy_function_changed_between_resizes(eng, first, second, size):
     """brightness and luma are different read values: a deep carver whose energy function changes kind between two resizes
-    lays its value plane out again (lift identity against the 8-bit oracle, which reads pixels afresh every time)"""
+    lays its value plane out again (lift identity against the 8-bit oracle, which reads pixels afresh every time).  wide: the
+    carver that is laid out again has a base layout of 338 columns and is not flat (k_wk_init_visible_deep over two chunks), and
+    the session that follows is longer than the frozen lag; 16I as well as 64F"""
     orc = L.oracle_api()
+    w, h, w1, w2, h2 = size
     rng = np.random.default_rng(first * 10 + second)
-    img = CD.base_image(rng, 44, 30, 4)
+    img = CD.base_image(rng, w, h, 4)
     o, e = L.Carver(orc, img), L.Carver.from_ext(eng, img.astype(np.float64) / 255.0)
-    for c in (o, e):
+    cs = [o, e] + ([L.Carver.from_ext(eng, img.astype(np.uint16) * 257)] if size is WIDE else [])
+    for c in cs:
         c.configure(nrg_func=first)
-        assert c.resize(38, 30) == L.LQR_OK
+        assert c.resize(w1, h) == L.LQR_OK
         assert c.api.lqr_carver_set_energy_function_builtin(c.p, second) == L.LQR_OK
-        assert c.resize(31, 26) == L.LQR_OK
+        assert c.resize(w2, h2) == L.LQR_OK
     assert np.array_equal(e.vmap_dump()["data"], o.vmap_dump()["data"])
     assert np.array_equal(bits(e.read_image_ext()), bits(o.read_image().astype(np.float64) / 255.0))
-    o.destroy(); e.destroy()
+    for c in cs[2:]:
+        assert np.array_equal(c.vmap_dump()["data"], o.vmap_dump()["data"])
+        assert np.array_equal(c.read_image_ext(), o.read_image().astype(np.uint16) * 257)
+    for c in cs:
+        c.destroy()
 
 
 @pytest.mark.parametrize("name", ["interactive_16i", "interactive_32f", "interactive_64f", "edge_16i", "d16i_c3_e5", "enl_vert_32f"])
