@@ -132,6 +132,31 @@ def bind_coldepth(api):
     return api
 
 
+# include/lqr_imagetype.h: liblqr 0.4's image types (CMY, CMYK, CMYKA, custom channels) and the channel limit, in a table of their own
+(LQR_RGB_IMAGE, LQR_RGBA_IMAGE, LQR_GREY_IMAGE, LQR_GREYA_IMAGE, LQR_CMY_IMAGE, LQR_CMYK_IMAGE, LQR_CMYKA_IMAGE,
+ LQR_CUSTOM_IMAGE) = range(8)
+IMGTYPE_SYMBOLS = {
+    "lqr_carver_set_image_type": (_I, [_P, _I]),
+    "lqr_carver_set_alpha_channel": (_I, [_P, _I]),
+    "lqr_carver_set_black_channel": (_I, [_P, _I]),
+    "lqrx_set_max_channels": (_I, [_I]),
+}
+
+
+def bind_imagetype(api):
+    """add IMGTYPE_SYMBOLS (and COLDEPTH_SYMBOLS) to a bound Api; a genuine liblqr-1 has no lqrx_set_max_channels and keeps none"""
+    bind_coldepth(api)
+    if not getattr(api, "has_imagetype", False):
+        for name, (res, args) in IMGTYPE_SYMBOLS.items():
+            if name.startswith("lqrx_") and not api.has_ext:
+                continue
+            fn = getattr(api.lib, api.prefix + name)      # AttributeError = missing export
+            fn.restype, fn.argtypes = res, args
+            setattr(api, name, fn)
+        api.has_imagetype = True
+    return api
+
+
 class Api:
     """Resolved function table of one library exporting the ABI."""
 
@@ -155,6 +180,11 @@ def engine_api():
             raise RuntimeError("HIP engine library missing: %s (run python -c 'import __graft_entry__ as g; g.build()')" % ENGINE_LIB)
         _apis["engine"] = Api(ENGINE_LIB, "")
     return _apis["engine"]
+
+
+def engine_imagetype_api():
+    """the engine with the colour-depth and image-type surfaces bound"""
+    return bind_imagetype(engine_api())
 
 
 def engine_coldepth_api():
@@ -248,6 +278,16 @@ class Carver:
         assert ret == LQR_OK, ret
         self.aux.append(aux)
         return aux
+
+    # -- the image type (include/lqr_imagetype.h); each returns the call's LqrRetVal
+    def set_image_type(self, image_type):
+        return bind_imagetype(self.api).lqr_carver_set_image_type(self.p, int(image_type))
+
+    def set_alpha_channel(self, index):
+        return bind_imagetype(self.api).lqr_carver_set_alpha_channel(self.p, int(index))
+
+    def set_black_channel(self, index):
+        return bind_imagetype(self.api).lqr_carver_set_black_channel(self.p, int(index))
 
     def _px(self):
         depth = getattr(self, "depth", LQR_COLDEPTH_8I)

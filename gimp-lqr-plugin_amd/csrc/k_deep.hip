@@ -1,16 +1,20 @@
-// k_deep.hip -- the kernels of carvers whose pixels are not 8-bit (lqr_carver_new_ext: 16I, 32F, 64F).
+// k_deep.hip -- the kernels of carvers that read through the value plane: pixels that are not 8-bit
+// (lqr_carver_new_ext: 16I, 32F, 64F), image types beyond grey / RGB with or without alpha (lqr_imagetype.h: CMY, CMYK, CMYKA,
+// CUSTOM), more than 4 channels.
 // (gfx950 / CDNA4, wave64; see lqr_common.h for the file map)
 //
-// The seam loop never sees pixels: the DP, the backtrack and the carve work on the float planes whatever the depth.  Depth
-// reaches only
-//   * the value the energy reads.  An 8-bit carver keeps its pixels packed in the u32 `pix` plane and turns them into brightness
-//     (or luma) on every read; a deep carver keeps, in the same plane allocated twice as wide, ONE double per pixel: that value,
-//     formed once by k_wk_init_deep with the arithmetic of px_bright and liblqr's normalisation of the depth (v / 65535 for 16I,
-//     (double) v for 32F, v for 64F).  k_emap_full_deep, k_emap_update_deep and k_frozen_catchup_deep read and move those
-//     doubles where their 8-bit forms unpack a u32.  8 bytes per pixel, whatever the channel count: 32F RGBA is 16, 64F RGBA 32.
+// The seam loop never sees pixels: the DP, the backtrack and the carve work on the float planes whatever the pixel.  Depth and
+// image type reach only
+//   * the value the energy reads.  An 8-bit grey / RGB (+ alpha) carver keeps its pixels packed in the u32 `pix` plane and turns
+//     them into brightness (or luma) on every read; a value-plane carver keeps, in the same plane allocated twice as wide, ONE
+//     double per pixel: that value, formed once by k_wk_init_deep with liblqr's normalisation of the depth (v / 255 for 8I,
+//     v / 65535 for 16I, (double) v for 32F, v for 64F) and the arithmetic of the image type (deep_value).  k_emap_full_deep,
+//     k_emap_update_deep and k_frozen_catchup_deep read and move those doubles where their 8-bit forms unpack a u32.  8 bytes per
+//     pixel, whatever the channel count: 32F RGBA is 16, 64F RGBA 32, 32F CMYKA 20.
 //   * the one-off passes on the base layout: inflate averages new pixels by the rule of the depth (k_inflate_deep); a transpose
 //     of pixels wider than 4 bytes is k_transpose_px, their compaction (flatten, read-out) k_compact_wide / k_compact_jobs_wide;
-//     pixels of 2 or 4 bytes go through the 8-bit kernels, which move them as bytes / one dword.
+//     pixels of up to 4 bytes go through the 8-bit kernels, which move them as bytes / one dword.  A pixel is channels x {1, 2, 4, 8}
+//     bytes, up to 64 channels: any size from 1 to 512, odd ones included (px_move).
 #include "lqr_common.h"
 #include "lqr_kernels.h"
 
@@ -20,32 +24,50 @@ typedef GLOBAL_AS double gf64;
 template <int DEPTH>
 __device__ __forceinline__ double deep_norm(const gu8 *px, int k)
 {
+    if (DEPTH == 0) return norm255(px[k]);
     if (DEPTH == 1) return __ddiv_rn((double) ((const GLOBAL_AS uint16_t *) px)[k], 65535.0);
     if (DEPTH == 2) return (double) ((const GLOBAL_AS float *) px)[k];
     return ((const gf64 *) px)[k];
 }
-// brightness / luma times alpha: px_bright's arithmetic on the depth's normalised channels
+// liblqr's lqr_carver_read_brightness / _luma for the image type (rd.mode) on the depth's normalised channels, every operation
+// rounded individually: px_bright's arithmetic for grey and RGB; CMY(K) turned into RGB first; CUSTOM the mean of the colour
+// channels (each lightened by the black channel, the mean inverted if there is one), brightness and luma alike; then times alpha.
+// The channels are read from global memory one by one (no private array: none of these kernels may use scratch).
 template <int DEPTH>
-__device__ __forceinline__ double deep_value(const gu8 *px, int ch, bool luma)
+__device__ __forceinline__ double deep_value(const gu8 *px, const DeepRead &rd)
 {
     double b;
-    if (ch <= 2) {
+    if (rd.mode == RD_GREY) {
         b = deep_norm<DEPTH>(px, 0);
-        if (ch == 2) b = __dmul_rn(b, deep_norm<DEPTH>(px, 1));
+    } else if (rd.mode == RD_CUSTOM) {
+        const bool has_black = rd.black >= 0;
+        const double kf = __dsub_rn(1.0, has_black ? deep_norm<DEPTH>(px, rd.black) : 0.0);
+        double s = 0.0;
+        for (int k = 0; k < rd.ch; k++)
+            if (k != rd.alpha && k != rd.black) s = __dadd_rn(s, __dsub_rn(1.0, __dmul_rn(__dsub_rn(1.0, deep_norm<DEPTH>(px, k)), kf)));
+        s = __ddiv_rn(s, (double) (rd.ch - (rd.alpha >= 0 ? 1 : 0) - (has_black ? 1 : 0)));
+        b = has_black ? __dsub_rn(1.0, s) : s;
     } else {
-        const double r = deep_norm<DEPTH>(px, 0), g = deep_norm<DEPTH>(px, 1), bl = deep_norm<DEPTH>(px, 2);
-        if (luma)
+        double r = deep_norm<DEPTH>(px, 0), g = deep_norm<DEPTH>(px, 1), bl = deep_norm<DEPTH>(px, 2);
+        if (rd.mode != RD_RGB) {
+            r = __dsub_rn(1.0, r); g = __dsub_rn(1.0, g); bl = __dsub_rn(1.0, bl);
+            if (rd.mode == RD_CMYK) {
+                const double kf = __dsub_rn(1.0, deep_norm<DEPTH>(px, 3));
+                r = __dmul_rn(r, kf); g = __dmul_rn(g, kf); bl = __dmul_rn(bl, kf);
+            }
+        }
+        if (rd.luma)
             b = __dadd_rn(__dadd_rn(__dmul_rn(0.2126, r), __dmul_rn(0.7152, g)), __dmul_rn(0.0722, bl));
         else
             b = __ddiv_rn(__dadd_rn(__dadd_rn(r, g), bl), 3.0);
-        if (ch == 4) b = __dmul_rn(b, deep_norm<DEPTH>(px, 3));
     }
+    if (rd.alpha >= 0) b = __dmul_rn(b, deep_norm<DEPTH>(px, rd.alpha));
     return b;
 }
 
 // E1 for a flat carver: the value plane (and bias / rigidity planes) from the base layout, as k_wk_init
 template <int DEPTH>
-__global__ void k_wk_init_deep(const DevCarver *cs, int w, int h, int stride, int ch, int luma)
+__global__ void k_wk_init_deep(const DevCarver *cs, int w, int h, int stride, DeepRead rd)
 {
     const GCarver c = gview_phys(cs[blockIdx.z]);
     gf64 *val = (gf64 *) c.pix;
@@ -53,11 +75,11 @@ __global__ void k_wk_init_deep(const DevCarver *cs, int w, int h, int stride, in
     if (x == 0 && y == 0) { c.flags[FLAG_ORG] = 0; c.flags[FLAG_ORG_PREV] = 0; c.flags[FLAG_SIDE] = 0; }
     if (x >= stride) return;
     const size_t o = (size_t) y * stride + x;
-    constexpr int bpc = DEPTH == 1 ? 2 : DEPTH == 2 ? 4 : 8;
+    constexpr int bpc = DEPTH == 0 ? 1 : DEPTH == 1 ? 2 : DEPTH == 2 ? 4 : 8;
     double v = 0.0;
     float b = 0.0f, r = 0.0f;
     if (x < w) {
-        v = deep_value<DEPTH>(c.rgb0 + ((size_t) y * w + x) * ch * bpc, ch, luma != 0);
+        v = deep_value<DEPTH>(c.rgb0 + ((size_t) y * w + x) * rd.ch * bpc, rd);
         if (c.bias0) b = c.bias0[(size_t) y * w + x];
         if (c.rig0) r = c.rig0[(size_t) y * w + x];
     }
@@ -68,12 +90,12 @@ __global__ void k_wk_init_deep(const DevCarver *cs, int w, int h, int stride, in
 
 // ... and for a carver that is not flat: the pixels without a level, in order (k_wk_init_visible)
 template <int DEPTH>
-__global__ __launch_bounds__(256) void k_wk_init_visible_deep(const DevCarver *cs, int w0, int h, int stride, int ch, int luma)
+__global__ __launch_bounds__(256) void k_wk_init_visible_deep(const DevCarver *cs, int w0, int h, int stride, DeepRead rd)
 {
     __shared__ int s_wave[4];
     const GCarver c = gview_phys(cs[blockIdx.y]);
     gf64 *val = (gf64 *) c.pix;
-    constexpr int bpc = DEPTH == 1 ? 2 : DEPTH == 2 ? 4 : 8;
+    constexpr int bpc = DEPTH == 0 ? 1 : DEPTH == 1 ? 2 : DEPTH == 2 ? 4 : 8;
     const int y = blockIdx.x, tid = threadIdx.x;
     if (y == 0 && tid == 0) { c.flags[FLAG_ORG] = 0; c.flags[FLAG_ORG_PREV] = 0; c.flags[FLAG_SIDE] = 0; }
     const size_t ri = (size_t) y * w0, ro = (size_t) y * stride;
@@ -84,7 +106,7 @@ __global__ __launch_bounds__(256) void k_wk_init_visible_deep(const DevCarver *c
         int total;
         const int rank = carry + block_rank_256(keep, s_wave, total);
         if (keep && rank < stride) {
-            val[ro + rank] = deep_value<DEPTH>(c.rgb0 + (ri + col) * ch * bpc, ch, luma != 0);
+            val[ro + rank] = deep_value<DEPTH>(c.rgb0 + (ri + col) * rd.ch * bpc, rd);
             if (c.bias) c.bias[ro + rank] = c.bias0 ? c.bias0[ri + col] : 0.0f;
             if (c.rig) c.rig[ro + rank] = c.rig0 ? c.rig0[ri + col] : 0.0f;
         }
@@ -196,27 +218,30 @@ __global__ __launch_bounds__(256) void k_frozen_catchup_deep(const DevCarver *cs
     }
 }
 
-// one pixel of `bytes` bytes (2 .. 32), in the widest unit that divides it: pixels of a plane start at multiples of their size,
-// so the unit is aligned (16-byte accesses for 32F RGBA and 64F grey-alpha / RGBA)
+// one pixel of `bytes` bytes, in the widest unit that divides it: pixels of a plane start at multiples of their size, so the unit
+// is aligned (16-byte accesses for 32F RGBA and 64F grey-alpha / RGBA).  An odd size (8I pixels of 5, 7, 9 .. channels) goes byte
+// by byte: its pixels start on odd addresses, and a wider unit would reach past the pixel
 __device__ __forceinline__ void px_move(uint8_t *dst, const uint8_t *src, int bytes)
 {
     if ((bytes & 15) == 0) for (int k = 0; k < bytes; k += 16) *(u32x4 *) (dst + k) = *(const u32x4 *) (src + k);
     else if ((bytes & 7) == 0) for (int k = 0; k < bytes; k += 8) *(uint64_t *) (dst + k) = *(const uint64_t *) (src + k);
     else if ((bytes & 3) == 0) for (int k = 0; k < bytes; k += 4) *(uint32_t *) (dst + k) = *(const uint32_t *) (src + k);
-    else for (int k = 0; k < bytes; k += 2) *(uint16_t *) (dst + k) = *(const uint16_t *) (src + k);
+    else if ((bytes & 1) == 0) for (int k = 0; k < bytes; k += 2) *(uint16_t *) (dst + k) = *(const uint16_t *) (src + k);
+    else for (int k = 0; k < bytes; k++) dst[k] = src[k];
 }
-// a pixel created by enlargement, channel by channel, by liblqr's rule for the depth (lqr_carver_inflate): 16I the integer
-// floor((a + b) / 2) as for 8I; 32F (a + b) * 0.5f in float; 64F (a + b) * 0.5 in double
+// a pixel created by enlargement, channel by channel (alpha and black like any other), by liblqr's rule for the depth
+// (lqr_carver_inflate): 8I and 16I the integer floor((a + b) / 2); 32F (a + b) * 0.5f in float; 64F (a + b) * 0.5 in double
 __device__ __forceinline__ void px_avg_deep(uint8_t *dst, const uint8_t *a, const uint8_t *b, int ch, int depth)
 {
     for (int k = 0; k < ch; k++) {
-        if (depth == 1) ((uint16_t *) dst)[k] = (uint16_t) (((int) ((const uint16_t *) a)[k] + (int) ((const uint16_t *) b)[k]) >> 1);
+        if (depth == 0) dst[k] = (uint8_t) (((int) a[k] + (int) b[k]) >> 1);
+        else if (depth == 1) ((uint16_t *) dst)[k] = (uint16_t) (((int) ((const uint16_t *) a)[k] + (int) ((const uint16_t *) b)[k]) >> 1);
         else if (depth == 2) ((float *) dst)[k] = __fmul_rn(__fadd_rn(((const float *) a)[k], ((const float *) b)[k]), 0.5f);
         else ((double *) dst)[k] = __dmul_rn(__dadd_rn(((const double *) a)[k], ((const double *) b)[k]), 0.5);
     }
 }
 
-// E14 for the deep carvers of a batch (k_inflate's pass and its fused level self-check; jobs[i].ch = channels)
+// E14 for the carvers of a batch that k_inflate does not take: deep ones, 8I ones of more than 4 channels (k_inflate's pass and its fused level self-check; jobs[i].ch = channels)
 __global__ __launch_bounds__(256) void k_inflate_deep(const InflateDevX *jobs, int w0, int w1, int l, int max_level, int *dev_err)
 {
     __shared__ int s_wave[4];
@@ -227,7 +252,7 @@ __global__ __launch_bounds__(256) void k_inflate_deep(const InflateDevX *jobs, i
     bool twice = false;
     const InflateDevX jx = jobs[blockIdx.y];
     const InflateDev &j = jx.j;
-    const int ch = j.ch, depth = jx.depth, bytes = ch * (depth == 1 ? 2 : depth == 2 ? 4 : 8);
+    const int ch = j.ch, depth = jx.depth, bytes = ch * (depth == 0 ? 1 : depth == 1 ? 2 : depth == 2 ? 4 : 8);
     const int y = blockIdx.x, tid = threadIdx.x;
     const int32_t *vrow = j.vs + (size_t) y * w0;
     const size_t ri = (size_t) y * w0, ro = (size_t) y * w1;
@@ -320,12 +345,14 @@ __global__ __launch_bounds__(256) void k_compact_jobs_wide(const InflateDev *job
 }
 
 // ---- the instantiations the shim launches (lqr_kernels.h declares them)
-template __global__ void k_wk_init_deep<1>(const DevCarver *, int, int, int, int, int);
-template __global__ void k_wk_init_deep<2>(const DevCarver *, int, int, int, int, int);
-template __global__ void k_wk_init_deep<3>(const DevCarver *, int, int, int, int, int);
-template __global__ void k_wk_init_visible_deep<1>(const DevCarver *, int, int, int, int, int);
-template __global__ void k_wk_init_visible_deep<2>(const DevCarver *, int, int, int, int, int);
-template __global__ void k_wk_init_visible_deep<3>(const DevCarver *, int, int, int, int, int);
+template __global__ void k_wk_init_deep<0>(const DevCarver *, int, int, int, DeepRead);
+template __global__ void k_wk_init_deep<1>(const DevCarver *, int, int, int, DeepRead);
+template __global__ void k_wk_init_deep<2>(const DevCarver *, int, int, int, DeepRead);
+template __global__ void k_wk_init_deep<3>(const DevCarver *, int, int, int, DeepRead);
+template __global__ void k_wk_init_visible_deep<0>(const DevCarver *, int, int, int, DeepRead);
+template __global__ void k_wk_init_visible_deep<1>(const DevCarver *, int, int, int, DeepRead);
+template __global__ void k_wk_init_visible_deep<2>(const DevCarver *, int, int, int, DeepRead);
+template __global__ void k_wk_init_visible_deep<3>(const DevCarver *, int, int, int, DeepRead);
 #define INST_EMAP_DEEP(N) template __global__ void k_emap_full_deep<N>(const DevCarver *, DpK, int, int, int); \
     template __global__ void k_emap_update_deep<N, 12>(const DevCarver *, DpK, int, int, int, int, int); \
     template __global__ void k_emap_update_deep<N, 36>(const DevCarver *, DpK, int, int, int, int, int); \

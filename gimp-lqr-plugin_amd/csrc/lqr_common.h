@@ -540,10 +540,20 @@ struct InflateDev {
     float *nbias, *nrig;
     int ch;
 };
-// a job of k_inflate_deep: the carver's depth (LqrColDepth 1 .. 3) beside its planes; j.ch = channels
+// a job of k_inflate_deep: the carver's depth (LqrColDepth; 0 for 8-bit pixels of more than 4 channels) beside its planes; j.ch = channels
 struct InflateDevX {
     InflateDev j;
     int depth;
+};
+// How a carver that reads through the value plane (k_deep.hip) forms the value its energy reads: liblqr's image type
+// (lqr_imagetype.h) reduced to the arithmetic it selects, the alpha and black channel indices (-1: none), brightness or luma
+#define RD_GREY 0           // GREY, GREYA: channel 0
+#define RD_RGB 1            // RGB, RGBA: channels 0 .. 2
+#define RD_CMY 2            // CMY: 1 - channels 0 .. 2
+#define RD_CMYK 3           // CMYK, CMYKA: (1 - channels 0 .. 2) * (1 - channel 3)
+#define RD_CUSTOM 4         // CUSTOM: the mean over the colour channels
+struct DeepRead {
+    int ch, mode, alpha, black, luma;
 };
 #define EU_ROWS 62          // k_emap_update: rows per block (+2 halo rows)
 #ifndef EU_LOGB

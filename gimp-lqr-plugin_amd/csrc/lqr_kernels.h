@@ -52,9 +52,10 @@ __global__ __launch_bounds__(256) void k_compact_jobs(const InflateDev *jobs, in
 __global__ void k_transpose(const InflateDev *jobs, int w, int h);
 __global__ __launch_bounds__(256) void k_mask_line_max(const uint8_t *mask, int channels, int width, int a0, int b0, int line_len, int direction, int *out);
 
-// k_deep.hip (carvers of depth 16I / 32F / 64F; `pix` holds one double per pixel)
-template <int DEPTH> __global__ void k_wk_init_deep(const DevCarver *cs, int w, int h, int stride, int ch, int luma);
-template <int DEPTH> __global__ __launch_bounds__(256) void k_wk_init_visible_deep(const DevCarver *cs, int w0, int h, int stride, int ch, int luma);
+// k_deep.hip (carvers that read through the value plane -- depth 16I / 32F / 64F, image types beyond grey / RGB (+ alpha), more than 4
+// channels: `pix` holds one double per pixel; DEPTH 0 = 8I)
+template <int DEPTH> __global__ void k_wk_init_deep(const DevCarver *cs, int w, int h, int stride, DeepRead rd);
+template <int DEPTH> __global__ __launch_bounds__(256) void k_wk_init_visible_deep(const DevCarver *cs, int w0, int h, int stride, DeepRead rd);
 template <int NRG> __global__ void k_emap_full_deep(const DevCarver *cs, DpK p, int w, int h, int stride);
 template <int NRG, int EU_NT> __global__ __launch_bounds__(64) void k_emap_update_deep(const DevCarver *cs, DpK p, int w, int h, int stride, int k, int epoch);
 __global__ __launch_bounds__(256) void k_frozen_catchup_deep(const DevCarver *cs, int from, int to, int w_from, int h, int stride);

@@ -35,8 +35,10 @@ static int g_n_cu = 0;
 // ===========================================================================
 struct LqrHipCarver {
     int ch = 0;
-    int depth = 0;                   // LqrColDepth: 0 8I (pixels packed in `pix`), 1 .. 3 16I / 32F / 64F (`pix` holds a double per pixel, k_deep.hip)
-    int luma = 0;                    // (depth > 0) the value in `pix` is luma, not brightness
+    int depth = 0;                   // LqrColDepth: 0 8I, 1 .. 3 16I / 32F / 64F
+    int luma = 0;                    // (value plane) the value in `pix` is luma, not brightness
+    int mode = RD_RGB, alpha = -1, black = -1;      // how the value is formed (lqrhip_carver_set_read; DeepRead)
+    int pix_deep = 0;                // `pix` as allocated holds a double per pixel (reads_value() at the time)
     int w0 = 0, h0 = 0;              // base layout dims
     // base planes
     uint8_t *rgb0 = nullptr;
@@ -530,6 +532,23 @@ static int d2h_staged(void *dst, const void *src, size_t bytes)
     return rc;
 }
 
+// A carver reads through the value plane (`pix` holds one double per pixel, the value the energy reads; k_deep.hip) unless it is
+// 8-bit grey / RGB with or without alpha in liblqr's default layout: those keep their pixels packed in `pix` and every kernel they had.
+// (The rule is restated by tests/imgtype_cases.py reads_value; same_config in host/lqr_carver.c groups only carvers whose type
+// and roles are equal, so that a group is on one side of it.  Keep the three in step.)
+static inline bool reads_value(const LqrHipCarver *c)
+{
+    if (c->depth != 0 || c->ch > 4 || (c->mode != RD_GREY && c->mode != RD_RGB)) return true;
+    return c->black >= 0 || c->alpha != (c->ch == 2 ? 1 : c->ch == 4 ? 3 : -1);
+}
+static inline DeepRead deep_read(const LqrHipCarver *c) { return DeepRead{c->ch, c->mode, c->alpha, c->black, c->luma}; }
+// liblqr's default image type for a channel count, as a read mode
+static void default_read(LqrHipCarver *c)
+{
+    c->mode = c->ch <= 2 ? RD_GREY : c->ch <= 4 ? RD_RGB : c->ch == 5 ? RD_CMYK : RD_CUSTOM;
+    c->alpha = c->ch == 2 ? 1 : c->ch == 4 ? 3 : c->ch == 5 ? 4 : -1;
+    c->black = c->ch == 5 ? 3 : -1;
+}
 // bytes per pixel of the base layout
 static inline size_t px_bytes(const LqrHipCarver *c) { return (size_t) c->ch << (c->depth == 0 ? 0 : c->depth == 1 ? 1 : c->depth == 2 ? 2 : 3); }
 
@@ -543,10 +562,11 @@ static int batch_sync_of(LqrHipCarver *c)
 // the base layout: w x h pixels of `channels` values of `depth` (LqrColDepth: 1 / 2 / 4 / 8 bytes each)
 extern "C" LqrHipCarver *lqrhip_carver_create_ext(const void *rgb, int w, int h, int channels, int depth)
 {
-    if (depth < 0 || depth > 3 || channels < 1 || channels > 4) { g_err = "unsupported colour depth / channels"; return nullptr; }
+    if (depth < 0 || depth > 3 || channels < 1 || channels > LQRHIP_MAX_CHANNELS) { g_err = "unsupported colour depth / channels"; return nullptr; }
     if (lqrhip_init() < 0) return nullptr;
     LqrHipCarver *c = new LqrHipCarver();
     c->ch = channels; c->depth = depth; c->w0 = w; c->h0 = h;
+    default_read(c);
     const size_t n = (size_t) w * h, bytes = n * px_bytes(c);
     if (dmalloc(&c->rgb0, bytes) || dmalloc(&c->vs, n)) { lqrhip_carver_destroy(c); return nullptr; }
     // the visibility map is cleared on the same stream, under the upload: one synchronisation for both
@@ -565,9 +585,21 @@ extern "C" LqrHipCarver *lqrhip_carver_create(const unsigned char *rgb, int w, i
 
 extern "C" int lqrhip_carver_set_read_luma(LqrHipCarver *c, int luma)
 {
-    const int changed = c->depth != 0 && (luma != 0) != (c->luma != 0);
+    const int changed = reads_value(c) && (luma != 0) != (c->luma != 0);
     c->luma = luma != 0;
     return changed;
+}
+
+extern "C" int lqrhip_carver_set_read(LqrHipCarver *c, int image_type, int alpha, int black)
+{
+    // LqrImageType: RGB, RGBA, GREY, GREYA, CMY, CMYK, CMYKA, CUSTOM
+    static const int mode_of[8] = {RD_RGB, RD_RGB, RD_GREY, RD_GREY, RD_CMY, RD_CMYK, RD_CMYK, RD_CUSTOM};
+    if (image_type < 0 || image_type > 7 || alpha >= c->ch || black >= c->ch) return LQRHIP_EARG;
+    const bool was = reads_value(c);
+    const int mode = mode_of[image_type], a = alpha < 0 ? -1 : alpha, k = black < 0 ? -1 : black;
+    const bool differs = mode != c->mode || a != c->alpha || k != c->black;
+    c->mode = mode; c->alpha = a; c->black = k;
+    return (differs && (was || reads_value(c))) ? 1 : 0;
 }
 
 static void free_working(LqrHipCarver *c)
@@ -613,11 +645,12 @@ static int ensure_working(LqrHipCarver *c, int w, int h)
 {
     int stride = ((w + 16) + 63) & ~63;
     bool need_bias = c->bias0 != nullptr, need_rig = c->rig0 != nullptr;
-    if (c->pix && c->stride == stride && c->wk_h == h && (!!c->bias == need_bias) && (!!c->rig == need_rig)) return 0;
+    const int deep = reads_value(c) ? 1 : 0;
+    if (c->pix && c->stride == stride && c->wk_h == h && (!!c->bias == need_bias) && (!!c->rig == need_rig) && c->pix_deep == deep) return 0;
     free_working(c);
     c->stride = 0; c->wk_h = 0;
     size_t n = (size_t) stride * (h + 1) + 1024;
-    const size_t npix = c->depth ? 2 * n : n;          // a deep carver's plane holds a double per pixel
+    const size_t npix = deep ? 2 * n : n;              // a value plane holds a double per pixel
     int rc;
     if ((rc = dmalloc(&c->pix, npix)) || (rc = dmalloc(&c->en, n)) || (rc = dmalloc(&c->m, n)) || (rc = dmalloc(&c->least, n)) ||
         (rc = dmalloc(&c->seam_x, (size_t) h + 8)) || (rc = dmalloc(&c->flags, (size_t) FLAG_WORDS)) ||
@@ -633,7 +666,7 @@ static int ensure_working(LqrHipCarver *c, int w, int h)
     if (e == hipSuccess) e = hipMemsetAsync(c->flags, 0, (size_t) FLAG_WORDS * sizeof(int32_t), g_stream0);
     if (e == hipSuccess) e = hipStreamSynchronize(g_stream0);
     if (e != hipSuccess) { free_working(c); HIPCK(e); }
-    c->stride = stride; c->wk_h = h;
+    c->stride = stride; c->wk_h = h; c->pix_deep = deep;
     if (c->batch) c->batch->dirty = true;
     return 0;
 }
@@ -904,16 +937,19 @@ extern "C" int lqrhip_wk_init(LqrHipBatch *b, int from_visible)
     LqrHipCarver *c0 = b->cs[0];
     int w = c0->w0, h = c0->h0, rc;
     for (auto *c : b->cs) {
-        if (c->w0 != w || c->h0 != h || c->ch != c0->ch || c->depth != c0->depth || c->luma != c0->luma) return LQRHIP_EARG;
+        if (c->w0 != w || c->h0 != h || c->ch != c0->ch || c->depth != c0->depth || c->luma != c0->luma || c->mode != c0->mode ||
+            c->alpha != c0->alpha || c->black != c0->black)
+            return LQRHIP_EARG;
         if ((rc = ensure_working(c, w, h))) return rc;
     }
     if ((rc = batch_upload(b))) return rc;
     for (auto *c : b->cs) c->frozen_epoch = 0;
-    if (c0->depth) {
+    if (reads_value(c0)) {
         const dim3 grid((c0->stride + 255) / 256, h, (unsigned) b->cs.size()), grid_v(h, (unsigned) b->cs.size());
-#define LAUNCH_WKD(D) do { if (from_visible) hipLaunchKernelGGL(k_wk_init_visible_deep<D>, grid_v, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, c0->ch, c0->luma); \
-                           else hipLaunchKernelGGL(k_wk_init_deep<D>, grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, c0->ch, c0->luma); } while (0)
-        if (c0->depth == 1) LAUNCH_WKD(1); else if (c0->depth == 2) LAUNCH_WKD(2); else LAUNCH_WKD(3);
+        const DeepRead rd = deep_read(c0);
+#define LAUNCH_WKD(D) do { if (from_visible) hipLaunchKernelGGL(k_wk_init_visible_deep<D>, grid_v, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, rd); \
+                           else hipLaunchKernelGGL(k_wk_init_deep<D>, grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, rd); } while (0)
+        if (c0->depth == 0) LAUNCH_WKD(0); else if (c0->depth == 1) LAUNCH_WKD(1); else if (c0->depth == 2) LAUNCH_WKD(2); else LAUNCH_WKD(3);
 #undef LAUNCH_WKD
     } else if (from_visible) {
         hipLaunchKernelGGL(k_wk_init_visible, dim3(h, (unsigned) b->cs.size()), dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, c0->ch);
@@ -932,7 +968,7 @@ extern "C" int lqrhip_emap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w,
     LqrHipCarver *c0 = b->cs[0];
     dim3 grid((w + 255) / 256, h, (unsigned) b->cs.size());
     DpK k = make_dpk(p, c0->ch);
-    if (c0->depth) {
+    if (reads_value(c0)) {
 #define LAUNCH_EMAP(N) hipLaunchKernelGGL((k_emap_full_deep<N>), grid, dim3(256), 0, b->stream, b->d_desc, k, w, h, c0->stride)
         NRG_DISPATCH(p->nrg_func, LAUNCH_EMAP)
 #undef LAUNCH_EMAP
@@ -1181,7 +1217,7 @@ static int frozen_catchup(LqrHipBatch *b, int to, int w_at_to, int h)
     if (to <= from) return 0;
     const int w_from = w_at_to + (to - from);
     size_t lds = (size_t) (to - from) * sizeof(int) + (size_t) w_from + 16;
-    if (c0->depth)
+    if (reads_value(c0))
         hipLaunchKernelGGL(k_frozen_catchup_deep, dim3(h, (unsigned) b->cs.size()), dim3(256), lds, b->stream, b->d_desc, from, to, w_from, h,
                            c0->stride);
     else
@@ -1366,8 +1402,8 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
     }
     // Single images and groups up to 4: the carve and the energy update in one launch (k_carve_e, k_carve.hip) -- the wave that has moved
     // a row refreshes that row's energies; one dependent launch less per seam.  delta_x <= 2 (12 brightness samples per row).
-    // (deep carvers: the two kernels, k_carve and k_emap_update_deep)
-    const bool fuse_e = p->delta_x <= 2 && vp_group <= (size_t) g_carve_fused && wnew > 1 && c0->depth == 0;
+    // (value-plane carvers: the two kernels, k_carve and k_emap_update_deep)
+    const bool fuse_e = p->delta_x <= 2 && vp_group <= (size_t) g_carve_fused && wnew > 1 && !reads_value(c0);
     if (fuse_e) {
         const int lag_max = n <= 4 ? FROZEN_LAG_MAX / 4 : FROZEN_LAG_MAX;
         if (log_index + 1 - c0->frozen_epoch > lag_max && (rc = frozen_catchup(b, log_index + 1, wnew, h))) return rc;      // (needs the seam log only: before the carve)
@@ -1399,7 +1435,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
 #define LAUNCH_EUPD(N) do { if (p->delta_x <= 2) LAUNCH_EUPD_NT(N, 12); else if (p->delta_x <= 8) LAUNCH_EUPD_NT(N, 36); else LAUNCH_EUPD_NT(N, 68); } while (0)
 #define LAUNCH_EUPD_NT_DEEP(N, NT) hipLaunchKernelGGL((k_emap_update_deep<N, NT>), dim3((h + EU_ROWS - 1) / EU_ROWS, n), dim3(64), 0, b->stream, b->d_desc, k, wnew, h, stride, log_index, epoch)
 #define LAUNCH_EUPD_DEEP(N) do { if (p->delta_x <= 2) LAUNCH_EUPD_NT_DEEP(N, 12); else if (p->delta_x <= 8) LAUNCH_EUPD_NT_DEEP(N, 36); else LAUNCH_EUPD_NT_DEEP(N, 68); } while (0)
-        if (c0->depth) { NRG_DISPATCH(p->nrg_func, LAUNCH_EUPD_DEEP) }
+        if (reads_value(c0)) { NRG_DISPATCH(p->nrg_func, LAUNCH_EUPD_DEEP) }
         else { NRG_DISPATCH(p->nrg_func, LAUNCH_EUPD) }
 #undef LAUNCH_EUPD_DEEP
 #undef LAUNCH_EUPD_NT_DEEP
@@ -1614,15 +1650,15 @@ struct PlaneJobs {
         depth.push_back(c->depth);
         return 0;
     }
-    // inflate (by_width = false): 8-bit jobs -> dev8, the others -> devx; transpose and flatten (by_width): pixels of up to 4 bytes ->
+    // inflate (by_width = false): 8-bit jobs of up to 4 channels -> dev8, the others -> devx; transpose and flatten (by_width): pixels of up to 4 bytes ->
     // dev8 (the 8-bit kernels move them as bytes / one dword), wider ones -> devw (k_deep.hip's kernels, 16-byte accesses where they fit)
     int split(hipStream_t s, bool by_width)
     {
         for (size_t i = 0; i < dev.size(); i++) {
             InflateDev d = dev[i];
             if (by_width) { (d.ch <= 4 ? dev8 : devw).push_back(d); continue; }
-            if (depth[i] == 0) { dev8.push_back(d); continue; }
-            d.ch = d.ch >> (depth[i] == 1 ? 1 : depth[i] == 2 ? 2 : 3);
+            if (depth[i] == 0 && d.ch <= 4) { dev8.push_back(d); continue; }
+            d.ch = d.ch >> depth[i];
             devx.push_back(InflateDevX{d, depth[i]});
         }
         int rc;

@@ -22,6 +22,7 @@
 
 #include "../../include/lqr.h"
 #include "../../include/lqr_coldepth.h"
+#include "../../include/lqr_imagetype.h"
 #include "../../include/lqr_hip.h"
 
 #define MAXI(a, b) ((a) > (b) ? (a) : (b))
@@ -57,6 +58,8 @@ struct _LqrCarver {
     int level, max_level;
     int channels;
     int col_depth;              /* LqrColDepth: 0 (8I, what lqr_carver_new makes) .. 3 (64F) */
+    int image_type;             /* LqrImageType, with the channel indices of its roles (-1: none): what the energy reads (lqr_imagetype.h) */
+    int alpha_channel, black_channel;
     int preserve_input;         /* lqr_carver_set_preserve_input_image: the caller's buffer is never written nor freed */
     int img_w, img_h;           /* the image handed to lqr_carver_new */
     int transposed;
@@ -179,6 +182,23 @@ void lqr_vmap_destroy(LqrVMap *v) { if (v) { free(v->buffer); free(v); } }
 /* ======================= lifecycle ======================================= */
 /* the carver of lqr_carver_new / lqr_carver_new_ext, arguments checked: pixels of `depth` (LqrColDepth) uploaded as the base
  * layout, liblqr's defaults */
+static const LqrImageType default_type[6] = {LQR_RGB_IMAGE, LQR_GREY_IMAGE, LQR_GREYA_IMAGE, LQR_RGB_IMAGE, LQR_RGBA_IMAGE, LQR_CMYKA_IMAGE};
+static void set_type_defaults(LqrCarver *r, LqrImageType t)
+{
+    r->image_type = (int) t;
+    r->alpha_channel = t == LQR_GREYA_IMAGE ? 1 : t == LQR_RGBA_IMAGE ? 3 : t == LQR_CMYKA_IMAGE ? 4 : -1;
+    r->black_channel = (t == LQR_CMYK_IMAGE || t == LQR_CMYKA_IMAGE) ? 3 : -1;
+}
+
+/* the limit on channels per pixel: 4 unless the caller raised it (lqr_imagetype.h) */
+static int g_max_channels = 4;
+gint lqrx_set_max_channels(gint n)
+{
+    const int prev = g_max_channels;
+    if (n >= 4 && n <= LQRHIP_MAX_CHANNELS) g_max_channels = n;
+    return prev;
+}
+
 static LqrCarver *carver_new(void *buffer, int width, int height, int channels, int depth)
 {
     LqrCarver *r = (LqrCarver *) calloc(1, sizeof *r);
@@ -193,13 +213,15 @@ static LqrCarver *carver_new(void *buffer, int width, int height, int channels, 
      * and becomes the read-out buffer: handing 33 MB back to the C library and asking for 31 MB again costs an munmap, an
      * mmap and a page fault per 4 KiB -- more than the transfer itself (measured: 64 x 4K uploads 207 ms with the free, 62 without) */
     r->col_depth = depth;
+    r->channels = channels;
+    set_type_defaults(r, channels >= 6 ? LQR_CUSTOM_IMAGE : default_type[channels]);
+    (void) lqrhip_carver_set_read(r->dev, r->image_type, r->alpha_channel, r->black_channel);
     r->in_buffer = (guchar *) buffer;
     r->in_buffer_len = (size_t) width * height * channels * k_depth_bytes[depth];
     r->level = r->max_level = 1;
     r->delta_x = 1;
     r->w = r->w0 = r->w_start = width;
     r->h = r->h0 = r->h_start = height;
-    r->channels = channels;
     r->img_w = width; r->img_h = height;
     r->nrg_func = LQR_EF_GRAD_XABS;
     r->nrg_radius = 1;
@@ -212,7 +234,12 @@ static LqrCarver *carver_new(void *buffer, int width, int height, int channels, 
 
 LqrCarver *lqr_carver_new(guchar *buffer, gint width, gint height, gint channels)
 {
-    if (!buffer || width < 1 || height < 1 || channels < 1 || channels > 4) return NULL;
+    if (!buffer || width < 1 || height < 1 || channels < 1) return NULL;
+    if (channels > g_max_channels) {        /* (said on stderr since the limit can be raised; lqr_carver_new_ext always said it) */
+        fprintf(stderr, "liblqr-hip: lqr_carver_new: %d channels are not supported (1 .. %d channels; lqrx_set_max_channels raises the limit)\n",
+                channels, g_max_channels);
+        return NULL;
+    }
     return carver_new(buffer, width, height, channels, LQR_COLDEPTH_8I);
 }
 
@@ -221,9 +248,9 @@ LqrCarver *lqr_carver_new(guchar *buffer, gint width, gint height, gint channels
 LqrCarver *lqr_carver_new_ext(void *buffer, gint width, gint height, gint channels, LqrColDepth colour_depth)
 {
     const int depth = (int) colour_depth;
-    if (channels > 4 || depth < LQR_COLDEPTH_8I || depth > LQR_COLDEPTH_64F) {
-        fprintf(stderr, "liblqr-hip: lqr_carver_new_ext: %d channels at colour depth %d are not supported (1 .. 4 channels, depths 8I 16I 32F 64F)\n",
-                channels, depth);
+    if (channels > g_max_channels || depth < LQR_COLDEPTH_8I || depth > LQR_COLDEPTH_64F) {
+        fprintf(stderr, "liblqr-hip: lqr_carver_new_ext: %d channels at colour depth %d are not supported (1 .. %d channels, depths 8I 16I 32F 64F; "
+                "lqrx_set_max_channels raises the channel limit)\n", channels, depth, g_max_channels);
         return NULL;
     }
     if (!buffer || width < 1 || height < 1 || channels < 1) return NULL;
@@ -233,11 +260,36 @@ LqrCarver *lqr_carver_new_ext(void *buffer, gint width, gint height, gint channe
 void lqr_carver_set_preserve_input_image(LqrCarver *r) { r->preserve_input = 1; }
 LqrColDepth lqr_carver_get_col_depth(LqrCarver *r) { return (LqrColDepth) r->col_depth; }
 gint lqr_carver_get_bpp(LqrCarver *r) { return r->channels; }          /* liblqr: the deprecated name of get_channels */
-LqrImageType lqr_carver_get_image_type(LqrCarver *r)
+LqrImageType lqr_carver_get_image_type(LqrCarver *r) { return (LqrImageType) r->image_type; }
+
+/* the image type and its roles as they stand go to the device; a root carver whose energy reads something else now lays its
+ * working planes out again at the next session (an attached carver has none) */
+static void type_changed(LqrCarver *r)
 {
-    static const LqrImageType by_channels[5] = {LQR_RGB_IMAGE, LQR_GREY_IMAGE, LQR_GREYA_IMAGE, LQR_RGB_IMAGE, LQR_RGBA_IMAGE};
-    return by_channels[r->channels];
+    if (lqrhip_carver_set_read(r->dev, r->image_type, r->alpha_channel, r->black_channel) == 1 && !r->root) r->wk_valid = 0;
 }
+LqrRetVal lqr_carver_set_image_type(LqrCarver *r, LqrImageType image_type)
+{
+    static const int channels_of[7] = {3, 4, 1, 2, 3, 4, 5};        /* RGB RGBA GREY GREYA CMY CMYK CMYKA */
+    if ((int) image_type < LQR_RGB_IMAGE || (int) image_type > LQR_CUSTOM_IMAGE) return LQR_ERROR;
+    if (image_type != LQR_CUSTOM_IMAGE && channels_of[image_type] != r->channels) return LQR_ERROR;
+    set_type_defaults(r, image_type);
+    type_changed(r);
+    return LQR_OK;
+}
+/* one role moved to channel `index` (negative: cleared); the other role loses the channel if it held it */
+static LqrRetVal set_role(LqrCarver *r, int *role, int *other, int index)
+{
+    if (index >= r->channels) return LQR_ERROR;
+    if (index < 0) index = -1;
+    else if (*other == index) *other = -1;
+    *role = index;
+    r->image_type = LQR_CUSTOM_IMAGE;
+    type_changed(r);
+    return LQR_OK;
+}
+LqrRetVal lqr_carver_set_alpha_channel(LqrCarver *r, gint i) { return set_role(r, &r->alpha_channel, &r->black_channel, i); }
+LqrRetVal lqr_carver_set_black_channel(LqrCarver *r, gint i) { return set_role(r, &r->black_channel, &r->alpha_channel, i); }
 
 LqrRetVal lqr_carver_init(LqrCarver *r, gint delta_x, gfloat rigidity)
 {
@@ -296,12 +348,12 @@ LqrRetVal lqr_carver_attach(LqrCarver *r, LqrCarver *aux)
 /* ======================= configuration =================================== */
 LqrRetVal lqr_carver_set_energy_function_builtin(LqrCarver *r, LqrEnergyFuncBuiltinType ef)
 {
+    /* a value-plane carver's working planes hold the value the energy reads (brightness or luma): a change of kind rebuilds them.
+     * Every carver is told, a packed 8-bit one too: a later lqr_carver_set_image_type can turn it into a value-plane carver, which
+     * then finds the flag; the call returns 1 only where the planes in use change. */
+    const int luma = (int) ef >= LQR_EF_LUMA_GRAD_NORM && (int) ef <= LQR_EF_LUMA_GRAD_XABS;
     if ((int) ef < LQR_EF_GRAD_NORM || (int) ef > LQR_EF_NULL) return LQR_ERROR;
-    if (r->col_depth != LQR_COLDEPTH_8I) {
-        /* a deep carver's working planes hold the value the energy reads (brightness or luma): a change of kind rebuilds them */
-        const int luma = (int) ef >= LQR_EF_LUMA_GRAD_NORM && (int) ef <= LQR_EF_LUMA_GRAD_XABS;
-        if (lqrhip_carver_set_read_luma(r->dev, luma)) r->wk_valid = 0;
-    }
+    if (lqrhip_carver_set_read_luma(r->dev, luma)) r->wk_valid = 0;
     r->nrg_func = (int) ef;
     r->nrg_radius = (ef == LQR_EF_NULL) ? 0 : 1;
     return LQR_OK;
@@ -738,6 +790,8 @@ static LqrRetVal group_resize_dir(Group *g, int w1, int want_transposed)
     return LQR_OK;
 }
 
+/* (type and roles: a group reads alike, so it is all packed or all value-plane -- reads_value in csrc/lqr_shim.hip -- and the
+ * launch arguments of the read hold for every member) */
 static int same_config(const LqrCarver *a, const LqrCarver *b)
 {
     LqrCarverList *la = a->attached, *lb = b->attached;
@@ -746,7 +800,8 @@ static int same_config(const LqrCarver *a, const LqrCarver *b)
         a->transposed != b->transposed || a->active != b->active || a->delta_x != b->delta_x || a->rigidity != b->rigidity ||
         a->has_bias != b->has_bias || a->has_rigmask != b->has_rigmask || a->nrg_func != b->nrg_func ||
         a->leftright != b->leftright || a->lr_switch_frequency != b->lr_switch_frequency || a->enl_step != b->enl_step ||
-        a->resize_order != b->resize_order || a->wk_valid != b->wk_valid || a->col_depth != b->col_depth)
+        a->resize_order != b->resize_order || a->wk_valid != b->wk_valid || a->col_depth != b->col_depth ||
+        a->image_type != b->image_type || a->alpha_channel != b->alpha_channel || a->black_channel != b->black_channel)
         return 0;
     for (; la && lb; la = la->next, lb = lb->next)
         if (la->current->channels != lb->current->channels || la->current->col_depth != lb->current->col_depth) return 0;

@@ -11,8 +11,10 @@
  *   LQR_COLDEPTH_16I  unsigned short   energy reads v / 65535
  *   LQR_COLDEPTH_32F  float            energy reads (double) v
  *   LQR_COLDEPTH_64F  double           energy reads v
- * channels is 1 .. 4 (grey, grey + alpha, RGB, RGBA); more channels, or a depth outside the enum,
- * make lqr_carver_new_ext return NULL with one line on stderr.  lqr_carver_new_ext(..., LQR_COLDEPTH_8I)
+ * channels is 1 .. 4 (grey, grey + alpha, RGB, RGBA) by default; lqr_imagetype.h raises that limit
+ * (lqrx_set_max_channels: CMYKA and custom layouts of up to 64 channels) and sets what the channels
+ * mean (CMY, CMYK, ...).  More channels than the limit in force, or a depth outside the enum, make
+ * lqr_carver_new_ext return NULL with one line on stderr.  lqr_carver_new_ext(..., LQR_COLDEPTH_8I)
  * is lqr_carver_new.  Float values outside [0, 1] and negative ones are carved as they are.
  *
  * Buffer ownership (as liblqr): the carver owns `buffer` and free()s it at lqr_carver_destroy,

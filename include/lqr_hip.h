@@ -37,6 +37,7 @@ extern "C" {
 #define LQRHIP_EARG (-3)
 #define LQRHIP_EFAULT (-4)   /* a kernel of the session gave up or a self-check failed: roll back, redo (lqrhip_session_rollback) */
 #define LQRHIP_MAX_DELTA 16
+#define LQRHIP_MAX_CHANNELS 64      /* channels per pixel at most (lqrx_set_max_channels) */
 
 typedef struct LqrHipCarver LqrHipCarver;   /* device-resident planes of one carver */
 typedef struct LqrHipBatch LqrHipBatch;     /* n carvers advancing in lock-step     */
@@ -63,9 +64,14 @@ LqrHipCarver *lqrhip_carver_create(const unsigned char *rgb, int w, int h, int c
 /* lqr_carver_new_ext (lqr_coldepth.h): the same for pixels of `depth` (LqrColDepth 0 .. 3: channels x 1 / 2 / 4 / 8 bytes).
  * Every call below that moves base-layout pixels (read-out, reset) moves w x h x channels x that many bytes. */
 LqrHipCarver *lqrhip_carver_create_ext(const void *rgb, int w, int h, int channels, int depth);
-/* a carver of depth 16I / 32F / 64F keeps the value its energy reads (brightness, or luma with `luma`) in its working
+/* a carver that reads through the value plane (depth 16I / 32F / 64F, or see lqrhip_carver_set_read) keeps the value its energy reads (brightness, or luma with `luma`) in its working
  * planes: returns 1 if that kind changed, i.e. the working planes must be laid out again (lqrhip_wk_init) */
 int lqrhip_carver_set_read_luma(LqrHipCarver *c, int luma);
+/* liblqr's image type (lqr_imagetype.h: LqrImageType 0 .. 7) with its alpha and black channel indices (negative: none).  8-bit grey /
+ * RGB carvers with or without alpha in the default layout keep their packed pixels; every other carver reads through the value
+ * plane as the deep ones do.  Returns 1 if what the energy reads changed (the working planes must be laid out again), 0 if not,
+ * LQRHIP_EARG for a type or an index out of range. */
+int lqrhip_carver_set_read(LqrHipCarver *c, int image_type, int alpha, int black);
 void lqrhip_carver_destroy(LqrHipCarver *c);
 /* Start over on an existing carver, as lqr_carver_destroy + lqr_carver_new + lqr_carver_init would
  * (render.c:376,222,224), but from an image that is already in HBM: the base layout becomes the

@@ -369,6 +369,27 @@ class RefCarver:
         self.aux.append(aux)
         return aux
 
+    # -- the image type (include/lqr_imagetype.h), as binding.Carver's
+    def set_image_type(self, image_type):
+        return self.r.call("lqr_carver_set_image_type", self.p, int(image_type))
+
+    def set_alpha_channel(self, index):
+        return self.r.call("lqr_carver_set_alpha_channel", self.p, int(index))
+
+    def set_black_channel(self, index):
+        return self.r.call("lqr_carver_set_black_channel", self.p, int(index))
+
+    def read_planes(self):
+        """lqr_carver_read_brightness and lqr_carver_read_luma of every pixel of the carver as it stands: two float64 arrays"""
+        r = self.r
+        W, H = r.call("lqr_carver_get_width", self.p), r.call("lqr_carver_get_height", self.p)
+        out = np.zeros((2, H, W), np.float64)
+        for i, fn in enumerate(("lqr_carver_read_brightness", "lqr_carver_read_luma")):
+            for y in range(H):
+                for x in range(W):
+                    out[i, y, x] = r.call(fn, self.p, x, y, fp=True)
+        return out[0], out[1]
+
     def _px(self):
         dt = np.dtype(self.DTYPES[getattr(self, "depth", 0)])
         return dt, self.ch * dt.itemsize
