@@ -87,6 +87,15 @@ struct ProfRec {
 static int g_prof = 0;                 // 0 off, 1 every kernel, 2 the roofline kernel (k_carve) only
 static std::map<std::string, ProfRec> g_profrec;
 static hipStream_t g_stream0 = nullptr;
+// the launch census (test hook, lqr_hip.h): which form of each stage was launched, counted on the host at the launch sites
+static unsigned long long g_census[LQRHIP_CENSUS_SLOTS];
+#define CENSUS(slot) (g_census[(slot)]++)
+extern "C" int lqrhip_launch_census(unsigned long long *out, int n, int reset)
+{
+    if (out && n > 0) memcpy(out, g_census, (size_t) std::min(n, (int) LQRHIP_CENSUS_SLOTS) * sizeof g_census[0]);
+    if (reset) memset(g_census, 0, sizeof g_census);
+    return LQRHIP_CENSUS_SLOTS;
+}
 
 extern "C" const char *lqrhip_last_error(void) { return g_err.c_str(); }
 
@@ -989,6 +998,7 @@ static int launch_dp_tiled(LqrHipBatch *b, const DpK &k, int w, int h, int lr)
     const dim3 grid((w + DPT_OWN - 1) / DPT_OWN, (unsigned) b->cs.size());
 #define LAUNCH_TILE(LRV, RIGV) hipLaunchKernelGGL((k_dp_tile<LRV, RIGV>), grid, dim3(64), 0, b->stream, b->d_desc, k, w, h, c0->stride, y0)
     for (int y0 = 0; y0 < h; y0 += DPT_ROWS) {
+        CENSUS(LQRHIP_CENSUS_DP_TILE);
         if (lr) { if (k.use_rig) LAUNCH_TILE(true, true); else LAUNCH_TILE(true, false); }
         else { if (k.use_rig) LAUNCH_TILE(false, true); else LAUNCH_TILE(false, false); }
     }
@@ -1099,6 +1109,7 @@ static int launch_dp_persistent(LqrHipBatch *b, const DpK &k, int w, int h, int 
     }
     const int epoch = 1 + ((b->tile_epoch++) % ((1 << (31 - DPP_BLK_BITS)) - 2));          // never 0; above the block index in the 32-bit tag
     const dim3 grid(ntiles, (unsigned) n);
+    CENSUS(general ? LQRHIP_CENSUS_TILE_P_GENERAL : px == 3 ? LQRHIP_CENSUS_TILE_P_G3 : px == 2 ? LQRHIP_CENSUS_TILE_P_G2 : LQRHIP_CENSUS_TILE_P_G4);
 #define LAUNCH_TILE(PXV, LRV, RIGV) hipLaunchKernelGGL((k_dp_tile_p<PXV, LRV, RIGV, UPDATE>), grid, dim3(64 * DPP_W), 0, b->stream, b->d_desc + first, k, w, h, c0->stride, b->exch, epoch, g_dev_err)
 #define LAUNCH_TILE_PX(PXV)                                                                 \
     do {                                                                                    \
@@ -1178,9 +1189,13 @@ static int launch_dp(LqrHipBatch *b, const DpK &k, int w, int h, int lr)
     dim3 grid((unsigned) b->cs.size());
 #define LAUNCH_DP_T(P, T)                                                                                             \
     do {                                                                                                              \
-        if (lds > 64 * 1024)                                                                                          \
+        if (lds > 64 * 1024) {                                                                                        \
             HIPCK(hipFuncSetAttribute((const void *) k_dp_sweep<P, UPDATE, T>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                       (int) lds));                                                                    \
+            CENSUS(LQRHIP_CENSUS_LDS_ATTR_SWEEP);                                                                     \
+        }                                                                                                             \
+        CENSUS(LQRHIP_CENSUS_SWEEP + 2 * (P == 1 ? 0 : P == 2 ? 1 : P == 4 ? 2 : P == 8 ? 3 : 4) + (T == DP_THREADS ? 1 : 0)); \
+        CENSUS(UPDATE ? LQRHIP_CENSUS_SWEEP_UPDATE : LQRHIP_CENSUS_SWEEP_FULL);                                       \
         hipLaunchKernelGGL((k_dp_sweep<P, UPDATE, T>), grid, dim3(T), lds, b->stream, b->d_desc, k, w, h, c0->stride, lr); \
     } while (0)
 #define LAUNCH_DP(P) do { if constexpr (UPDATE) { if (nth == 256) LAUNCH_DP_T(P, 256); else LAUNCH_DP_T(P, DP_THREADS); } else LAUNCH_DP_T(P, DP_THREADS); } while (0)
@@ -1267,6 +1282,7 @@ static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr
     }
     const int epoch = 1 + ((b->tile_epoch++) % ((1 << 22) - 2));           // never 0; 22 bits above the 10 bits of level + 1
     const dim3 grid((unsigned) (8 * ((n + 7) / 8) * P));          // the slots of an image on one XCD (k_levels.hip)
+    CENSUS(LQRHIP_CENSUS_BAND_LEVELS);
 #define LAUNCH_LV(LRV, RIGV, DV, RMV) hipLaunchKernelGGL((k_band_levels<LRV, RIGV, DV, RMV>), grid, dim3(128), 0, b->stream, b->d_desc, k, w, h, c0->stride, b->exch, epoch, g_dev_err, P, (int) n)
 #define LAUNCH_LV_LR(RIGV, DV, RMV) do { if (lr) LAUNCH_LV(true, RIGV, DV, RMV); else LAUNCH_LV(false, RIGV, DV, RMV); } while (0)
 #define LAUNCH_LV_D(DV) do { if (!k.use_rig) LAUNCH_LV_LR(false, DV, false); else if (!rigm) LAUNCH_LV_LR(true, DV, false); else LAUNCH_LV_LR(true, DV, true); } while (0)
@@ -1372,6 +1388,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
         }
         if (grew) { b->dirty = true; if ((rc = batch_upload(b))) return rc; }
         ProfScope ps("vpath", b->stream, 0);
+        CENSUS(LQRHIP_CENSUS_VP_PARALLEL);
 #define LAUNCH_VP(DV) do { \
         hipLaunchKernelGGL(k_vp_maps<DV>, dim3((w + 255) / 256, nchunks, n), dim3(256), 0, b->stream, b->d_desc, w, h, stride); \
         hipLaunchKernelGGL(k_vp_solve<DV>, dim3(n), dim3(VPATH_THREADS), (size_t) (nchunks + 2) * sizeof(int), b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit); } while (0)
@@ -1382,6 +1399,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
 #undef LAUNCH_VP
     } else {
         ProfScope ps("vpath", b->stream, 0);
+        CENSUS(p->delta_x <= 7 ? LQRHIP_CENSUS_VPATH1 : LQRHIP_CENSUS_VPATH);
         if (p->delta_x == 1)
             hipLaunchKernelGGL(k_vpath1<1>, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit);
         else if (p->delta_x == 2)
@@ -1409,6 +1427,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
         if (log_index + 1 - c0->frozen_epoch > lag_max && (rc = frozen_catchup(b, log_index + 1, wnew, h))) return rc;      // (needs the seam log only: before the carve)
         const int epoch = c0->frozen_epoch;
         ProfScope ps("carve", b->stream, 4.0 * (double) w * h * n);
+        CENSUS(LQRHIP_CENSUS_CARVE_E);
 #define LAUNCH_CE(N) hipLaunchKernelGGL((k_carve_e<N>), dim3((h + 3) / 4, n), dim3(256), 0, b->stream, b->d_desc, k, w, h, stride, move_dp, log_index, epoch)
         NRG_DISPATCH(p->nrg_func, LAUNCH_CE)
 #undef LAUNCH_CE
@@ -1418,6 +1437,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
         ProfScope ps("carve", b->stream, 4.0 * (double) w * h * n);
         // (a grid of a half, a quarter, an eighth of the rows, the kernel striding over the rest, measured at 64 x 4K in round 5: 508 / 504 / 490 k
         // against 488 - 501 k: inside the run-to-run spread; not adopted)
+        CENSUS(LQRHIP_CENSUS_CARVE);
         hipLaunchKernelGGL(k_carve, dim3((h + 3) / 4, n), dim3(256), 0, b->stream, b->d_desc, w, h, stride, p->delta_x, move_dp);
     }
     if (wnew <= 1) {            // liblqr's finish_vsmap case: nothing left to update
@@ -1495,6 +1515,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
     const bool band_tw = fast_band && g_update_mode != 2 && wnew <= 4200 && (size_t) 2 * h * sizeof(int) <= 64 * 1024;
     if (band_tw) {
         ProfScope ps("band_update", b->stream, 0);
+        CENSUS(LQRHIP_CENSUS_BAND_TW);
 #define LAUNCH_TW(LRV, RIGV) hipLaunchKernelGGL((k_band_update_tw<4, LRV, RIGV>), dim3(n), dim3(128 * 4), (size_t) 2 * h * sizeof(int), b->stream, b->d_desc, k, wnew, h, stride, g_dev_err)
         if (leftright_next) { if (p->use_rigidity) LAUNCH_TW(true, true); else LAUNCH_TW(true, false); }
         else { if (p->use_rigidity) LAUNCH_TW(false, true); else LAUNCH_TW(false, false); }
@@ -1504,7 +1525,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
         // the kernels around it (k_vpath1 74 -> 92 us, k_carve 149 -> 162), the step is not the sum of a chain's kernels; removed)
     } else if (fast_band) {
         ProfScope ps("band_update", b->stream, 0);
-#define LAUNCH_MW(NWV, LRV, RIGV) hipLaunchKernelGGL((k_band_update_mw<2, NWV, 8, LRV, RIGV>), dim3(n), dim3(64 * NWV), (size_t) h * sizeof(int), b->stream, b->d_desc, k, wnew, h, stride)
+#define LAUNCH_MW(NWV, LRV, RIGV) do { CENSUS(NWV == 16 ? LQRHIP_CENSUS_BAND_MW16 : LQRHIP_CENSUS_BAND_MW8); hipLaunchKernelGGL((k_band_update_mw<2, NWV, 8, LRV, RIGV>), dim3(n), dim3(64 * NWV), (size_t) h * sizeof(int), b->stream, b->d_desc, k, wnew, h, stride); } while (0)
 #define LAUNCH_MW_N(LRV, RIGV) do { if (wnew > 4200) LAUNCH_MW(16, LRV, RIGV); /* 8K: dirty regions up to ~900 px */ else LAUNCH_MW(8, LRV, RIGV); } while (0)
         if (leftright_next) { if (p->use_rigidity) LAUNCH_MW_N(true, true); else LAUNCH_MW_N(true, false); }
         else { if (p->use_rigidity) LAUNCH_MW_N(false, true); else LAUNCH_MW_N(false, false); }
@@ -1512,6 +1533,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
 #undef LAUNCH_MW
     } else {
         ProfScope ps("band_update", b->stream, 0);
+        CENSUS(LQRHIP_CENSUS_BAND_GENERIC);
         hipLaunchKernelGGL(k_band_update, dim3(n), dim3(64), 0, b->stream, b->d_desc, k, wnew, h, stride, leftright_next);
     }
     {
@@ -1535,9 +1557,13 @@ extern "C" int lqrhip_vs_commit(LqrHipBatch *b, int w0, int h0, int wc0, int n_s
     int rc;
     if ((rc = batch_upload(b))) return rc;
     size_t lds = ((size_t) n_seams + wc0) * sizeof(int);
+    // (unreachable while the host refuses frames wider than LQRHIP_MAX_FRAME_WIDTH, host/lqr_carver.c: a session carves at most wc0 - 1
+    // seams, so n_seams + wc0 <= 2 * 16384 - 1 ints = 128 KB)
     if (lds > 150 * 1024) { g_err = "vs_commit: session too large for LDS"; return LQRHIP_EARG; }
-    if (lds > 64 * 1024)
+    if (lds > 64 * 1024) {
         HIPCK(hipFuncSetAttribute((const void *) k_vs_commit, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+        CENSUS(LQRHIP_CENSUS_LDS_ATTR_COMMIT);
+    }
     hipLaunchKernelGGL(k_vs_commit, dim3(h0, (unsigned) b->cs.size()), dim3(256), lds, b->stream, b->d_desc, w0, h0, wc0, n_seams,
                        first_level, finish);
     HIPCK(hipGetLastError());

@@ -808,6 +808,28 @@ static int same_config(const LqrCarver *a, const LqrCarver *b)
     return !la && !lb;
 }
 
+/* The supported geometry: a session starts from a frame of at most LQRHIP_MAX_FRAME_WIDTH
+ * px in the direction it carves.  Which kernels a wider frame would meet depends on the path it happens to take (the persistent
+ * tiled kernels have no such bound, k_dp_sweep behind the band kernels and on the recovery path has), so the rule is decided here,
+ * from the sizes alone and before the resize touches the device: the walk below is group_resize_dir's bookkeeping -- the frame the
+ * carver has now, and the frame after every flatten of a stepwise enlargement. */
+static int frame_refused(const LqrCarver *r, int w1, int want_transposed)
+{
+    const int same = (r->transposed == want_transposed);
+    int ws = same ? r->w_start : r->h_start, wc = same ? r->w : r->h, delta_max;
+    if (w1 == wc) return 0;                             /* nothing to carve in this direction */
+    if (ws > LQRHIP_MAX_FRAME_WIDTH || wc > LQRHIP_MAX_FRAME_WIDTH) return 1;
+    for (;;) {
+        int new_w;
+        delta_max = (int) ((r->enl_step - 1) * ws) - 1;
+        if (delta_max < 1) delta_max = 1;
+        new_w = MINI(w1, ws + delta_max);
+        if (new_w >= w1) return 0;
+        ws = new_w;                                     /* flattened: the next session starts from here */
+        if (ws > LQRHIP_MAX_FRAME_WIDTH) return 1;
+    }
+}
+
 static LqrRetVal group_resize(LqrCarver **rs, int n, int w1, int h1)
 {
     Group g;
@@ -816,6 +838,12 @@ static LqrRetVal group_resize(LqrCarver **rs, int n, int w1, int h1)
     if (w1 < 1 || h1 < 1) return LQR_ERROR;
     for (i = 0; i < n; i++)
         if (rs[i]->root || !rs[i]->progress) return LQR_ERROR;
+    for (i = 0; i < n; i++)
+        if (frame_refused(rs[i], w1, 0) || frame_refused(rs[i], h1, 1)) {
+            fprintf(stderr, "liblqr-hip: resize refused: a frame wider than %d px in the direction being carved is not supported\n",
+                    LQRHIP_MAX_FRAME_WIDTH);
+            return LQR_ERROR;
+        }
     LQR_CATCH(group_open(&g, rs, n));
     if (rs[0]->resize_order == LQR_RES_ORDER_HOR) {
         if ((ret = group_resize_dir(&g, w1, 0)) == LQR_OK) ret = group_resize_dir(&g, h1, 1);

@@ -38,6 +38,9 @@ extern "C" {
 #define LQRHIP_EFAULT (-4)   /* a kernel of the session gave up or a self-check failed: roll back, redo (lqrhip_session_rollback) */
 #define LQRHIP_MAX_DELTA 16
 #define LQRHIP_MAX_CHANNELS 64      /* channels per pixel at most (lqrx_set_max_channels) */
+/* The widest frame, in the direction being carved, that a session may start from: k_dp_sweep holds two rows of it in LDS (128 KB)
+ * at 16 px per thread.  The host side refuses wider ones before any device call (host/lqr_carver.c, frame_refused). */
+#define LQRHIP_MAX_FRAME_WIDTH 16384
 
 typedef struct LqrHipCarver LqrHipCarver;   /* device-resident planes of one carver */
 typedef struct LqrHipBatch LqrHipBatch;     /* n carvers advancing in lock-step     */
@@ -253,6 +256,34 @@ void lqrhip_set_band_levels(int slots);
  * wave; the full-width sweep took over), [1] synchronous (mispredicted or second-tile) loads, [2] tile-levels processed,
  * [3] slot-levels idle, [4] levels in which a slot had two tiles */
 int lqrhip_band_levels_stats(unsigned long long *out8, int reset);
+/* Test hook: the launch census -- which FORM of each stage the shim launched since the last reset, counted on the host at the
+ * launch sites (lqrhip_prof_get's names do not tell: "band_update" is four kernels, "dp_update" every sweep).  Copies the first
+ * min(n, LQRHIP_CENSUS_SLOTS) counters to `out`, clears all of them if `reset`, and returns LQRHIP_CENSUS_SLOTS.  Kernel launches
+ * are counted, one per launch whatever the size of the batch (k_vp_maps + k_vp_solve count as one backtrack). */
+enum {
+    LQRHIP_CENSUS_VP_PARALLEL = 0,      /* E7: k_vp_maps / k_vp_solve */
+    LQRHIP_CENSUS_VPATH1 = 1,           /*     k_vpath1<delta_x> */
+    LQRHIP_CENSUS_VPATH = 2,            /*     k_vpath */
+    LQRHIP_CENSUS_CARVE_E = 3,          /* E8: k_carve_e (carve + energy update) */
+    LQRHIP_CENSUS_CARVE = 4,            /*     k_carve */
+    LQRHIP_CENSUS_TILE_P_G3 = 5,        /* E5 / E9: k_dp_tile_p, geometry 3 (32-column tiles, plain) */
+    LQRHIP_CENSUS_TILE_P_G2 = 6,        /*     geometry 2 (64-column tiles, plain) */
+    LQRHIP_CENSUS_TILE_P_G4 = 7,        /*     4 px per lane (plain) */
+    LQRHIP_CENSUS_TILE_P_GENERAL = 8,   /*     the delta_x 2 .. 10 / rigidity-mask instantiations */
+    LQRHIP_CENSUS_DP_TILE = 9,          /* E5: k_dp_tile, one launch per 32 rows */
+    LQRHIP_CENSUS_BAND_LEVELS = 10,     /* E9: k_band_levels */
+    LQRHIP_CENSUS_BAND_TW = 11,         /*     k_band_update_tw */
+    LQRHIP_CENSUS_BAND_MW8 = 12,        /*     k_band_update_mw, 8 waves */
+    LQRHIP_CENSUS_BAND_MW16 = 13,       /*     k_band_update_mw, 16 waves */
+    LQRHIP_CENSUS_BAND_GENERIC = 14,    /*     k_band_update (one wave) */
+    LQRHIP_CENSUS_SWEEP = 15,           /* k_dp_sweep<P, ., T>: slot 15 + 2 * log2(P) + (T == 1024), P = 1, 2, 4, 8, 16 px per thread */
+    LQRHIP_CENSUS_SWEEP_FULL = 25,      /* ... of these, the full DPs (E5) */
+    LQRHIP_CENSUS_SWEEP_UPDATE = 26,    /* ... and the launches behind a band kernel (E9) */
+    LQRHIP_CENSUS_LDS_ATTR_SWEEP = 27,  /* k_dp_sweep launches with more than 64 KB of dynamic LDS (hipFuncSetAttribute first) */
+    LQRHIP_CENSUS_LDS_ATTR_COMMIT = 28, /* k_vs_commit launches with more than 64 KB of dynamic LDS */
+    LQRHIP_CENSUS_SLOTS = 32
+};
+int lqrhip_launch_census(unsigned long long *out, int n, int reset);
 
 #ifdef __cplusplus
 }
