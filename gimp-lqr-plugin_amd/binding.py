@@ -157,6 +157,44 @@ def bind_imagetype(api):
     return api
 
 
+# include/lqr_masks.h: liblqr's computed-mask calls (gdouble planes, single values, clears) and the engine's device forms and plane
+# read-outs, in a table of their own
+_Z = C.c_size_t
+MASK_SYMBOLS = {
+    "lqr_carver_bias_add_xy": (_I, [_P, _D, _I, _I]),
+    "lqr_carver_bias_add_area": (_I, [_P, _P, _I, _I, _I, _I, _I]),
+    "lqr_carver_bias_add": (_I, [_P, _P, _I]),
+    "lqr_carver_bias_add_rgb": (_I, [_P, _P, _I, _I]),
+    "lqr_carver_bias_clear": (None, [_P]),
+    "lqr_carver_rigmask_add_xy": (_I, [_P, _D, _I, _I]),
+    "lqr_carver_rigmask_add_area": (_I, [_P, _P, _I, _I, _I, _I]),
+    "lqr_carver_rigmask_add": (_I, [_P, _P]),
+    "lqr_carver_rigmask_add_rgb": (_I, [_P, _P, _I]),
+    "lqr_carver_rigmask_clear": (None, [_P]),
+    "lqrx_carver_bias_add_area_device": (_I, [_P, _P, _I, _I, _I, _I, _I, _I]),
+    "lqrx_carver_rigmask_add_area_device": (_I, [_P, _P, _I, _I, _I, _I, _I]),
+    "lqrx_carver_get_bias": (_I, [_P, _P]),
+    "lqrx_carver_get_rigmask": (_I, [_P, _P]),
+}
+
+
+def bind_masks(api):
+    """add MASK_SYMBOLS (and COLDEPTH_SYMBOLS) to a bound Api; a genuine liblqr-1 has none of the lqrx_ ones"""
+    bind_coldepth(api)
+    if not getattr(api, "has_masks", False):
+        for name, (res, args) in MASK_SYMBOLS.items():
+            if name.startswith("lqrx_") and not api.has_ext:
+                continue
+            fn = getattr(api.lib, api.prefix + name)      # AttributeError = missing export
+            fn.restype, fn.argtypes = res, args
+            setattr(api, name, fn)
+        if api.has_ext:
+            api.lqrhip_debug_mask_flushes = api.lib.lqrhip_debug_mask_flushes
+            api.lqrhip_debug_mask_flushes.restype, api.lqrhip_debug_mask_flushes.argtypes = C.c_ulonglong, []
+        api.has_masks = True
+    return api
+
+
 class Api:
     """Resolved function table of one library exporting the ABI."""
 
@@ -185,6 +223,11 @@ def engine_api():
 def engine_imagetype_api():
     """the engine with the colour-depth and image-type surfaces bound"""
     return bind_imagetype(engine_api())
+
+
+def engine_masks_api():
+    """the engine with the colour-depth and computed-mask surfaces bound"""
+    return bind_masks(engine_api())
 
 
 def engine_coldepth_api():
@@ -270,6 +313,10 @@ class Carver:
             ret = api.lqr_carver_init(self.p, delta_x, float(rigidity))
             assert ret == LQR_OK, ret
         return self
+
+    def init(self, delta_x=1, rigidity=0.0):
+        """lqr_carver_init on a carver made with init=False; returns the LqrRetVal"""
+        return self.api.lqr_carver_init(self.p, int(delta_x), float(rigidity))
 
     def attach_ext(self, array, depth=None):
         """an attached carver of any depth"""
@@ -388,6 +435,77 @@ class Carver:
             mask = mask[:, :, None]
         h, w, ch = mask.shape
         return self.api.lqr_carver_rigmask_add_rgb_area(self.p, mask.ctypes.data, ch, w, h, x_off, y_off)
+
+    # -- computed masks (include/lqr_masks.h); each returns the call's LqrRetVal.  Masks are h x w arrays of float64
+    @staticmethod
+    def _fmask(mask):
+        mask = np.ascontiguousarray(mask, dtype=np.float64)
+        assert mask.ndim == 2
+        return mask
+
+    def bias_add_f(self, mask, factor, x_off=None, y_off=None):
+        """lqr_carver_bias_add_area; without offsets lqr_carver_bias_add (the mask must then have the carver's size)"""
+        a, mask = bind_masks(self.api), self._fmask(mask)
+        if x_off is None:
+            return a.lqr_carver_bias_add(self.p, mask.ctypes.data, int(factor))
+        return a.lqr_carver_bias_add_area(self.p, mask.ctypes.data, int(factor), mask.shape[1], mask.shape[0], int(x_off), int(y_off))
+
+    def rigmask_add_f(self, mask, x_off=None, y_off=None):
+        a, mask = bind_masks(self.api), self._fmask(mask)
+        if x_off is None:
+            return a.lqr_carver_rigmask_add(self.p, mask.ctypes.data)
+        return a.lqr_carver_rigmask_add_area(self.p, mask.ctypes.data, mask.shape[1], mask.shape[0], int(x_off), int(y_off))
+
+    def bias_add_rgb(self, mask, factor):
+        """lqr_carver_bias_add_rgb: an 8-bit mask of the carver's size"""
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        return bind_masks(self.api).lqr_carver_bias_add_rgb(self.p, mask.ctypes.data, int(factor), 1 if mask.ndim == 2 else mask.shape[2])
+
+    def rigmask_add_rgb(self, mask):
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        return bind_masks(self.api).lqr_carver_rigmask_add_rgb(self.p, mask.ctypes.data, 1 if mask.ndim == 2 else mask.shape[2])
+
+    def bias_add_xy(self, entries):
+        """one lqr_carver_bias_add_xy per (x, y, value), in order; returns the list of return values"""
+        f = bind_masks(self.api).lqr_carver_bias_add_xy
+        return [f(self.p, float(v), int(x), int(y)) for x, y, v in entries]
+
+    def rigmask_add_xy(self, entries):
+        f = bind_masks(self.api).lqr_carver_rigmask_add_xy
+        return [f(self.p, float(v), int(x), int(y)) for x, y, v in entries]
+
+    def _add_device(self, fn, tensor, more, x_off, y_off):
+        """tensor: a contiguous h x w float32 / float64 torch tensor on the device"""
+        assert tensor.is_cuda and tensor.is_contiguous() and tensor.dim() == 2
+        depth = {torch.float32: LQR_COLDEPTH_32F, torch.float64: LQR_COLDEPTH_64F}[tensor.dtype]
+        torch.cuda.current_stream().synchronize()          # the engine reads the buffer on a stream of its own
+        return fn(self.p, tensor.data_ptr(), depth, *more, tensor.shape[1], tensor.shape[0], int(x_off), int(y_off))
+
+    def bias_add_device(self, tensor, factor, x_off=0, y_off=0):
+        return self._add_device(bind_masks(self.api).lqrx_carver_bias_add_area_device, tensor, [int(factor)], x_off, y_off)
+
+    def rigmask_add_device(self, tensor, x_off=0, y_off=0):
+        return self._add_device(bind_masks(self.api).lqrx_carver_rigmask_add_area_device, tensor, [], x_off, y_off)
+
+    def bias_clear(self):
+        bind_masks(self.api).lqr_carver_bias_clear(self.p)
+
+    def rigmask_clear(self):
+        bind_masks(self.api).lqr_carver_rigmask_clear(self.p)
+
+    def _get_plane(self, fn):
+        a = self.api
+        out = np.zeros((a.lqr_carver_get_height(self.p), a.lqr_carver_get_width(self.p)), np.float32)
+        ret = fn(self.p, out.ctypes.data)
+        assert ret == LQR_OK, ret
+        return out
+
+    def get_bias(self):
+        """the bias plane of a flat carver in image orientation (zeros if there is none)"""
+        return self._get_plane(bind_masks(self.api).lqrx_carver_get_bias)
+
+    def get_rigmask(self):
+        return self._get_plane(bind_masks(self.api).lqrx_carver_get_rigmask)
 
     def configure(self, nrg_func=LQR_EF_GRAD_XABS, res_order=LQR_RES_ORDER_HOR, switch_freq=2,
                   enl_step=1.5, dump_vmaps=False, progress=False):

@@ -10,6 +10,7 @@
 //   k_tiles.hip      E5/E9           k_dp_tile, k_dp_tile_p (an image spread over several compute units)
 //   k_levels.hip     E9              k_band_levels (the band on several compute units, tiles assigned level by level)
 //   k_oneoff.hip     E8(vs)/E11/E12/E14, auto-size  k_vs_commit, k_inflate, k_compact(_jobs), k_transpose, k_mask_line_max
+//   k_masks.hip      E2 (lqr_masks.h) k_mask_add_f (float / double masks, host or device), k_mask_scatter (queued _xy calls), k_plane_transpose
 //   lqr_shim.hip     the lqrhip_* C ABI of include/lqr_hip.h: allocation cache, batches, the per-seam launch sequence
 // lqr_kernels.h declares every kernel for the shim; each kernel file instantiates the templates the shim launches.
 //

@@ -63,3 +63,9 @@ __global__ __launch_bounds__(256) void k_inflate_deep(const InflateDevX *jobs, i
 __global__ void k_transpose_px(const InflateDev *jobs, int w, int h);
 __global__ __launch_bounds__(256) void k_compact_wide(const uint8_t *rgb, const int32_t *vs, uint8_t *nrgb, int w0, int w, int bytes, int level);
 __global__ __launch_bounds__(256) void k_compact_jobs_wide(const InflateDev *jobs, int w0, int w, int level);
+
+// k_masks.hip (computed masks, include/lqr_masks.h: T = float or double)
+template <class T> __global__ __launch_bounds__(256) void k_mask_add_f(float *plane, int w0, const T *mask, int mw, int x0, int y0, int x1, int y1, int nx, int ny,
+                                                                       int transposed, int is_rig, int bias_factor);
+__global__ __launch_bounds__(256) void k_mask_scatter(float *plane, const int *index, const double *value, size_t n, int is_rig);
+__global__ __launch_bounds__(256) void k_plane_transpose(const float *plane, float *out, int w0, int h0);

@@ -736,6 +736,131 @@ extern "C" int lqrhip_mask_add(LqrHipCarver *c, const unsigned char *mask, int c
     return rc;
 }
 
+// ---- computed masks (include/lqr_masks.h; kernels in k_masks.hip) ---------------------------------
+extern "C" int lqrhip_mask_plane_ensure(LqrHipCarver *c, int is_rigmask)
+{
+    float **plane = is_rigmask ? &c->rig0 : &c->bias0;
+    if (*plane) return 0;
+    int rc = batch_sync_of(c);
+    if (rc) return rc;
+    const size_t n = (size_t) c->w0 * c->h0;
+    if ((rc = dmalloc(plane, n))) return rc;
+    hipError_t e = dzero(*plane, n * sizeof(float));
+    if (e != hipSuccess) { dfree(*plane); HIPCK(e); }
+    if (c->batch) c->batch->dirty = true;
+    return 0;
+}
+
+extern "C" int lqrhip_mask_add_f(LqrHipCarver *c, const void *mask, int depth, int on_device, int width, int height, int x_off, int y_off,
+                                 int transposed, int is_rigmask, int bias_factor)
+{
+    if ((depth != 2 && depth != 3) || !mask || width < 1 || height < 1) { g_err = "mask: float or double values, at least 1 x 1"; return LQRHIP_EARG; }
+    int rc = batch_sync_of(c);
+    if (rc) return rc;
+    if ((rc = lqrhip_mask_plane_ensure(c, is_rigmask))) return rc;
+    float *plane = is_rigmask ? c->rig0 : c->bias0;
+    // the clipping of lqrhip_mask_add
+    const int wt = transposed ? c->h0 : c->w0, ht = transposed ? c->w0 : c->h0;
+    const int x0 = x_off < 0 ? x_off : 0, y0 = y_off < 0 ? y_off : 0;
+    const int x1 = x_off > 0 ? x_off : 0, y1 = y_off > 0 ? y_off : 0;
+    const long long xe = (long long) width + x_off, ye = (long long) height + y_off;
+    const int x2 = wt < xe ? wt : (int) xe, y2 = ht < ye ? ht : (int) ye;
+    const int nx = x2 - x1, ny = y2 - y1;
+    if (nx <= 0 || ny <= 0) return 0;
+    const size_t mbytes = (size_t) width * height * (depth == 2 ? sizeof(float) : sizeof(double));
+    uint8_t *staged = nullptr;
+    if (!on_device && (rc = dmalloc(&staged, mbytes))) return rc;
+    auto run = [&]() -> int {
+        if (!on_device) {
+            int rcu = h2d_staged(staged, mask, mbytes);
+            if (rcu) return rcu;
+        }
+        const void *src = on_device ? mask : (const void *) staged;
+        dim3 grid((nx + 255) / 256, ny);
+        if (depth == 2)
+            hipLaunchKernelGGL(k_mask_add_f<float>, grid, dim3(256), 0, g_stream0, plane, c->w0, (const float *) src, width, x0, y0, x1, y1, nx, ny,
+                               transposed, is_rigmask, bias_factor);
+        else
+            hipLaunchKernelGGL(k_mask_add_f<double>, grid, dim3(256), 0, g_stream0, plane, c->w0, (const double *) src, width, x0, y0, x1, y1, nx, ny,
+                               transposed, is_rigmask, bias_factor);
+        HIPCK(hipGetLastError());
+        HIPCK(hipStreamSynchronize(g_stream0));        // the caller may reuse its buffer
+        return 0;
+    };
+    rc = run();
+    if (rc) (void) hipStreamSynchronize(g_stream0);
+    dfree(staged);
+    return rc;
+}
+
+static unsigned long long g_mask_flushes = 0;
+extern "C" unsigned long long lqrhip_debug_mask_flushes(void) { return g_mask_flushes; }
+
+extern "C" int lqrhip_mask_scatter(LqrHipCarver *c, int is_rigmask, const int *index, const double *value, const size_t *start, int buckets)
+{
+    if (buckets < 1 || start[buckets] == 0) return 0;
+    int rc = batch_sync_of(c);
+    if (rc) return rc;
+    if ((rc = lqrhip_mask_plane_ensure(c, is_rigmask))) return rc;
+    float *plane = is_rigmask ? c->rig0 : c->bias0;
+    const size_t n = start[buckets];
+    int *dindex = nullptr;
+    double *dvalue = nullptr;
+    if ((rc = dmalloc(&dindex, n)) || (rc = dmalloc(&dvalue, n))) { dfree(dindex); return rc; }
+    auto run = [&]() -> int {
+        int rcu = h2d_staged(dindex, index, n * sizeof(int));
+        if (!rcu) rcu = h2d_staged(dvalue, value, n * sizeof(double));
+        if (rcu) return rcu;
+        // bucket after bucket on one stream: a pixel that is hit k times receives its values in call order
+        for (int b = 0; b < buckets; b++) {
+            const size_t nb = start[b + 1] - start[b];
+            if (!nb) continue;
+            hipLaunchKernelGGL(k_mask_scatter, dim3((unsigned) ((nb + 255) / 256)), dim3(256), 0, g_stream0, plane, dindex + start[b], dvalue + start[b],
+                               nb, is_rigmask);
+            HIPCK(hipGetLastError());
+            g_mask_flushes++;
+        }
+        HIPCK(hipStreamSynchronize(g_stream0));
+        return 0;
+    };
+    rc = run();
+    if (rc) (void) hipStreamSynchronize(g_stream0);
+    dfree(dindex); dfree(dvalue);
+    return rc;
+}
+
+extern "C" int lqrhip_mask_clear(LqrHipCarver *c, int is_rigmask)
+{
+    float **plane = is_rigmask ? &c->rig0 : &c->bias0;
+    if (!*plane) return 0;
+    int rc = batch_sync_of(c);
+    if (rc) return rc;
+    HIPCK(hipStreamSynchronize(g_stream0));
+    dfree(*plane);
+    // the working copy goes at the next lqrhip_wk_init (ensure_working lays the planes out for the masks the carver has)
+    if (c->batch) c->batch->dirty = true;
+    return 0;
+}
+
+extern "C" int lqrhip_read_mask_plane(LqrHipCarver *c, int is_rigmask, int transposed, float *out)
+{
+    int rc = batch_sync_of(c);
+    if (rc) return rc;
+    const size_t n = (size_t) c->w0 * c->h0;
+    const float *plane = is_rigmask ? c->rig0 : c->bias0;
+    if (!plane) { memset(out, 0, n * sizeof(float)); return 0; }
+    if (!transposed) return d2h_staged(out, plane, n * sizeof(float));
+    float *t = nullptr;
+    if ((rc = dmalloc(&t, n))) return rc;
+    hipLaunchKernelGGL(k_plane_transpose, dim3((c->w0 + 15) / 16, (c->h0 + 15) / 16), dim3(256), 0, g_stream0, plane, t, c->w0, c->h0);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) rc = d2h_staged(out, t, n * sizeof(float));
+    else { g_err = std::string("k_plane_transpose: ") + hipGetErrorString(e); rc = LQRHIP_EHIP; }
+    (void) hipStreamSynchronize(g_stream0);
+    dfree(t);
+    return rc;
+}
+
 // ---- batch -----------------------------------------------------------------
 // A lock-step group can be split over several HIP streams (sub-batches) that advance seam by seam side by side: a seam
 // round is a latency-bound chain (backtrack, energy update, band update: ~0.7 ms at 4K whatever the batch size, on a

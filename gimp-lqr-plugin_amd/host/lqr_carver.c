@@ -23,7 +23,9 @@
 #include "../../include/lqr.h"
 #include "../../include/lqr_coldepth.h"
 #include "../../include/lqr_imagetype.h"
+#include "../../include/lqr_masks.h"
 #include "../../include/lqr_hip.h"
+#include "lqr_mask_queue.h"
 
 #define MAXI(a, b) ((a) > (b) ? (a) : (b))
 #define MINI(a, b) ((a) < (b) ? (a) : (b))
@@ -71,6 +73,7 @@ struct _LqrCarver {
     float rigidity;
     float rigidity_map[2 * LQRHIP_MAX_DELTA + 1];      /* [dx + delta_x] */
     int has_bias, has_rigmask;
+    LqrMaskQueue mq[2];         /* lqr_carver_bias_add_xy / lqr_carver_rigmask_add_xy calls not yet on the device ([0] bias, [1] rigidity mask) */
     int nrg_func, nrg_radius;
     int leftright, lr_switch_frequency;
     float enl_step;
@@ -229,6 +232,8 @@ static LqrCarver *carver_new(void *buffer, int width, int height, int channels, 
     r->resize_order = LQR_RES_ORDER_HOR;
     r->progress = lqr_progress_new();
     if (!r->progress) { lqrhip_carver_destroy(r->dev); free(r); return NULL; }
+    lqr_maskq_init(&r->mq[0], 0);
+    lqr_maskq_init(&r->mq[1], 0);
     return r;
 }
 
@@ -314,6 +319,7 @@ static void carver_free_host(LqrCarver *r)
     free(r->ro_image); free(r->ro_buffer);
     if (!r->preserve_input) free(r->in_buffer);
     free(r->dbg_en); free(r->dbg_m); free(r->dbg_least);
+    lqr_maskq_free(&r->mq[0]); lqr_maskq_free(&r->mq[1]);        /* what was still queued is dropped */
     free(r);
 }
 
@@ -486,6 +492,33 @@ static void dp_params(const LqrCarver *r, LqrHipDpParams *p)
     p->w_start = r->w_start;
 }
 
+/* ======================= queued _xy mask calls (lqr_masks.h) ============= */
+/* One plane's queue onto the device, in call order (lqr_mask_queue.h).  LQR_NOMEM (host or device) leaves the queue as it was; any
+ * other failure drops it. */
+static LqrRetVal mask_queue_flush_one(LqrCarver *r, int is_rig)
+{
+    LqrMaskQueue *q = &r->mq[is_rig];
+    int *index, rc;
+    double *value;
+    size_t *start;
+    if (!q->n) return LQR_OK;
+    index = (int *) malloc(q->n * sizeof *index);
+    value = (double *) malloc(q->n * sizeof *value);
+    start = (size_t *) malloc(((size_t) q->buckets + 1) * sizeof *start);
+    if (!index || !value || !start) { free(index); free(value); free(start); return LQR_NOMEM; }
+    lqr_maskq_pack(q, index, value, start);
+    rc = lqrhip_mask_scatter(r->dev, is_rig, index, value, start, (int) q->buckets);
+    free(index); free(value); free(start);
+    if (rc != LQRHIP_ENOMEM) lqr_maskq_reset(q);
+    return hip_ret(rc);
+}
+/* before anything that reads or writes the mask planes or changes the layout */
+static LqrRetVal mask_queue_flush(LqrCarver *r)
+{
+    LQR_CATCH(mask_queue_flush_one(r, 0));
+    return mask_queue_flush_one(r, 1);
+}
+
 /* ======================= flatten / transpose (E11) ======================= */
 static LqrRetVal group_flatten(Group *g)
 {
@@ -533,6 +566,7 @@ LqrRetVal lqr_carver_flatten(LqrCarver *r)
     Group g;
     LqrRetVal ret;
     if (r->root) return LQR_ERROR;
+    LQR_CATCH(mask_queue_flush(r));
     LQR_CATCH(group_open(&g, &r, 1));
     ret = group_flatten(&g);
     group_close(&g);
@@ -552,6 +586,7 @@ LqrRetVal lqr_carver_bias_add_rgb_area(LqrCarver *r, guchar *rgb, gint bias_fact
 {
     LQR_CATCH(mask_prepare(r));
     if (bias_factor == 0) return LQR_OK;
+    LQR_CATCH(mask_queue_flush(r));
     HIP_CATCH(lqrhip_mask_add(r->dev, rgb, channels, width, height, x_off, y_off, r->transposed, 0, bias_factor));
     r->has_bias = 1;
     r->wk_valid = 0;
@@ -562,11 +597,126 @@ LqrRetVal lqr_carver_rigmask_add_rgb_area(LqrCarver *r, guchar *rgb, gint channe
                                           gint y_off)
 {
     LQR_CATCH(mask_prepare(r));
+    LQR_CATCH(mask_queue_flush(r));
     HIP_CATCH(lqrhip_mask_add(r->dev, rgb, channels, width, height, x_off, y_off, r->transposed, 1, 0));
     r->has_rigmask = 1;
     r->wk_valid = 0;
     return LQR_OK;
 }
+
+/* ---- computed masks (lqr_masks.h): gdouble planes from host or device memory, single values, clears ---- */
+/* liblqr takes a bias before lqr_carver_init (the plane is part of the base layout, which exists from lqr_carver_new on); a rigidity
+ * mask needs the initialised carver, as there (mask_prepare) */
+static LqrRetVal bias_prepare(LqrCarver *r)
+{
+    if (r->root) return LQR_ERROR;
+    if (r->w != r->w0 || r->w_start != r->w0 || r->h != r->h0 || r->h_start != r->h0) LQR_CATCH(lqr_carver_flatten(r));
+    return LQR_OK;
+}
+static LqrRetVal mask_add_f(LqrCarver *r, const void *buffer, int depth, int on_device, int is_rig, int bias_factor, int width, int height,
+                            int x_off, int y_off)
+{
+    if (!is_rig && bias_factor == 0) return LQR_OK;     /* liblqr: before anything else */
+    LQR_CATCH(is_rig ? mask_prepare(r) : bias_prepare(r));
+    LQR_CATCH(mask_queue_flush(r));
+    HIP_CATCH(lqrhip_mask_add_f(r->dev, buffer, depth, on_device, width, height, x_off, y_off, r->transposed, is_rig, bias_factor));
+    if (is_rig) r->has_rigmask = 1; else r->has_bias = 1;
+    r->wk_valid = 0;
+    return LQR_OK;
+}
+LqrRetVal lqr_carver_bias_add_area(LqrCarver *r, gdouble *buffer, gint bias_factor, gint width, gint height, gint x_off, gint y_off)
+{
+    return mask_add_f(r, buffer, LQR_COLDEPTH_64F, 0, 0, bias_factor, width, height, x_off, y_off);
+}
+LqrRetVal lqr_carver_bias_add(LqrCarver *r, gdouble *buffer, gint bias_factor)
+{
+    return lqr_carver_bias_add_area(r, buffer, bias_factor, lqr_carver_get_width(r), lqr_carver_get_height(r), 0, 0);
+}
+LqrRetVal lqr_carver_bias_add_rgb(LqrCarver *r, guchar *rgb, gint bias_factor, gint channels)
+{
+    if (bias_factor == 0) return LQR_OK;
+    LQR_CATCH(bias_prepare(r));
+    LQR_CATCH(mask_queue_flush(r));
+    HIP_CATCH(lqrhip_mask_add(r->dev, rgb, channels, lqr_carver_get_width(r), lqr_carver_get_height(r), 0, 0, r->transposed, 0, bias_factor));
+    r->has_bias = 1;
+    r->wk_valid = 0;
+    return LQR_OK;
+}
+LqrRetVal lqr_carver_rigmask_add_area(LqrCarver *r, gdouble *buffer, gint width, gint height, gint x_off, gint y_off)
+{
+    return mask_add_f(r, buffer, LQR_COLDEPTH_64F, 0, 1, 0, width, height, x_off, y_off);
+}
+LqrRetVal lqr_carver_rigmask_add(LqrCarver *r, gdouble *buffer)
+{
+    return lqr_carver_rigmask_add_area(r, buffer, lqr_carver_get_width(r), lqr_carver_get_height(r), 0, 0);
+}
+LqrRetVal lqr_carver_rigmask_add_rgb(LqrCarver *r, guchar *rgb, gint channels)
+{
+    return lqr_carver_rigmask_add_rgb_area(r, rgb, channels, lqr_carver_get_width(r), lqr_carver_get_height(r), 0, 0);
+}
+LqrRetVal lqrx_carver_bias_add_area_device(LqrCarver *r, const void *device_buffer, LqrColDepth depth, gint bias_factor, gint width, gint height,
+                                           gint x_off, gint y_off)
+{
+    if (depth != LQR_COLDEPTH_32F && depth != LQR_COLDEPTH_64F) return LQR_ERROR;
+    return mask_add_f(r, device_buffer, (int) depth, 1, 0, bias_factor, width, height, x_off, y_off);
+}
+LqrRetVal lqrx_carver_rigmask_add_area_device(LqrCarver *r, const void *device_buffer, LqrColDepth depth, gint width, gint height, gint x_off,
+                                              gint y_off)
+{
+    if (depth != LQR_COLDEPTH_32F && depth != LQR_COLDEPTH_64F) return LQR_ERROR;
+    return mask_add_f(r, device_buffer, (int) depth, 1, 1, 0, width, height, x_off, y_off);
+}
+
+/* One value: queued, not launched (a caller makes one call per pixel of its mask).  Only the first call of a run touches the device:
+ * it flattens the carver and makes sure the plane exists.  The value goes to the device as the caller gave it; the conversion to
+ * float and the halving happen in k_mask_scatter. */
+static LqrRetVal mask_add_xy(LqrCarver *r, int is_rig, double v, int x, int y)
+{
+    LqrMaskQueue *q = &r->mq[is_rig];
+    int rc, index;
+    if (!q->n) {
+        LQR_CATCH(is_rig ? mask_prepare(r) : bias_prepare(r));
+        if (x < 0 || y < 0 || x >= lqr_carver_get_width(r) || y >= lqr_carver_get_height(r)) return LQR_ERROR;
+        HIP_CATCH(lqrhip_mask_plane_ensure(r->dev, is_rig));
+        if (is_rig) r->has_rigmask = 1; else r->has_bias = 1;
+        r->wk_valid = 0;
+    } else if (x < 0 || y < 0 || x >= lqr_carver_get_width(r) || y >= lqr_carver_get_height(r))
+        return LQR_ERROR;
+    index = r->transposed ? x * r->w0 + y : y * r->w0 + x;
+    rc = lqr_maskq_append(q, (size_t) r->w0 * r->h0, index, v);
+    if (rc == LQR_MASKQ_FULL) {         /* the bound: an early flush */
+        LQR_CATCH(mask_queue_flush_one(r, is_rig));
+        rc = lqr_maskq_append(q, (size_t) r->w0 * r->h0, index, v);
+    }
+    return rc == LQR_MASKQ_OK ? LQR_OK : rc == LQR_MASKQ_NOMEM ? LQR_NOMEM : LQR_ERROR;
+}
+LqrRetVal lqr_carver_bias_add_xy(LqrCarver *r, gdouble bias, gint x, gint y)
+{
+    if (bias == 0) return LQR_OK;
+    return mask_add_xy(r, 0, bias, x, y);
+}
+LqrRetVal lqr_carver_rigmask_add_xy(LqrCarver *r, gdouble rigidity, gint x, gint y) { return mask_add_xy(r, 1, rigidity, x, y); }
+
+/* the plane goes, with what was queued for it: same_config groups the carver with unmasked ones again */
+static void mask_clear(LqrCarver *r, int is_rig)
+{
+    lqr_maskq_reset(&r->mq[is_rig]);
+    (void) hip_ret(lqrhip_mask_clear(r->dev, is_rig));
+    if (is_rig) r->has_rigmask = 0; else r->has_bias = 0;
+    r->wk_valid = 0;
+}
+void lqr_carver_bias_clear(LqrCarver *r) { mask_clear(r, 0); }
+void lqr_carver_rigmask_clear(LqrCarver *r) { mask_clear(r, 1); }
+
+static LqrRetVal mask_read(LqrCarver *r, int is_rig, gfloat *out)
+{
+    LQR_CATCH(mask_queue_flush(r));
+    if (r->w != r->w0 || r->w_start != r->w0 || r->h != r->h0 || r->h_start != r->h0) return LQR_ERROR;     /* flat carvers only */
+    HIP_CATCH(lqrhip_read_mask_plane(r->dev, is_rig, r->transposed, out));
+    return LQR_OK;
+}
+LqrRetVal lqrx_carver_get_bias(LqrCarver *r, gfloat *out) { return mask_read(r, 0, out); }
+LqrRetVal lqrx_carver_get_rigmask(LqrCarver *r, gfloat *out) { return mask_read(r, 1, out); }
 
 /* ======================= per-seam loop (E10) ============================= */
 static LqrRetVal take_debug_snapshot(LqrCarver *r)
@@ -838,6 +988,7 @@ static LqrRetVal group_resize(LqrCarver **rs, int n, int w1, int h1)
     if (w1 < 1 || h1 < 1) return LQR_ERROR;
     for (i = 0; i < n; i++)
         if (rs[i]->root || !rs[i]->progress) return LQR_ERROR;
+    for (i = 0; i < n; i++) LQR_CATCH(mask_queue_flush(rs[i]));
     for (i = 0; i < n; i++)
         if (frame_refused(rs[i], w1, 0) || frame_refused(rs[i], h1, 1)) {
             fprintf(stderr, "liblqr-hip: resize refused: a frame wider than %d px in the direction being carved is not supported\n",
@@ -1008,6 +1159,7 @@ LqrRetVal lqrx_carver_reload_device_batch(LqrCarver **rs, gint n, void *const *d
     for (i = 0; i < n; i++) {
         LqrCarver *r = rs[i];
         LqrVMapList *v, *vn;
+        lqr_maskq_reset(&r->mq[0]); lqr_maskq_reset(&r->mq[1]);        /* masks are dropped, queued ones too */
         HIP_CATCH(lqrhip_carver_reset(r->dev, device_rgb[i], r->img_w, r->img_h));
         for (v = r->flushed_vs; v; v = vn) { vn = v->next; lqr_vmap_destroy(v->current); free(v); }
         r->flushed_vs = NULL;
@@ -1053,6 +1205,7 @@ LqrRetVal lqrx_carver_get_energy(LqrCarver *r, gfloat *buffer)
     LqrHipDpParams p;
     LqrRetVal ret = LQR_OK;
     if (r->root) return LQR_ERROR;
+    LQR_CATCH(mask_queue_flush(r));
     LQR_CATCH(group_open(&g, &r, 1));
     if (r->w != r->w_start - r->max_level + 1) ret = group_flatten(&g);
     if (ret == LQR_OK && !r->wk_valid) {

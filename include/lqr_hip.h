@@ -27,6 +27,8 @@
 #ifndef LQR_HIP_H
 #define LQR_HIP_H
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -95,6 +97,23 @@ int lqrhip_carver_activate(LqrHipCarver *c);
  * says whether the carver frame is the transpose of image orientation. */
 int lqrhip_mask_add(LqrHipCarver *c, const unsigned char *mask, int channels, int width, int height,
                     int x_off, int y_off, int transposed, int is_rigmask, int bias_factor);
+
+/* E2 for computed masks (lqr_masks.h): the _area forms on width x height values of `depth` (LqrColDepth 2: float, 3: double), clipped
+ * as lqrhip_mask_add clips.  on_device = 0: a host buffer, staged as the rgb form's; 1: `mask` is device memory and is read where it
+ * lies.  Either way the call returns after the kernel has run. */
+int lqrhip_mask_add_f(LqrHipCarver *c, const void *mask, int depth, int on_device, int width, int height, int x_off, int y_off,
+                      int transposed, int is_rigmask, int bias_factor);
+/* make sure the bias (is_rigmask 0) or rigidity-mask plane exists (zero-filled when new) */
+int lqrhip_mask_plane_ensure(LqrHipCarver *c, int is_rigmask);
+/* a packed run of queued _xy calls (host/lqr_mask_queue.h): n entries in `buckets` buckets, bucket b being entries start[b] ..
+ * start[b + 1]; one k_mask_scatter launch per bucket, in order */
+int lqrhip_mask_scatter(LqrHipCarver *c, int is_rigmask, const int *index, const double *value, const size_t *start, int buckets);
+/* lqr_carver_bias_clear / lqr_carver_rigmask_clear: free the plane (base layout and working copy) */
+int lqrhip_mask_clear(LqrHipCarver *c, int is_rigmask);
+/* test hook behind lqrx_carver_get_bias / _get_rigmask: the plane of a flat carver in image orientation (zeros if there is none) */
+int lqrhip_read_mask_plane(LqrHipCarver *c, int is_rigmask, int transposed, float *out);
+/* Test hook: k_mask_scatter launches since the library was loaded (how the _xy calls were batched) */
+unsigned long long lqrhip_debug_mask_flushes(void);
 
 /* -- batch ------------------------------------------------------------------ */
 /* into how many device batches (HIP streams) the host splits a lock-step group of n carvers.  Automatic (set 0): 4 for

@@ -362,6 +362,9 @@ class RefCarver:
     def free_input(self):
         self.r.free(self.buf)
 
+    def init(self, delta_x=1, rigidity=0.0):
+        return self.r.call("lqr_carver_init", self.p, int(delta_x), ("f", float(rigidity)))
+
     def attach_ext(self, array, depth=None):
         aux = RefCarver.from_ext(self.api, array, depth, init=False)
         ret = self.r.call("lqr_carver_attach", self.p, aux.p)
@@ -479,6 +482,86 @@ class RefCarver:
         ret = self.r.call("lqr_carver_rigmask_add_rgb_area", self.p, p, ch, w, h, x_off, y_off)
         self.r.free(p)
         return ret
+
+    # -- computed masks (include/lqr_masks.h), as binding.Carver's
+    def _fmask(self, mask):
+        mask = np.ascontiguousarray(mask, dtype=np.float64)
+        assert mask.ndim == 2
+        p = self.r.alloc(max(mask.nbytes, 1))
+        self.r.write(p, mask.tobytes())
+        return p, mask.shape
+
+    def bias_add_f(self, mask, factor, x_off=None, y_off=None):
+        p, (h, w) = self._fmask(mask)
+        if x_off is None:
+            ret = self.r.call("lqr_carver_bias_add", self.p, p, int(factor))
+        else:
+            ret = self.r.call("lqr_carver_bias_add_area", self.p, p, int(factor), w, h, int(x_off), int(y_off))
+        self.r.free(p)
+        return ret
+
+    def rigmask_add_f(self, mask, x_off=None, y_off=None):
+        p, (h, w) = self._fmask(mask)
+        if x_off is None:
+            ret = self.r.call("lqr_carver_rigmask_add", self.p, p)
+        else:
+            ret = self.r.call("lqr_carver_rigmask_add_area", self.p, p, w, h, int(x_off), int(y_off))
+        self.r.free(p)
+        return ret
+
+    def bias_add_rgb(self, mask, factor):
+        p, (h, w, ch) = self._mask(mask)
+        ret = self.r.call("lqr_carver_bias_add_rgb", self.p, p, int(factor), ch)
+        self.r.free(p)
+        return ret
+
+    def rigmask_add_rgb(self, mask):
+        p, (h, w, ch) = self._mask(mask)
+        ret = self.r.call("lqr_carver_rigmask_add_rgb", self.p, p, ch)
+        self.r.free(p)
+        return ret
+
+    def bias_add_xy(self, entries):
+        return [self.r.call("lqr_carver_bias_add_xy", self.p, ("d", float(v)), int(x), int(y)) for x, y, v in entries]
+
+    def rigmask_add_xy(self, entries):
+        return [self.r.call("lqr_carver_rigmask_add_xy", self.p, ("d", float(v)), int(x), int(y)) for x, y, v in entries]
+
+    def bias_clear(self):
+        self.r.call("lqr_carver_bias_clear", self.p)
+
+    def rigmask_clear(self):
+        self.r.call("lqr_carver_rigmask_clear", self.p)
+
+    def _get_plane(self, offset):
+        """a float plane of the genuine struct (bias 0x70, rigidity_mask 0x5c; oracle/REF_CHECK.md 3) of a flat carver, indexed by
+        position in the carver's frame; handed back in image orientation, zeros if the carver has none"""
+        r = self.r
+        w, h, w0, h0 = struct.unpack("<4i", r.read(self.p + 8, 16))
+        assert (w, h) == (w0, h0), "not flat"
+        ptr = struct.unpack("<I", r.read(self.p + offset, 4))[0]
+        plane = np.frombuffer(r.read(ptr, 4 * w0 * h0), np.float32).reshape(h0, w0).copy() if ptr else np.zeros((h0, w0), np.float32)
+        return np.ascontiguousarray(plane.T) if r.call("lqr_carver_get_orientation", self.p) else plane
+
+    def get_bias(self):
+        return self._get_plane(0x70)
+
+    def get_rigmask(self):
+        return self._get_plane(0x5c)
+
+    def energy(self):
+        """the energy plane of a flat carver, as binding.Carver.energy gives it (the carver's frame): lqr_carver_build_emap, then `en`
+        (0x6c) read through the pixel ids of `_raw` (0x7c)"""
+        r = self.r
+        w_start, h_start, w, h, w0, h0, level, max_level = struct.unpack("<8i", r.read(self.p, 32))
+        assert (w, h, max_level) == (w0, h0, 1) and w_start == w0, "not flat"
+        r.call("lqr_carver_set_width", self.p, w_start)
+        assert r.call("lqr_carver_build_emap", self.p) == LQR_OK
+        en_p, = struct.unpack("<I", r.read(self.p + 0x6c, 4))
+        raw_p, = struct.unpack("<I", r.read(self.p + 0x7c, 4))
+        ids = np.frombuffer(r.read(raw_p, 4 * w0 * h0), np.int32)
+        en = np.frombuffer(r.read(en_p, 4 * w0 * h0), np.float32)
+        return en[ids].reshape(h0, w0).copy()
 
     def configure(self, nrg_func=2, res_order=0, switch_freq=2, enl_step=1.5, dump_vmaps=False, progress=False):
         r = self.r
