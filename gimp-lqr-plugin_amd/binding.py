@@ -195,6 +195,32 @@ def bind_masks(api):
     return api
 
 
+# include/lqr_energy.h: liblqr's energy read-outs (as they are, normalised, as a picture) and the engine's forms into device memory
+ENERGY_SYMBOLS = {
+    "lqr_carver_get_energy": (_I, [_P, _P, _I]),
+    "lqr_carver_get_true_energy": (_I, [_P, _P, _I]),
+    "lqr_carver_get_energy_image": (_I, [_P, _P, _I, _I, _I]),
+    "lqrx_carver_get_energy_device": (_I, [_P, _P, _I, _I]),
+    "lqrx_carver_get_energy_image_device": (_I, [_P, _P, _I, _I, _I]),
+}
+IMAGE_TYPE_CHANNELS = {LQR_RGB_IMAGE: 3, LQR_RGBA_IMAGE: 4, LQR_GREY_IMAGE: 1, LQR_GREYA_IMAGE: 2, LQR_CMY_IMAGE: 3, LQR_CMYK_IMAGE: 4,
+                       LQR_CMYKA_IMAGE: 5}
+
+
+def bind_energy(api):
+    """add ENERGY_SYMBOLS (and COLDEPTH_SYMBOLS) to a bound Api; a genuine liblqr-1 has none of the lqrx_ ones"""
+    bind_coldepth(api)
+    if not getattr(api, "has_energy", False):
+        for name, (res, args) in ENERGY_SYMBOLS.items():
+            if name.startswith("lqrx_") and not api.has_ext:
+                continue
+            fn = getattr(api.lib, api.prefix + name)      # AttributeError = missing export
+            fn.restype, fn.argtypes = res, args
+            setattr(api, name, fn)
+        api.has_energy = True
+    return api
+
+
 class Api:
     """Resolved function table of one library exporting the ABI."""
 
@@ -228,6 +254,11 @@ def engine_imagetype_api():
 def engine_masks_api():
     """the engine with the colour-depth and computed-mask surfaces bound"""
     return bind_masks(engine_api())
+
+
+def engine_energy_api():
+    """the engine with the colour-depth and energy read-out surfaces bound"""
+    return bind_energy(engine_api())
 
 
 def engine_coldepth_api():
@@ -506,6 +537,55 @@ class Carver:
 
     def get_rigmask(self):
         return self._get_plane(bind_masks(self.api).lqrx_carver_get_rigmask)
+
+    # -- the energy read-outs (include/lqr_energy.h)
+    def energy_call(self, form, orientation, depth=LQR_COLDEPTH_32F, image_type=LQR_GREY_IMAGE, nbytes=0, guard=64, null=False):
+        """one read-out (form 0 lqr_carver_get_true_energy, 1 lqr_carver_get_energy, 2 lqr_carver_get_energy_image) into a buffer of
+        nbytes + guard bytes of 0xA5 (null: a NULL buffer): (LqrRetVal, the bytes afterwards)"""
+        a = bind_energy(self.api)
+        buf = np.full(nbytes + guard, 0xa5, np.uint8)
+        ptr = None if null else buf.ctypes.data
+        if form == 2:
+            ret = a.lqr_carver_get_energy_image(self.p, ptr, int(orientation), int(depth), int(image_type))
+        else:
+            ret = (a.lqr_carver_get_energy if form else a.lqr_carver_get_true_energy)(self.p, ptr, int(orientation))
+        return ret, buf
+
+    def _image_size(self):
+        return self.api.lqr_carver_get_height(self.p), self.api.lqr_carver_get_width(self.p)
+
+    def get_energy(self, orientation, true=False):
+        """lqr_carver_get_energy (true=True: lqr_carver_get_true_energy) as seams of `orientation` see it: height x width float32 in
+        image orientation.  The carver is left in that orientation"""
+        h, w = self._image_size()
+        ret, buf = self.energy_call(0 if true else 1, orientation, nbytes=4 * w * h, guard=0)
+        assert ret == LQR_OK, ret
+        return buf.view(np.float32).reshape(h, w)
+
+    def get_energy_image(self, orientation, depth, image_type):
+        """lqr_carver_get_energy_image: height x width x channels of the depth's dtype"""
+        h, w = self._image_size()
+        dt, ch = np.dtype(COLDEPTH_DTYPES[depth]), IMAGE_TYPE_CHANNELS[image_type]
+        ret, buf = self.energy_call(2, orientation, depth, image_type, nbytes=w * h * ch * dt.itemsize, guard=0)
+        assert ret == LQR_OK, ret
+        return buf.view(dt).reshape(h, w, ch)
+
+    def get_energy_device(self, tensor, orientation, true=False):
+        """the float forms into a contiguous float32 torch tensor of height x width elements on the device; returns the LqrRetVal"""
+        h, w = self._image_size()
+        assert tensor.is_cuda and tensor.is_contiguous() and tensor.dtype == torch.float32 and tensor.numel() == h * w
+        torch.cuda.current_stream().synchronize()          # the engine writes the buffer on a stream of its own
+        return bind_energy(self.api).lqrx_carver_get_energy_device(self.p, tensor.data_ptr(), int(orientation), 0 if true else 1)
+
+    def get_energy_image_device(self, tensor, orientation, depth, image_type):
+        """the picture into a contiguous torch tensor of height x width x channels elements of the depth's dtype on the device"""
+        h, w = self._image_size()
+        dt = {LQR_COLDEPTH_8I: torch.uint8, LQR_COLDEPTH_16I: (torch.uint16, torch.int16), LQR_COLDEPTH_32F: torch.float32,
+              LQR_COLDEPTH_64F: torch.float64}[depth]
+        assert tensor.is_cuda and tensor.is_contiguous() and tensor.numel() == h * w * IMAGE_TYPE_CHANNELS[image_type]
+        assert tensor.dtype in dt if isinstance(dt, tuple) else tensor.dtype == dt
+        torch.cuda.current_stream().synchronize()
+        return bind_energy(self.api).lqrx_carver_get_energy_image_device(self.p, tensor.data_ptr(), int(orientation), int(depth), int(image_type))
 
     def configure(self, nrg_func=LQR_EF_GRAD_XABS, res_order=LQR_RES_ORDER_HOR, switch_freq=2,
                   enl_step=1.5, dump_vmaps=False, progress=False):

@@ -11,6 +11,7 @@
 //   k_levels.hip     E9              k_band_levels (the band on several compute units, tiles assigned level by level)
 //   k_oneoff.hip     E8(vs)/E11/E12/E14, auto-size  k_vs_commit, k_inflate, k_compact(_jobs), k_transpose, k_mask_line_max
 //   k_masks.hip      E2 (lqr_masks.h) k_mask_add_f (float / double masks, host or device), k_mask_scatter (queued _xy calls), k_plane_transpose
+//   k_energy_out.hip energy read-outs (lqr_energy.h) k_energy_range (squash, min / max per workgroup), k_energy_out (normalise, expand to pixels, image orientation)
 //   lqr_shim.hip     the lqrhip_* C ABI of include/lqr_hip.h: allocation cache, batches, the per-seam launch sequence
 // lqr_kernels.h declares every kernel for the shim; each kernel file instantiates the templates the shim launches.
 //
@@ -566,3 +567,9 @@ constexpr int VP_REACH = 56;
 constexpr int VP_STAGE = 20;        // (4K: 39 chunks = 2 stages; the cone of a stage is 2 * 56 * 20 columns wide: 45 KB of LDS)
 constexpr int vp_chunk_rows(int delta) { return VP_REACH / delta; }
 #define VP_ROWS 62
+// energy read-outs (k_energy_out.hip): a workgroup of k_energy_range takes EO_CHUNK pixels of a frame row at a time and there are at
+// most EO_MAX_PARTIALS of them (each leaves one min / max pair, which every workgroup of k_energy_out folds: 2 pairs per thread);
+// k_energy_out writes tiles of EO_TILE x EO_TILE pixels
+#define EO_CHUNK 1024
+#define EO_MAX_PARTIALS 512
+#define EO_TILE 64

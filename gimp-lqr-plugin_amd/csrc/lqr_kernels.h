@@ -69,3 +69,10 @@ template <class T> __global__ __launch_bounds__(256) void k_mask_add_f(float *pl
                                                                        int transposed, int is_rig, int bias_factor);
 __global__ __launch_bounds__(256) void k_mask_scatter(float *plane, const int *index, const double *value, size_t n, int is_rig);
 __global__ __launch_bounds__(256) void k_plane_transpose(const float *plane, float *out, int w0, int h0);
+
+// k_energy_out.hip (energy read-outs, include/lqr_energy.h: PIC = the picture loop's arithmetic, TYPE = LqrImageType 0 .. 6, DEPTH = LqrColDepth)
+template <bool PIC> __global__ __launch_bounds__(256) void k_energy_range(const DevCarver *cs, int w, int h, int stride, float *partials);
+__global__ __launch_bounds__(256) void k_energy_plane(const DevCarver *cs, int w, int h, int stride, int transposed, int normalised,
+                                                      const float *partials, int n_partials, float *out);
+template <int TYPE, int DEPTH> __global__ __launch_bounds__(256) void k_energy_out(const DevCarver *cs, int w, int h, int stride, int transposed,
+                                                                                    const float *partials, int n_partials, uint8_t *out);

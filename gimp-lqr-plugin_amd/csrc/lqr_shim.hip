@@ -1115,6 +1115,61 @@ extern "C" int lqrhip_emap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w,
     return 0;
 }
 
+// ---- energy read-outs (include/lqr_energy.h; kernels in k_energy_out.hip) -------------------------
+extern "C" int lqrhip_energy_out(LqrHipBatch *b, int w, int h, int transposed, int form, int depth, int image_type, void *out, int on_device)
+{
+    static const int channels_of[7] = {3, 4, 1, 2, 3, 4, 5};        // RGB RGBA GREY GREYA CMY CMYK CMYKA
+    if (b->cs.size() != 1 || !out || w < 1 || h < 1 || form < 0 || form > 2) { g_err = "energy read-out: one carver, a buffer, form 0 .. 2"; return LQRHIP_EARG; }
+    if (form != 2) { depth = 2; image_type = 2; }                   // a float per pixel
+    if (depth < 0 || depth > 3 || image_type < 0 || image_type > 6) { g_err = "energy read-out: depth 0 .. 3, image type 0 .. 6"; return LQRHIP_EARG; }
+    int rc;
+    if ((rc = batch_upload(b))) return rc;
+    LqrHipCarver *c0 = b->cs[0];
+    if (!c0->en) return LQRHIP_EARG;
+    const size_t bytes = (size_t) w * h * channels_of[image_type] << depth;
+    const int chunks = (w + EO_CHUNK - 1) / EO_CHUNK;
+    const int n_partials = form ? (int) std::min((long long) EO_MAX_PARTIALS, (long long) h * chunks) : 0;
+    float *partials = nullptr;
+    uint8_t *staged = nullptr;
+    if (form && (rc = dmalloc(&partials, (size_t) 2 * n_partials))) return rc;
+    if (!on_device && (rc = dmalloc(&staged, bytes))) { dfree(partials); return rc; }
+    uint8_t *dst = on_device ? (uint8_t *) out : staged;
+    auto run = [&]() -> int {
+        // ("energy_out" in lqrhip_prof_get: the output stage alone, with the bytes it reads and writes)
+        ProfScope prof("energy_out", b->stream, (double) w * h * sizeof(float) * (form ? 2 : 1) + (double) bytes);
+        if (form == 1) hipLaunchKernelGGL(k_energy_range<false>, dim3(n_partials), dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, partials);
+        if (form == 2) hipLaunchKernelGGL(k_energy_range<true>, dim3(n_partials), dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, partials);
+        const int W = transposed ? h : w, H = transposed ? w : h;
+        const dim3 grid((W + EO_TILE - 1) / EO_TILE, (H + EO_TILE - 1) / EO_TILE);
+#define LAUNCH_EO(T, D) hipLaunchKernelGGL((k_energy_out<T, D>), grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, transposed, partials, n_partials, dst)
+#define LAUNCH_EO_D(T) do { if (depth == 0) LAUNCH_EO(T, 0); else if (depth == 1) LAUNCH_EO(T, 1); else if (depth == 2) LAUNCH_EO(T, 2); else LAUNCH_EO(T, 3); } while (0)
+        if (form != 2)
+            hipLaunchKernelGGL(k_energy_plane, grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, transposed, form, partials, n_partials, (float *) dst);
+        else switch (image_type) {
+            case 0: LAUNCH_EO_D(0); break;
+            case 1: LAUNCH_EO_D(1); break;
+            case 2: LAUNCH_EO_D(2); break;
+            case 3: LAUNCH_EO_D(3); break;
+            case 4: LAUNCH_EO_D(4); break;
+            case 5: LAUNCH_EO_D(5); break;
+            default: LAUNCH_EO_D(6); break;
+        }
+#undef LAUNCH_EO_D
+#undef LAUNCH_EO
+        return 0;
+    };
+    rc = run();
+    if (!rc) {
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+        if (e != hipSuccess) { g_err = std::string("energy read-out: ") + hipGetErrorString(e); (void) hipGetLastError(); rc = LQRHIP_EHIP; }
+    }
+    if (!rc) rc = check_dev_error();
+    if (!rc && !on_device) rc = d2h_staged(out, staged, bytes);
+    if (rc) (void) hipStreamSynchronize(b->stream);
+    dfree(partials); dfree(staged);
+    return rc;
+}
 
 // E5 as H/32 dependent launches of one wave per 192-column tile (any batch size)
 static int launch_dp_tiled(LqrHipBatch *b, const DpK &k, int w, int h, int lr)

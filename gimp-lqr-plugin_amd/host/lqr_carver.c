@@ -24,6 +24,7 @@
 #include "../../include/lqr_coldepth.h"
 #include "../../include/lqr_imagetype.h"
 #include "../../include/lqr_masks.h"
+#include "../../include/lqr_energy.h"
 #include "../../include/lqr_hip.h"
 #include "lqr_mask_queue.h"
 
@@ -1218,6 +1219,51 @@ LqrRetVal lqrx_carver_get_energy(LqrCarver *r, gfloat *buffer)
     if (ret == LQR_OK) ret = hip_ret(lqrhip_read_working(r->dev, r->w, r->h, buffer, NULL, NULL));
     group_close(&g);
     return ret;
+}
+
+/* ======================= energy read-outs (lqr_energy.h) ================= */
+/* All five entry points: the carver is brought to the frame seams of `orientation` are carved in, as lqr_carver_resize brings it there
+ * (flattened if it is not at the width of its visibility map, transposed -- and left so -- if it lies the other way), its energy is
+ * built, and the output stage writes it in image orientation.  form 0: the values as they are, 1: normalised, 2: pixels of depth /
+ * image_type.  A failure leaves the carver in one of the states this sequence passes through. */
+static LqrRetVal energy_read(LqrCarver *r, void *buffer, int on_device, int orientation, int form, int depth, int image_type)
+{
+    Group g;
+    LqrHipDpParams p;
+    LqrRetVal ret = LQR_OK;
+    if (!r || !buffer || (orientation != 0 && orientation != 1)) return LQR_ERROR;
+    if (form == 2 && (depth < LQR_COLDEPTH_8I || depth > LQR_COLDEPTH_64F || image_type < LQR_RGB_IMAGE || image_type >= LQR_CUSTOM_IMAGE))
+        return LQR_ERROR;
+    if (r->root) return LQR_ERROR;          /* (lqr_energy.h: an attached carver cannot be re-laid alone) */
+    LQR_CATCH(mask_queue_flush(r));
+    LQR_CATCH(group_open(&g, &r, 1));
+    if (r->w != r->w_start - r->max_level + 1) ret = group_flatten(&g);
+    if (ret == LQR_OK && r->transposed != orientation) ret = group_transpose(&g);
+    /* (a carver lqr_carver_init has not seen gets its working planes here too, and stays inactive) */
+    if (ret == LQR_OK && !r->wk_valid) {
+        if ((ret = hip_ret(lqrhip_wk_init(g.b[0], r->max_level != 1 || r->w0 != r->w_start))) == LQR_OK) r->wk_valid = 1;
+    }
+    if (ret == LQR_OK) {
+        dp_params(r, &p);
+        ret = hip_ret(lqrhip_emap_build(g.b[0], &p, r->w, r->h));
+    }
+    if (ret == LQR_OK) ret = hip_ret(lqrhip_energy_out(g.b[0], r->w, r->h, r->transposed, form, depth, image_type, buffer, on_device));
+    group_close(&g);
+    return ret;
+}
+LqrRetVal lqr_carver_get_energy(LqrCarver *r, gfloat *buffer, gint orientation) { return energy_read(r, buffer, 0, orientation, 1, 0, 0); }
+LqrRetVal lqr_carver_get_true_energy(LqrCarver *r, gfloat *buffer, gint orientation) { return energy_read(r, buffer, 0, orientation, 0, 0, 0); }
+LqrRetVal lqr_carver_get_energy_image(LqrCarver *r, void *buffer, gint orientation, LqrColDepth col_depth, LqrImageType image_type)
+{
+    return energy_read(r, buffer, 0, orientation, 2, (int) col_depth, (int) image_type);
+}
+LqrRetVal lqrx_carver_get_energy_device(LqrCarver *r, void *device_buffer, gint orientation, gint normalised)
+{
+    return energy_read(r, device_buffer, 1, orientation, normalised ? 1 : 0, 0, 0);
+}
+LqrRetVal lqrx_carver_get_energy_image_device(LqrCarver *r, void *device_buffer, gint orientation, LqrColDepth col_depth, LqrImageType image_type)
+{
+    return energy_read(r, device_buffer, 1, orientation, 2, (int) col_depth, (int) image_type);
 }
 
 LqrRetVal lqrx_carver_debug_maps(LqrCarver *r, gfloat *en, gfloat *m, gint *least_dx)

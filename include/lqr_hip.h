@@ -146,6 +146,12 @@ void *lqrhip_batch_stream(LqrHipBatch *b);      /* hipStream_t, for event timing
 int lqrhip_wk_init(LqrHipBatch *b, int from_visible);
 /* E3+E4 lqr_carver_build_emap: full energy map of the w x h carved frame */
 int lqrhip_emap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h);
+/* The output stage of the energy read-outs (lqr_energy.h), enqueued behind lqrhip_emap_build on the stream of a batch of ONE carver: the
+ * w x h energy plane of the carver's frame goes out in IMAGE orientation (`transposed`: the frame is the transpose of it), as
+ * form 0 the values as they are (floats), form 1 squashed and normalised to [0, 1] (floats), form 2 the normalised values as pixels of
+ * `depth` (LqrColDepth) and `image_type` (LqrImageType 0 .. 6; the float forms ignore both).  on_device = 1: `out` is device memory
+ * and nothing is copied to the host; 0: a host buffer, filled from a staging block through the pinned ring.  Returns with `out` written. */
+int lqrhip_energy_out(LqrHipBatch *b, int w, int h, int transposed, int form, int depth, int image_type, void *out, int on_device);
 /* E5 lqr_carver_build_mmap: full cumulative-min DP, tie rule by `leftright` */
 int lqrhip_mmap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h, int leftright);
 /* One seam of lqr_carver_build_vsmap (reached from lqr_carver_resize,

@@ -118,6 +118,11 @@ FLOAT_ONLY = ("lqr_carver_build_mmap", "lqr_carver_update_mmap", "lqr_carver_ini
               "lqr_carver_resize_width", "lqr_carver_resize_height")
 # ... which call this one, whose callees compute energies in double: back to the 53-bit control word inside it
 DOUBLE_INSIDE = ("lqr_carver_build_maps",)
+# the energy read-outs (include/lqr_energy.h): the squash / normalise loops of these two are float-only ...
+ENERGY_FLOAT_ONLY = ("lqr_carver_get_energy", "lqr_carver_get_true_energy")
+# ... around this one, which computes energies in double (lqr_carver_get_energy_image calls lqr_carver_get_energy and runs its own
+# loop, in double, under the caller's control word)
+ENERGY_DOUBLE_INSIDE = ("lqr_carver_build_emap",)
 
 
 class Runner:
@@ -127,8 +132,9 @@ class Runner:
        float24: additionally run the FLOAT_ONLY functions under 0x07f (24-bit mantissa), i.e. float arithmetic as an SSE2
        build performs it ("sse" mode = cw 0x27f + float24)"""
 
-    def __init__(self, cw=0x37f, poison=None, float24=False, float24_only=None):
-        """float24_only: run only THESE functions of FLOAT_ONLY under the 24-bit word (per-function evidence, precision_evidence.py)"""
+    def __init__(self, cw=0x37f, poison=None, float24=False, float24_only=None, energy24=False):
+        """float24_only: run only THESE functions of FLOAT_ONLY under the 24-bit word (per-function evidence, precision_evidence.py);
+        energy24: also ENERGY_FLOAT_ONLY, with ENERGY_DOUBLE_INSIDE back under `cw` (make_energy_golden.py)"""
         self.pe = PE(exe_bytes())
         self.proc = subprocess.Popen([build_runner()], stdin=subprocess.PIPE, stdout=subprocess.PIPE, bufsize=0)
         pe = self.pe
@@ -153,6 +159,12 @@ class Runner:
                     self.wrap(k, name, 0x07f)
             for k, name in enumerate(DOUBLE_INSIDE):
                 self.wrap(len(FLOAT_ONLY) + k, name, cw)
+        if energy24:
+            base = len(FLOAT_ONLY) + len(DOUBLE_INSIDE)
+            for k, name in enumerate(ENERGY_FLOAT_ONLY):
+                self.wrap(base + k, name, 0x07f)
+            for k, name in enumerate(ENERGY_DOUBLE_INSIDE):
+                self.wrap(base + len(ENERGY_FLOAT_ONLY) + k, name, cw)
         if poison is not None:
             self._cmd(OP_POISON, poison)
             self._read(4)
@@ -296,8 +308,8 @@ class RefApi:
     """stands where binding.Api stands in tests/harness.py (api.carver_class picks RefCarver)"""
     has_ext = False
 
-    def __init__(self, cw=0x37f, poison=None, float24=False, float24_only=None):
-        self.r = Runner(cw, poison, float24, float24_only)
+    def __init__(self, cw=0x37f, poison=None, float24=False, float24_only=None, energy24=False):
+        self.r = Runner(cw, poison, float24, float24_only, energy24)
         self.carver_class = RefCarver
         self.cw = cw
 
@@ -562,6 +574,35 @@ class RefCarver:
         ids = np.frombuffer(r.read(raw_p, 4 * w0 * h0), np.int32)
         en = np.frombuffer(r.read(en_p, 4 * w0 * h0), np.float32)
         return en[ids].reshape(h0, w0).copy()
+
+    # -- the energy read-outs (include/lqr_energy.h), as binding.Carver's
+    ENERGY_FUNCS = ("lqr_carver_get_true_energy", "lqr_carver_get_energy", "lqr_carver_get_energy_image")
+
+    def energy_call(self, form, orientation, depth=2, image_type=2, nbytes=0, guard=64, null=False):
+        """one read-out (form 0 true, 1 normalised, 2 picture) into nbytes + guard bytes of 0xA5: (LqrRetVal, the bytes afterwards)"""
+        r = self.r
+        p = r.alloc(nbytes + guard)
+        r.write(p, b"\xa5" * (nbytes + guard))
+        more = (int(depth), int(image_type)) if form == 2 else ()
+        ret = r.call(self.ENERGY_FUNCS[form], self.p, 0 if null else p, int(orientation), *more)
+        raw = r.read(p, nbytes + guard)
+        r.free(p)
+        return ret, np.frombuffer(raw, np.uint8).copy()
+
+    def _energy_shaped(self, form, orientation, depth=2, image_type=2, channels=1):
+        W, H = self.r.call("lqr_carver_get_width", self.p), self.r.call("lqr_carver_get_height", self.p)
+        dt = np.dtype(self.DTYPES[depth])
+        ret, buf = self.energy_call(form, orientation, depth, image_type, nbytes=W * H * channels * dt.itemsize, guard=0)
+        assert ret == LQR_OK, ret
+        return buf.view(dt).reshape((H, W, channels) if form == 2 else (H, W))
+
+    def get_energy(self, orientation, true=False):
+        """lqr_carver_get_energy / lqr_carver_get_true_energy: height x width float32, image orientation"""
+        return self._energy_shaped(0 if true else 1, orientation)
+
+    def get_energy_image(self, orientation, depth, image_type):
+        """lqr_carver_get_energy_image: height x width x channels of the depth's dtype"""
+        return self._energy_shaped(2, orientation, depth, image_type, {0: 3, 1: 4, 2: 1, 3: 2, 4: 3, 5: 4, 6: 5}[image_type])
 
     def configure(self, nrg_func=2, res_order=0, switch_freq=2, enl_step=1.5, dump_vmaps=False, progress=False):
         r = self.r

@@ -230,7 +230,7 @@ extern double tramp_f(u32 fn, const u32 *words, u32 n);
  * operation rounded to float), the driver retargets the call sites of such a function to one of these stubs, which
  * runs the original under another control word (0x07f: 24-bit mantissa) and restores the caller's.  Not re-entrant per
  * slot, which the wrapped functions do not need. */
-#define N_WRAP 8
+#define N_WRAP 16
 u32 wrap_orig[N_WRAP], wrap_ret[N_WRAP];
 unsigned short wrap_cw[N_WRAP], wrap_saved[N_WRAP];
 #define WRAP_STUB(k) \
@@ -243,6 +243,7 @@ unsigned short wrap_cw[N_WRAP], wrap_saved[N_WRAP];
             "  jmp *wrap_ret+4*" #k "\n"); \
     extern void wrap_stub##k(void);
 WRAP_STUB(0) WRAP_STUB(1) WRAP_STUB(2) WRAP_STUB(3) WRAP_STUB(4) WRAP_STUB(5) WRAP_STUB(6) WRAP_STUB(7)
+WRAP_STUB(8) WRAP_STUB(9) WRAP_STUB(10) WRAP_STUB(11) WRAP_STUB(12) WRAP_STUB(13) WRAP_STUB(14) WRAP_STUB(15)
 
 /* ---------------- protocol ---------------- */
 enum { OP_WRITE = 1, OP_READ, OP_ALLOC, OP_FREE, OP_CALL, OP_INFO, OP_SETCW, OP_EVENTS, OP_HEAPCHECK, OP_SCANALL, OP_POISON,
@@ -309,7 +310,8 @@ void _start_c(void)
         case OP_PROGRET: { u32 ok = 1; prog_ret = (int) hdr[1]; wr(&ok, 4); } break;
         case OP_WRAP: {       /* hdr[1] slot, hdr[2] original function, hdr[3] control word; reply: the stub's address */
             static void (*const stubs[N_WRAP])(void) = { wrap_stub0, wrap_stub1, wrap_stub2, wrap_stub3, wrap_stub4, wrap_stub5,
-                                                         wrap_stub6, wrap_stub7 };
+                                                         wrap_stub6, wrap_stub7, wrap_stub8, wrap_stub9, wrap_stub10, wrap_stub11,
+                                                         wrap_stub12, wrap_stub13, wrap_stub14, wrap_stub15 };
             u32 a;
             if (hdr[1] >= N_WRAP) die(86);
             wrap_orig[hdr[1]] = hdr[2]; wrap_cw[hdr[1]] = (unsigned short) hdr[3];
