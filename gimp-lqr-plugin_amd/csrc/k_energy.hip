@@ -6,23 +6,28 @@
 // ---------------------------------------------------------------------------
 // one-off kernels: working-plane init, full energy map, masks
 // ---------------------------------------------------------------------------
-__global__ void k_wk_init(const DevCarver *cs, int w, int h, int stride, int ch)
+// FORM (lqr_pixel.h): PixPacked -- the pixel's bytes in a u32 -- or PixValue<DEPTH> -- the value the energy reads, a double
+template <class FORM>
+__global__ void k_wk_init(const DevCarver *cs, int w, int h, int stride, typename FORM::Arg a)
 {
     const GCarver c = gview_phys(cs[blockIdx.z]);
+    GLOBAL_AS typename FORM::T *pix = (GLOBAL_AS typename FORM::T *) c.pix;
     int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x == 0 && y == 0) { c.flags[FLAG_ORG] = 0; c.flags[FLAG_ORG_PREV] = 0; c.flags[FLAG_SIDE] = 0; }      // planes laid out afresh
     if (x >= stride) return;
     size_t o = (size_t) y * stride + x;
-    uint32_t p = 0;
+    typename FORM::T p = 0;
     float b = 0.0f, r = 0.0f;
     if (x < w) {
-        const gu8 *s = c.rgb0 + ((size_t) y * w + x) * ch;
-        if (ch == 4) p = *(const gu32 *) s;
-        else for (int k = 0; k < ch; k++) p |= (uint32_t) s[k] << (8 * k);
+        if constexpr (std::is_same<FORM, PixPacked>::value) {      // PixPacked::form, spelt out: inlined from the call, the 8-bit form of this
+            const gu8 *s = c.rgb0 + ((size_t) y * w + x) * a;       // kernel (not of k_wk_init_visible) gets its byte loop scheduled differently
+            if (a == 4) p = *(const gu32 *) s;
+            else for (int k = 0; k < a; k++) p |= (uint32_t) s[k] << (8 * k);
+        } else p = FORM::form(c.rgb0, (size_t) y * w + x, a);
         if (c.bias0) b = c.bias0[(size_t) y * w + x];
         if (c.rig0) r = c.rig0[(size_t) y * w + x];
     }
-    c.pix[o] = p;
+    pix[o] = p;
     if (c.bias) c.bias[o] = b;
     if (c.rig) c.rig[o] = r;
 }
@@ -30,10 +35,12 @@ __global__ void k_wk_init(const DevCarver *cs, int w, int h, int stride, int ch)
 // The same from a carver that is NOT flat (round 6: a session redone after a fault, or working planes lost on a multi-size
 // image): the carved frame is the pixels of the base layout that have no level yet (vs == 0), in order -- what k_vs_commit
 // ranks.  One block per row, ballot-rank compaction; the tail of the row is zero-filled as k_wk_init does.
-__global__ __launch_bounds__(256) void k_wk_init_visible(const DevCarver *cs, int w0, int h, int stride, int ch)
+template <class FORM>
+__global__ __launch_bounds__(256) void k_wk_init_visible(const DevCarver *cs, int w0, int h, int stride, typename FORM::Arg a)
 {
     __shared__ int s_wave[4];
     const GCarver c = gview_phys(cs[blockIdx.y]);
+    GLOBAL_AS typename FORM::T *pix = (GLOBAL_AS typename FORM::T *) c.pix;
     const int y = blockIdx.x, tid = threadIdx.x;
     if (y == 0 && tid == 0) { c.flags[FLAG_ORG] = 0; c.flags[FLAG_ORG_PREV] = 0; c.flags[FLAG_SIDE] = 0; }
     const size_t ri = (size_t) y * w0, ro = (size_t) y * stride;
@@ -44,33 +51,31 @@ __global__ __launch_bounds__(256) void k_wk_init_visible(const DevCarver *cs, in
         int total;
         const int rank = carry + block_rank_256(keep, s_wave, total);
         if (keep && rank < stride) {
-            const gu8 *s = c.rgb0 + (ri + col) * ch;
-            uint32_t p = 0;
-            if (ch == 4) p = *(const gu32 *) s;
-            else for (int k = 0; k < ch; k++) p |= (uint32_t) s[k] << (8 * k);
-            c.pix[ro + rank] = p;
+            pix[ro + rank] = FORM::form(c.rgb0, ri + col, a);
             if (c.bias) c.bias[ro + rank] = c.bias0 ? c.bias0[ri + col] : 0.0f;
             if (c.rig) c.rig[ro + rank] = c.rig0 ? c.rig0[ri + col] : 0.0f;
         }
         carry += total;
     }
     for (int x = carry + tid; x < stride; x += 256) {
-        c.pix[ro + x] = 0u;
+        pix[ro + x] = 0;
         if (c.bias) c.bias[ro + x] = 0.0f;
         if (c.rig) c.rig[ro + x] = 0.0f;
     }
 }
 
-template <int NRG>
+// E3/E4.  VALUE (lqr_pixel.h, PixRead): the working plane holds the value the energy reads, not packed pixels
+template <int NRG, bool VALUE>
 __global__ void k_emap_full(const DevCarver *cs, DpK p, int w, int h, int stride)
 {
-    __shared__ double s_n255[256];
-    fill_norm255(s_n255, threadIdx.x, blockDim.x);
-    __syncthreads();
+    PixRead<VALUE> rd;
+    rd.setup(threadIdx.x, blockDim.x);
     const GCarver c = gview(cs[blockIdx.z]);
     int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= w) return;
-    c.en[(size_t) y * stride + x] = energy_at<NRG>(c, p, stride, x, y, w, h, Norm255Lut{s_n255});
+    float e = grad_energy_f<NRG>([&](int xx, int yy) { return rd(c.pix, (size_t) yy * stride + xx, p.ch, NRG >= 3); }, x, y, w, h);
+    if (c.bias) e = __fadd_rn(e, __fdiv_rn(c.bias[(size_t) y * stride + x], (float) p.w_start));
+    c.en[(size_t) y * stride + x] = e;
 }
 
 // E2: mask value = mean(colour)/255 * alpha/255 (help/en/index.wiki:48)
@@ -107,17 +112,17 @@ __global__ void k_mask_add(float *plane, int w0, const uint8_t *mask, int channe
 // y-1..y+1 by its own gradient and [min - 1, max] of the seam over rows y-2..y+2 by its neighbours', and the
 // seam moves at most delta_x per row: at most max(4*delta_x + 2, 2*delta_x + 4) columns.  EU_NT is a template
 // parameter chosen by the launch from delta_x: 12 (delta_x <= 2), 36 (<= 8), 68 (<= 16 = LQRHIP_MAX_DELTA).
-template <int NRG, int EU_NT>
+// VALUE: the frozen plane holds the value the energy reads (PixRead: no table of v / 255 then, and the sample is the element).
+template <int NRG, int EU_NT, bool VALUE>
 __global__ __launch_bounds__(64) void k_emap_update(const DevCarver *cs, DpK p, int w, int h, int stride, int k, int epoch)
 {
     const GCarver c = gview(cs[blockIdx.y]);
     __shared__ double bt[64][EU_NT];
     __shared__ float bb[64][EU_NT];
     __shared__ int slo[64];
-    __shared__ double s_n255[256];
     const int tid = threadIdx.x;
-    fill_norm255(s_n255, tid, 64);
-    __syncthreads();
+    PixRead<VALUE> rd;
+    rd.setup(tid, 64);
     const int y = blockIdx.x * EU_ROWS + tid - 1;
     const bool row_ok = (y >= 0 && y < h);
     constexpr bool luma = (NRG >= 3);
@@ -152,7 +157,7 @@ __global__ __launch_bounds__(64) void k_emap_update(const DevCarver *cs, DpK p, 
         for (int i = 0; i < EU_NT; i++) {
             const bool ok = (lo + i <= min(r, w - 1)) && pos[i] < wf;
             const size_t o = (size_t) y * stride + (ok ? pos[i] : 0);
-            bt[tid][i] = ok ? px_bright(c.pix[o], p.ch, luma, Norm255Lut{s_n255}) : 0.0;
+            bt[tid][i] = ok ? rd(c.pix, o, p.ch, luma) : 0.0;
             bb[tid][i] = (ok && c.bias) ? c.bias[o] : 0.0f;
         }
     }
@@ -167,7 +172,8 @@ __global__ __launch_bounds__(64) void k_emap_update(const DevCarver *cs, DpK p, 
 }
 
 // bring the frozen planes (pix, bias) forward: remove seams [from, to) of the session log from
-// every row; w_from = width of the frame the planes are in.  One block per row, in place.
+// every row; w_from = width of the frame the planes are in.  One block per row, in place.  VALUE: 8-byte values instead of packed pixels
+template <bool VALUE>
 __global__ __launch_bounds__(256) void k_frozen_catchup(const DevCarver *cs, int from, int to, int w_from, int h, int stride)
 {
     const GCarver c = gview(cs[blockIdx.y]);
@@ -185,13 +191,14 @@ __global__ __launch_bounds__(256) void k_frozen_catchup(const DevCarver *cs, int
         rem[pz] = 1;
     }
     __syncthreads();
-    gu32 *prow = c.pix + (size_t) y * stride;
+    typedef typename PixRead<VALUE>::T T;
+    GLOBAL_AS T *prow = (GLOBAL_AS T *) c.pix + (size_t) y * stride;
     gf32 *brow = c.bias ? c.bias + (size_t) y * stride : (gf32 *) nullptr;
     int carry = 0;
     for (int base = 0; base < w_from; base += 256) {
         const int col = base + tid;
         const bool keep = (col < w_from) && !rem[col];
-        const uint32_t v = (col < w_from) ? prow[col] : 0u;
+        const T v = (col < w_from) ? prow[col] : 0;
         const float bv = (brow && col < w_from) ? brow[col] : 0.0f;
         int total;
         const int rank = carry + block_rank_256(keep, s_wave, total);     // barriers inside: all reads of the chunk are done
@@ -201,9 +208,16 @@ __global__ __launch_bounds__(256) void k_frozen_catchup(const DevCarver *cs, int
 }
 
 
-// ---- the instantiations the shim launches (lqr_kernels.h declares them)
-#define INST_EMAP(N) template __global__ void k_emap_full<N>(const DevCarver *, DpK, int, int, int); \
-    template __global__ void k_emap_update<N, 12>(const DevCarver *, DpK, int, int, int, int, int); \
-    template __global__ void k_emap_update<N, 36>(const DevCarver *, DpK, int, int, int, int, int); \
-    template __global__ void k_emap_update<N, 68>(const DevCarver *, DpK, int, int, int, int, int);
-INST_EMAP(0) INST_EMAP(1) INST_EMAP(2) INST_EMAP(3) INST_EMAP(4) INST_EMAP(5) INST_EMAP(6)
+// ---- the instantiations the shim launches (lqr_kernels.h declares them).  The value forms exist for energies 0, 1, 2 and 6 only:
+// the plane already holds brightness or luma, so 3, 4, 5 would be the code of 0, 1, 2 again (plane_nrg in lqr_shim.hip)
+#define INST_WK(FORM) template __global__ void k_wk_init<FORM>(const DevCarver *, int, int, int, FORM::Arg); \
+    template __global__ void k_wk_init_visible<FORM>(const DevCarver *, int, int, int, FORM::Arg);
+INST_WK(PixPacked) INST_WK(PixValue<0>) INST_WK(PixValue<1>) INST_WK(PixValue<2>) INST_WK(PixValue<3>)
+#define INST_EMAP(N, V) template __global__ void k_emap_full<N, V>(const DevCarver *, DpK, int, int, int); \
+    template __global__ void k_emap_update<N, 12, V>(const DevCarver *, DpK, int, int, int, int, int); \
+    template __global__ void k_emap_update<N, 36, V>(const DevCarver *, DpK, int, int, int, int, int); \
+    template __global__ void k_emap_update<N, 68, V>(const DevCarver *, DpK, int, int, int, int, int);
+INST_EMAP(0, false) INST_EMAP(1, false) INST_EMAP(2, false) INST_EMAP(3, false) INST_EMAP(4, false) INST_EMAP(5, false) INST_EMAP(6, false)
+INST_EMAP(0, true) INST_EMAP(1, true) INST_EMAP(2, true) INST_EMAP(6, true)
+template __global__ void k_frozen_catchup<false>(const DevCarver *, int, int, int, int, int);
+template __global__ void k_frozen_catchup<true>(const DevCarver *, int, int, int, int, int);

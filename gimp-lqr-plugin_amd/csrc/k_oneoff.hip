@@ -43,23 +43,6 @@ __global__ __launch_bounds__(256) void k_vs_commit(const DevCarver *cs, int w0, 
     }
 }
 
-// one interleaved pixel of `ch` bytes, base layout: RGBA pixels are dword-aligned (rows start at y * w * 4) and move as
-// one 32-bit access instead of four byte accesses
-__device__ __forceinline__ void px_copy(uint8_t *dst, const uint8_t *src, int ch)
-{
-    if (ch == 4) *(uint32_t *) dst = *(const uint32_t *) src;
-    else for (int k = 0; k < ch; k++) dst[k] = src[k];
-}
-__device__ __forceinline__ void px_avg(uint8_t *dst, const uint8_t *a, const uint8_t *b, int ch)       // (a + b) / 2 per channel, as integers
-{
-    if (ch == 4) {
-        const uint32_t x = *(const uint32_t *) a, y = *(const uint32_t *) b;
-        *(uint32_t *) dst = (x & y) + (((x ^ y) & 0xfefefefeu) >> 1);          // per byte floor((x + y) / 2), no carries across bytes
-    } else {
-        for (int k = 0; k < ch; k++) dst[k] = (uint8_t) (((int) a[k] + (int) b[k]) / 2);
-    }
-}
-
 // E14: one block per row (blockIdx.x) of one carver of the batch (blockIdx.y: every carver and attached carver of the
 // batch in ONE launch -- a launch per carver leaves most of the chip idle behind each row's serial rank scan).
 // dup(c) = the seam was computed in this session.
@@ -67,6 +50,8 @@ __device__ __forceinline__ void px_avg(uint8_t *dst, const uint8_t *a, const uin
 // once in every row (k_vs_commit's contract).  The pass reads every level anyway: a bit per level in LDS (atomicOr) finds a level
 // that occurs twice, the row's dup count a missing one.  A failure goes to the host-visible error word (DEVERR_LEVELS); the host
 // then does not adopt the inflated planes, rolls the session back and redoes it (host/lqr_carver.c, group_build_maps).
+// DEEP (lqr_pixel.h, BasePx): the carvers of a batch whose pixels are not 8-bit ones of up to 4 channels; jobs[i].ch = bytes per pixel either way
+template <bool DEEP>
 __global__ __launch_bounds__(256) void k_inflate(const InflateDev *jobs, int w0, int w1, int l, int max_level, int *dev_err)
 {
     __shared__ int s_wave[4];
@@ -98,13 +83,13 @@ __global__ __launch_bounds__(256) void k_inflate(const InflateDev *jobs, int w0,
             int z = col + rank;
             int left = col > 0 ? col - 1 : col;
             if (dup) {
-                px_avg(nrgb + (ro + z) * ch, rgb + (ri + left) * ch, rgb + (ri + col) * ch, ch);
+                BasePx<DEEP>::avg(nrgb + (ro + z) * ch, rgb + (ri + left) * ch, rgb + (ri + col) * ch, ch, j.depth);
                 if (nbias) nbias[ro + z] = __fmul_rn(__fadd_rn(bias[ri + left], bias[ri + col]), 0.5f);
                 if (nrig) nrig[ro + z] = __fmul_rn(__fadd_rn(rig[ri + left], rig[ri + col]), 0.5f);
                 if (nvs) nvs[ro + z] = l - v + max_level;
                 z++;
             }
-            px_copy(nrgb + (ro + z) * ch, rgb + (ri + col) * ch, ch);
+            BasePx<DEEP>::move(nrgb + (ro + z) * ch, rgb + (ri + col) * ch, ch);
             if (nbias) nbias[ro + z] = bias[ri + col];
             if (nrig) nrig[ro + z] = rig[ri + col];
             if (nvs) nvs[ro + z] = v ? v + l - max_level + 1 : 0;
@@ -161,7 +146,9 @@ __global__ void k_inject(const DevCarver *cs, int what, int h, int w0, int log_i
     }
 }
 
-// E11/E12: compaction of the pixels visible at `level`; any output may be null
+// E11/E12: compaction of the pixels visible at `level`; any output may be null.  DEEP: pixels wider than 4 bytes (ch = bytes per
+// pixel) -- the read-out of a deep carver's pixels, which is all that form is launched for: it writes nrgb and no other plane
+template <bool DEEP>
 __global__ __launch_bounds__(256) void k_compact(const uint8_t *rgb, const int32_t *vs, const float *bias, const float *rig,
                                                   uint8_t *nrgb, float *nbias, float *nrig, int32_t *nvmap, int w0, int w, int ch,
                                                   int level, int depth)
@@ -178,16 +165,17 @@ __global__ __launch_bounds__(256) void k_compact(const uint8_t *rgb, const int32
         int total;
         int rank = carry + block_rank_256(keep, s_wave, total);
         if (keep && rank < w) {
-            if (nrgb) px_copy(nrgb + (ro + rank) * ch, rgb + (ri + col) * ch, ch);
-            if (nbias) nbias[ro + rank] = bias[ri + col];
-            if (nrig) nrig[ro + rank] = rig[ri + col];
-            if (nvmap) nvmap[ro + rank] = v ? v - depth : 0;
+            if (nrgb) BasePx<DEEP>::move(nrgb + (ro + rank) * ch, rgb + (ri + col) * ch, ch);
+            if (!DEEP && nbias) nbias[ro + rank] = bias[ri + col];
+            if (!DEEP && nrig) nrig[ro + rank] = rig[ri + col];
+            if (!DEEP && nvmap) nvmap[ro + rank] = v ? v - depth : 0;
         }
         carry += total;
     }
 }
 
 // E11 flatten for every carver of a batch in ONE launch (job table as k_inflate: blockIdx.y = job, blockIdx.x = row)
+template <bool DEEP>
 __global__ __launch_bounds__(256) void k_compact_jobs(const InflateDev *jobs, int w0, int w, int level)
 {
     __shared__ int s_wave[4];
@@ -203,7 +191,7 @@ __global__ __launch_bounds__(256) void k_compact_jobs(const InflateDev *jobs, in
         int total;
         int rank = carry + block_rank_256(keep, s_wave, total);
         if (keep && rank < w) {
-            px_copy(j.nrgb + (ro + rank) * ch, j.rgb + (ri + col) * ch, ch);
+            BasePx<DEEP>::move(j.nrgb + (ro + rank) * ch, j.rgb + (ri + col) * ch, ch);
             if (j.nbias) j.nbias[ro + rank] = j.bias[ri + col];
             if (j.nrig) j.nrig[ro + rank] = j.rig[ri + col];
         }
@@ -211,7 +199,8 @@ __global__ __launch_bounds__(256) void k_compact_jobs(const InflateDev *jobs, in
     }
 }
 
-// E11 transpose of every carver of a batch in one launch (blockIdx.z = job); RGBA pixels move as dwords
+// E11 transpose of every carver of a batch in one launch (blockIdx.z = job) for pixels of up to 4 bytes, staged through an LDS tile
+// as dwords; wider pixels: k_transpose_px
 __global__ void k_transpose(const InflateDev *jobs, int w, int h)
 {
     __shared__ uint32_t t32[32][33];
@@ -250,6 +239,24 @@ __global__ void k_transpose(const InflateDev *jobs, int w, int h)
     }
 }
 
+// E11 transpose of pixels wider than 4 bytes (jobs[i].ch = bytes per pixel), no LDS tile: one thread per output pixel of a
+// 32 x 32 tile, rows of the output written together
+__global__ void k_transpose_px(const InflateDev *jobs, int w, int h)
+{
+    const InflateDev j = jobs[blockIdx.z];
+    const int bytes = j.ch;
+    const int oy = blockIdx.y * 32 + threadIdx.x;          // output column = old y
+    for (int i = threadIdx.y; i < 32; i += blockDim.y) {
+        const int ox = blockIdx.x * 32 + i;                // output row = old x
+        if (ox < w && oy < h) {
+            const size_t src = (size_t) oy * w + ox, dst = (size_t) ox * h + oy;
+            px_move(j.nrgb + dst * bytes, j.rgb + src * bytes, bytes);
+            if (j.nbias) j.nbias[dst] = j.bias[src];
+            if (j.nrig) j.nrig[dst] = j.rig[src];
+        }
+    }
+}
+
 // auto-size (plug-in's guess_new_size, src/layers_combo.c:275-392): one block per line counts the
 // mask pixels at or above the threshold; atomicMax over lines
 __global__ __launch_bounds__(256) void k_mask_line_max(const uint8_t *mask, int channels, int width, int a0, int b0, int line_len,
@@ -278,4 +285,7 @@ __global__ __launch_bounds__(256) void k_mask_line_max(const uint8_t *mask, int 
 
 
 // ---- the instantiations the shim launches (lqr_kernels.h declares them)
-// (no templates)
+#define INST_BASE(D) template __global__ void k_inflate<D>(const InflateDev *, int, int, int, int, int *); \
+    template __global__ void k_compact<D>(const uint8_t *, const int32_t *, const float *, const float *, uint8_t *, float *, float *, int32_t *, int, int, int, int, int); \
+    template __global__ void k_compact_jobs<D>(const InflateDev *, int, int, int);
+INST_BASE(false) INST_BASE(true)

@@ -3,17 +3,19 @@
 // dp_row_g) that all the halo kernels run, and the geometry constants of the tiled kernels that their launchers need.
 //
 // Translation units (one per stage, so that a change to one protocol rebuilds -- and re-register-allocates -- only that one):
-//   k_energy.hip     E1/E2/E3/E4/E6  k_wk_init, k_mask_add, k_emap_full, k_emap_update, k_frozen_catchup
+//   k_energy.hip     E1/E2/E3/E4/E6  k_wk_init(_visible), k_mask_add, k_emap_full, k_emap_update, k_frozen_catchup
 //   k_backtrack.hip  E7              k_vpath, k_vpath1 (they also pick the side the carve moves)
 //   k_carve.hip      E8              k_carve
 //   k_band.hip       E5/E9           k_dp_sweep, k_band_update, k_band_update_mw, k_band_update_tw (one workgroup per image)
 //   k_tiles.hip      E5/E9           k_dp_tile, k_dp_tile_p (an image spread over several compute units)
 //   k_levels.hip     E9              k_band_levels (the band on several compute units, tiles assigned level by level)
-//   k_oneoff.hip     E8(vs)/E11/E12/E14, auto-size  k_vs_commit, k_inflate, k_compact(_jobs), k_transpose, k_mask_line_max
+//   k_oneoff.hip     E8(vs)/E11/E12/E14, auto-size  k_vs_commit, k_inflate, k_compact(_jobs), k_transpose(_px), k_mask_line_max
 //   k_masks.hip      E2 (lqr_masks.h) k_mask_add_f (float / double masks, host or device), k_mask_scatter (queued _xy calls), k_plane_transpose
 //   k_energy_out.hip energy read-outs (lqr_energy.h) k_energy_range (squash, min / max per workgroup), k_energy_out (normalise, expand to pixels, image orientation)
 //   lqr_shim.hip     the lqrhip_* C ABI of include/lqr_hip.h: allocation cache, batches, the per-seam launch sequence
 // lqr_kernels.h declares every kernel for the shim; each kernel file instantiates the templates the shim launches.
+// lqr_pixel.h (k_energy.hip, k_oneoff.hip): the packed 8-bit and the value / deep form of a pixel as compile-time policies, so that
+// every kernel that touches pixels exists once and serves 8-bit grey / RGB carvers and those of any other depth, type or channel count
 //
 // The stages replace liblqr-1's CPU engine as reached from the plug-in's
 // render path (gimp-lqr-plugin src/render.c:318,328,529 -> lqr_carver_resize):
@@ -540,14 +542,10 @@ struct InflateDev {
     uint8_t *nrgb;
     int32_t *nvs;
     float *nbias, *nrig;
-    int ch;
+    int ch;                 // bytes per pixel
+    int depth;              // LqrColDepth (read by k_inflate<true> only: how new pixels are averaged)
 };
-// a job of k_inflate_deep: the carver's depth (LqrColDepth; 0 for 8-bit pixels of more than 4 channels) beside its planes; j.ch = channels
-struct InflateDevX {
-    InflateDev j;
-    int depth;
-};
-// How a carver that reads through the value plane (k_deep.hip) forms the value its energy reads: liblqr's image type
+// How a carver that reads through the value plane (lqr_pixel.h) forms the value its energy reads: liblqr's image type
 // (lqr_imagetype.h) reduced to the arithmetic it selects, the alpha and black channel indices (-1: none), brightness or luma
 #define RD_GREY 0           // GREY, GREYA: channel 0
 #define RD_RGB 1            // RGB, RGBA: channels 0 .. 2

@@ -4,15 +4,19 @@
 // (-Wl,-z,defs in the Makefile).
 #pragma once
 #include "lqr_common.h"
+#include "lqr_pixel.h"
+
+// Kernels that touch pixels take the pixel's form as a compile-time parameter (lqr_pixel.h): FORM = PixPacked or PixValue<DEPTH>, VALUE =
+// the working plane holds one double per pixel (carvers that are not 8-bit grey / RGB (+ alpha)), DEEP = base-layout pixels beyond 4 x 8 bits
 
 // k_energy.hip
-__global__ void k_wk_init(const DevCarver *cs, int w, int h, int stride, int ch);
-__global__ __launch_bounds__(256) void k_wk_init_visible(const DevCarver *cs, int w0, int h, int stride, int ch);
-template <int NRG> __global__ void k_emap_full(const DevCarver *cs, DpK p, int w, int h, int stride);
+template <class FORM> __global__ void k_wk_init(const DevCarver *cs, int w, int h, int stride, typename FORM::Arg a);
+template <class FORM> __global__ __launch_bounds__(256) void k_wk_init_visible(const DevCarver *cs, int w0, int h, int stride, typename FORM::Arg a);
+template <int NRG, bool VALUE> __global__ void k_emap_full(const DevCarver *cs, DpK p, int w, int h, int stride);
 __global__ void k_mask_add(float *plane, int w0, const uint8_t *mask, int channels, int mw, int x0, int y0, int x1, int y1,
                            int nx, int ny, int transposed, int is_rig, int bias_factor);
-template <int NRG, int EU_NT> __global__ __launch_bounds__(64) void k_emap_update(const DevCarver *cs, DpK p, int w, int h, int stride, int k, int epoch);
-__global__ __launch_bounds__(256) void k_frozen_catchup(const DevCarver *cs, int from, int to, int w_from, int h, int stride);
+template <int NRG, int EU_NT, bool VALUE> __global__ __launch_bounds__(64) void k_emap_update(const DevCarver *cs, DpK p, int w, int h, int stride, int k, int epoch);
+template <bool VALUE> __global__ __launch_bounds__(256) void k_frozen_catchup(const DevCarver *cs, int from, int to, int w_from, int h, int stride);
 
 // k_backtrack.hip
 __global__ __launch_bounds__(VPATH_THREADS) void k_vpath(const DevCarver *cs, int w, int h, int stride, int lr, int delta, int log_index, int moved_unit);
@@ -42,27 +46,16 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 // k_oneoff.hip
 __global__ __launch_bounds__(256) void k_vs_commit(const DevCarver *cs, int w0, int h0, int wc0, int n_seams, int first_level, int finish);
-__global__ __launch_bounds__(256) void k_inflate(const InflateDev *jobs, int w0, int w1, int l, int max_level, int *dev_err);
+template <bool DEEP> __global__ __launch_bounds__(256) void k_inflate(const InflateDev *jobs, int w0, int w1, int l, int max_level, int *dev_err);
 __global__ __launch_bounds__(256) void k_seam_check(const DevCarver *cs, int h, int wc0, int n_seams, int delta, int *dev_err);
 __global__ __launch_bounds__(256) void k_vs_rollback(const DevCarver *cs, size_t n, int first_level, int finish_level);
 __global__ void k_inject(const DevCarver *cs, int what, int h, int w0, int log_index, int first_level);
-__global__ __launch_bounds__(256) void k_compact(const uint8_t *rgb, const int32_t *vs, const float *bias, const float *rig,
+template <bool DEEP> __global__ __launch_bounds__(256) void k_compact(const uint8_t *rgb, const int32_t *vs, const float *bias, const float *rig,
                                                   uint8_t *nrgb, float *nbias, float *nrig, int32_t *nvmap, int w0, int w, int ch, int level, int depth);
-__global__ __launch_bounds__(256) void k_compact_jobs(const InflateDev *jobs, int w0, int w, int level);
+template <bool DEEP> __global__ __launch_bounds__(256) void k_compact_jobs(const InflateDev *jobs, int w0, int w, int level);
 __global__ void k_transpose(const InflateDev *jobs, int w, int h);
-__global__ __launch_bounds__(256) void k_mask_line_max(const uint8_t *mask, int channels, int width, int a0, int b0, int line_len, int direction, int *out);
-
-// k_deep.hip (carvers that read through the value plane -- depth 16I / 32F / 64F, image types beyond grey / RGB (+ alpha), more than 4
-// channels: `pix` holds one double per pixel; DEPTH 0 = 8I)
-template <int DEPTH> __global__ void k_wk_init_deep(const DevCarver *cs, int w, int h, int stride, DeepRead rd);
-template <int DEPTH> __global__ __launch_bounds__(256) void k_wk_init_visible_deep(const DevCarver *cs, int w0, int h, int stride, DeepRead rd);
-template <int NRG> __global__ void k_emap_full_deep(const DevCarver *cs, DpK p, int w, int h, int stride);
-template <int NRG, int EU_NT> __global__ __launch_bounds__(64) void k_emap_update_deep(const DevCarver *cs, DpK p, int w, int h, int stride, int k, int epoch);
-__global__ __launch_bounds__(256) void k_frozen_catchup_deep(const DevCarver *cs, int from, int to, int w_from, int h, int stride);
-__global__ __launch_bounds__(256) void k_inflate_deep(const InflateDevX *jobs, int w0, int w1, int l, int max_level, int *dev_err);
 __global__ void k_transpose_px(const InflateDev *jobs, int w, int h);
-__global__ __launch_bounds__(256) void k_compact_wide(const uint8_t *rgb, const int32_t *vs, uint8_t *nrgb, int w0, int w, int bytes, int level);
-__global__ __launch_bounds__(256) void k_compact_jobs_wide(const InflateDev *jobs, int w0, int w, int level);
+__global__ __launch_bounds__(256) void k_mask_line_max(const uint8_t *mask, int channels, int width, int a0, int b0, int line_len, int direction, int *out);
 
 // k_masks.hip (computed masks, include/lqr_masks.h: T = float or double)
 template <class T> __global__ __launch_bounds__(256) void k_mask_add_f(float *plane, int w0, const T *mask, int mw, int x0, int y0, int x1, int y1, int nx, int ny,

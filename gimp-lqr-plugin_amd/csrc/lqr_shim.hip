@@ -541,7 +541,7 @@ static int d2h_staged(void *dst, const void *src, size_t bytes)
     return rc;
 }
 
-// A carver reads through the value plane (`pix` holds one double per pixel, the value the energy reads; k_deep.hip) unless it is
+// A carver reads through the value plane (`pix` holds one double per pixel, the value the energy reads; lqr_pixel.h) unless it is
 // 8-bit grey / RGB with or without alpha in liblqr's default layout: those keep their pixels packed in `pix` and every kernel they had.
 // (The rule is restated by tests/imgtype_cases.py reads_value; same_config in host/lqr_carver.c groups only carvers whose type
 // and roles are equal, so that a group is on one side of it.  Keep the three in step.)
@@ -551,6 +551,15 @@ static inline bool reads_value(const LqrHipCarver *c)
     return c->black >= 0 || c->alpha != (c->ch == 2 ? 1 : c->ch == 4 ? 3 : -1);
 }
 static inline DeepRead deep_read(const LqrHipCarver *c) { return DeepRead{c->ch, c->mode, c->alpha, c->black, c->luma}; }
+// The kernels that touch the working plane exist in both forms (template parameter VALUE): f gets the carver's as a compile-time constant
+template <class F> static inline void with_form(const LqrHipCarver *c, F f)
+{
+    if (reads_value(c)) f(std::true_type{}); else f(std::false_type{});
+}
+// The energy a kernel is instantiated for.  On the value plane the luma energies (3, 4, 5) ARE the brightness energies (0, 1, 2): the
+// plane already holds brightness or luma (DeepRead.luma decided it when the plane was laid out) and grad_energy_f only looks at
+// NRG % 3, so the six would compile to three pairs of identical kernels.  The value forms are instantiated for 0, 1, 2 and 6 only.
+constexpr int plane_nrg(bool value, int nrg) { return value && nrg >= 3 && nrg <= 5 ? nrg - 3 : nrg; }
 // liblqr's default image type for a channel count, as a read mode
 static void default_read(LqrHipCarver *c)
 {
@@ -1078,19 +1087,15 @@ extern "C" int lqrhip_wk_init(LqrHipBatch *b, int from_visible)
     }
     if ((rc = batch_upload(b))) return rc;
     for (auto *c : b->cs) c->frozen_epoch = 0;
-    if (reads_value(c0)) {
-        const dim3 grid((c0->stride + 255) / 256, h, (unsigned) b->cs.size()), grid_v(h, (unsigned) b->cs.size());
-        const DeepRead rd = deep_read(c0);
-#define LAUNCH_WKD(D) do { if (from_visible) hipLaunchKernelGGL(k_wk_init_visible_deep<D>, grid_v, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, rd); \
-                           else hipLaunchKernelGGL(k_wk_init_deep<D>, grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, rd); } while (0)
-        if (c0->depth == 0) LAUNCH_WKD(0); else if (c0->depth == 1) LAUNCH_WKD(1); else if (c0->depth == 2) LAUNCH_WKD(2); else LAUNCH_WKD(3);
-#undef LAUNCH_WKD
-    } else if (from_visible) {
-        hipLaunchKernelGGL(k_wk_init_visible, dim3(h, (unsigned) b->cs.size()), dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, c0->ch);
-    } else {
-        dim3 grid((c0->stride + 255) / 256, h, (unsigned) b->cs.size());
-        hipLaunchKernelGGL(k_wk_init, grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, c0->ch);
-    }
+    const dim3 grid((c0->stride + 255) / 256, h, (unsigned) b->cs.size()), grid_v(h, (unsigned) b->cs.size());
+#define LAUNCH_WK(FORM, arg) do { if (from_visible) hipLaunchKernelGGL(k_wk_init_visible<FORM>, grid_v, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, arg); \
+                                  else hipLaunchKernelGGL(k_wk_init<FORM>, grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, arg); } while (0)
+    if (!reads_value(c0)) LAUNCH_WK(PixPacked, c0->ch);
+    else if (c0->depth == 0) LAUNCH_WK(PixValue<0>, deep_read(c0));
+    else if (c0->depth == 1) LAUNCH_WK(PixValue<1>, deep_read(c0));
+    else if (c0->depth == 2) LAUNCH_WK(PixValue<2>, deep_read(c0));
+    else LAUNCH_WK(PixValue<3>, deep_read(c0));
+#undef LAUNCH_WK
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -1102,15 +1107,11 @@ extern "C" int lqrhip_emap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w,
     LqrHipCarver *c0 = b->cs[0];
     dim3 grid((w + 255) / 256, h, (unsigned) b->cs.size());
     DpK k = make_dpk(p, c0->ch);
-    if (reads_value(c0)) {
-#define LAUNCH_EMAP(N) hipLaunchKernelGGL((k_emap_full_deep<N>), grid, dim3(256), 0, b->stream, b->d_desc, k, w, h, c0->stride)
+    with_form(c0, [&](auto value) {
+#define LAUNCH_EMAP(N) hipLaunchKernelGGL((k_emap_full<plane_nrg(value, N), value>), grid, dim3(256), 0, b->stream, b->d_desc, k, w, h, c0->stride)
         NRG_DISPATCH(p->nrg_func, LAUNCH_EMAP)
 #undef LAUNCH_EMAP
-    } else {
-#define LAUNCH_EMAP(N) hipLaunchKernelGGL((k_emap_full<N>), grid, dim3(256), 0, b->stream, b->d_desc, k, w, h, c0->stride)
-    NRG_DISPATCH(p->nrg_func, LAUNCH_EMAP)
-#undef LAUNCH_EMAP
-    }
+    });
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -1412,12 +1413,10 @@ static int frozen_catchup(LqrHipBatch *b, int to, int w_at_to, int h)
     if (to <= from) return 0;
     const int w_from = w_at_to + (to - from);
     size_t lds = (size_t) (to - from) * sizeof(int) + (size_t) w_from + 16;
-    if (reads_value(c0))
-        hipLaunchKernelGGL(k_frozen_catchup_deep, dim3(h, (unsigned) b->cs.size()), dim3(256), lds, b->stream, b->d_desc, from, to, w_from, h,
+    with_form(c0, [&](auto value) {
+        hipLaunchKernelGGL(k_frozen_catchup<value>, dim3(h, (unsigned) b->cs.size()), dim3(256), lds, b->stream, b->d_desc, from, to, w_from, h,
                            c0->stride);
-    else
-    hipLaunchKernelGGL(k_frozen_catchup, dim3(h, (unsigned) b->cs.size()), dim3(256), lds, b->stream, b->d_desc, from, to, w_from, h,
-                       c0->stride);
+    });
     HIPCK(hipGetLastError());
     for (auto *c : b->cs) c->frozen_epoch = to;
     return 0;
@@ -1600,7 +1599,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
     }
     // Single images and groups up to 4: the carve and the energy update in one launch (k_carve_e, k_carve.hip) -- the wave that has moved
     // a row refreshes that row's energies; one dependent launch less per seam.  delta_x <= 2 (12 brightness samples per row).
-    // (value-plane carvers: the two kernels, k_carve and k_emap_update_deep)
+    // (value-plane carvers: the two kernels, k_carve and k_emap_update<.., true>)
     const bool fuse_e = p->delta_x <= 2 && vp_group <= (size_t) g_carve_fused && wnew > 1 && !reads_value(c0);
     if (fuse_e) {
         const int lag_max = n <= 4 ? FROZEN_LAG_MAX / 4 : FROZEN_LAG_MAX;
@@ -1631,16 +1630,13 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
         const int lag_max = n <= 4 ? FROZEN_LAG_MAX / 4 : FROZEN_LAG_MAX;
         if (log_index + 1 - c0->frozen_epoch > lag_max && (rc = frozen_catchup(b, log_index + 1, wnew, h))) return rc;
         const int epoch = c0->frozen_epoch;
-#define LAUNCH_EUPD_NT(N, NT) hipLaunchKernelGGL((k_emap_update<N, NT>), dim3((h + EU_ROWS - 1) / EU_ROWS, n), dim3(64), 0, b->stream, b->d_desc, k, wnew, h, stride, log_index, epoch)
+        with_form(c0, [&](auto value) {
+#define LAUNCH_EUPD_NT(N, NT) hipLaunchKernelGGL((k_emap_update<plane_nrg(value, N), NT, value>), dim3((h + EU_ROWS - 1) / EU_ROWS, n), dim3(64), 0, b->stream, b->d_desc, k, wnew, h, stride, log_index, epoch)
 #define LAUNCH_EUPD(N) do { if (p->delta_x <= 2) LAUNCH_EUPD_NT(N, 12); else if (p->delta_x <= 8) LAUNCH_EUPD_NT(N, 36); else LAUNCH_EUPD_NT(N, 68); } while (0)
-#define LAUNCH_EUPD_NT_DEEP(N, NT) hipLaunchKernelGGL((k_emap_update_deep<N, NT>), dim3((h + EU_ROWS - 1) / EU_ROWS, n), dim3(64), 0, b->stream, b->d_desc, k, wnew, h, stride, log_index, epoch)
-#define LAUNCH_EUPD_DEEP(N) do { if (p->delta_x <= 2) LAUNCH_EUPD_NT_DEEP(N, 12); else if (p->delta_x <= 8) LAUNCH_EUPD_NT_DEEP(N, 36); else LAUNCH_EUPD_NT_DEEP(N, 68); } while (0)
-        if (reads_value(c0)) { NRG_DISPATCH(p->nrg_func, LAUNCH_EUPD_DEEP) }
-        else { NRG_DISPATCH(p->nrg_func, LAUNCH_EUPD) }
-#undef LAUNCH_EUPD_DEEP
-#undef LAUNCH_EUPD_NT_DEEP
+            NRG_DISPATCH(p->nrg_func, LAUNCH_EUPD)
 #undef LAUNCH_EUPD
 #undef LAUNCH_EUPD_NT
+        });
     }
     if (full_rebuild) {
         ProfScope ps("dp_sweep", b->stream, 9.0 * wnew * h * n);
@@ -1825,20 +1821,16 @@ struct PlaneJob {
 };
 struct PlaneJobs {
     std::vector<PlaneJob> jobs;
-    std::vector<InflateDev> dev;
     std::vector<int32_t *> new_vs;          // one per root (may be null)
-    InflateDev *d_jobs = nullptr;
-    // the jobs split by the kernel that takes them: `dev` holds ch = bytes per pixel (compaction moves bytes); inflate and transpose
-    // keep 8-bit / narrow pixels on their 8-bit kernels and hand the others to k_deep.hip's (split())
-    std::vector<int> depth;                 // per job of `dev`
-    std::vector<InflateDev> dev8, devw;     // inflate: 8-bit jobs (ch = channels); transpose: pixels of <= 4 bytes; ...
-    std::vector<InflateDevX> devx;          // ... inflate: deep jobs (ch = channels)
-    InflateDev *d_jobs8 = nullptr, *d_jobsw = nullptr;
-    InflateDevX *d_jobsx = nullptr;
+    // the job table (ch = bytes per pixel), ordered by the form of the kernel that takes each job (stage()): the first n_narrow go
+    // to the pass's 8-bit kernel, the others to its deep form / k_transpose_px (lqr_pixel.h: 16-byte accesses where they fit)
+    std::vector<InflateDev> dev;
+    InflateDev *d_dev = nullptr;
+    size_t n_narrow = 0;
     bool committed = false;
     ~PlaneJobs()
     {
-        dfree(d_jobs); dfree(d_jobs8); dfree(d_jobsw); dfree(d_jobsx);
+        dfree(d_dev);
         if (committed) return;
         for (auto &j : jobs) { dfree(j.nrgb); dfree(j.nbias); dfree(j.nrig); }
         for (auto *&v : new_vs) dfree(v);
@@ -1852,34 +1844,21 @@ struct PlaneJobs {
         if (!rc && c->rig0) rc = dmalloc(&j.nrig, n1);
         jobs.push_back(j);                  // owned from here on, also when rc != 0
         if (rc) return rc;
-        dev.push_back(InflateDev{c->rgb0, vs_old, c->bias0, c->rig0, j.nrgb, nvs, j.nbias, j.nrig, (int) px_bytes(c)});
-        depth.push_back(c->depth);
+        dev.push_back(InflateDev{c->rgb0, vs_old, c->bias0, c->rig0, j.nrgb, nvs, j.nbias, j.nrig, (int) px_bytes(c), c->depth});
         return 0;
     }
-    // inflate (by_width = false): 8-bit jobs of up to 4 channels -> dev8, the others -> devx; transpose and flatten (by_width): pixels of up to 4 bytes ->
-    // dev8 (the 8-bit kernels move them as bytes / one dword), wider ones -> devw (k_deep.hip's kernels, 16-byte accesses where they fit)
-    int split(hipStream_t s, bool by_width)
+    // the table to the device.  Transpose and flatten (by_width) keep pixels of up to 4 bytes on the 8-bit kernels, which move them
+    // as bytes / one dword; inflate averages, so only 8-bit pixels of up to 4 channels stay there
+    int stage(hipStream_t s, bool by_width)
     {
-        for (size_t i = 0; i < dev.size(); i++) {
-            InflateDev d = dev[i];
-            if (by_width) { (d.ch <= 4 ? dev8 : devw).push_back(d); continue; }
-            if (depth[i] == 0 && d.ch <= 4) { dev8.push_back(d); continue; }
-            d.ch = d.ch >> depth[i];
-            devx.push_back(InflateDevX{d, depth[i]});
-        }
-        int rc;
-        if (!dev8.empty()) { if ((rc = dmalloc(&d_jobs8, dev8.size()))) return rc; HIPCK(hipMemcpyAsync(d_jobs8, dev8.data(), dev8.size() * sizeof(InflateDev), hipMemcpyHostToDevice, s)); }
-        if (!devw.empty()) { if ((rc = dmalloc(&d_jobsw, devw.size()))) return rc; HIPCK(hipMemcpyAsync(d_jobsw, devw.data(), devw.size() * sizeof(InflateDev), hipMemcpyHostToDevice, s)); }
-        if (!devx.empty()) { if ((rc = dmalloc(&d_jobsx, devx.size()))) return rc; HIPCK(hipMemcpyAsync(d_jobsx, devx.data(), devx.size() * sizeof(InflateDevX), hipMemcpyHostToDevice, s)); }
-        return 0;
-    }
-    int upload(hipStream_t s)
-    {
-        int rc = dmalloc(&d_jobs, dev.size());
+        n_narrow = std::stable_partition(dev.begin(), dev.end(), [&](const InflateDev &d) { return d.ch <= 4 && (by_width || d.depth == 0); }) - dev.begin();
+        int rc = dmalloc(&d_dev, dev.size());
         if (rc) return rc;
-        HIPCK(hipMemcpyAsync(d_jobs, dev.data(), dev.size() * sizeof(InflateDev), hipMemcpyHostToDevice, s));
+        HIPCK(hipMemcpyAsync(d_dev, dev.data(), dev.size() * sizeof(InflateDev), hipMemcpyHostToDevice, s));
         return 0;
     }
+    size_t n_wide() const { return dev.size() - n_narrow; }
+    const InflateDev *d_wide() const { return d_dev + n_narrow; }
     // after the pass has completed: the new base planes become the carvers'
     void commit()
     {
@@ -1921,12 +1900,12 @@ extern "C" int lqrhip_inflate(LqrHipBatch *b, int w0, int h0, int l, int max_lev
                 if ((rc = pj.add(a, c->vs, nullptr, (size_t) w1 * h0))) return rc;
             if ((rc = pj.add(c, c->vs, nvs, (size_t) w1 * h0))) return rc;
         }
-        if ((rc = pj.split(b->stream, false))) return rc;
+        if ((rc = pj.stage(b->stream, false))) return rc;
         const size_t lds = (size_t) ((l - max_level + 1 + 31) / 32 + 1) * sizeof(unsigned);      // one bit per level of the session (the fused self-check)
-        if (!pj.dev8.empty())
-            hipLaunchKernelGGL(k_inflate, dim3(h0, (unsigned) pj.dev8.size()), dim3(256), lds, b->stream, pj.d_jobs8, w0, w1, l, max_level, g_selfcheck ? g_dev_err : (int *) nullptr);
-        if (!pj.devx.empty())
-            hipLaunchKernelGGL(k_inflate_deep, dim3(h0, (unsigned) pj.devx.size()), dim3(256), lds, b->stream, pj.d_jobsx, w0, w1, l, max_level, g_selfcheck ? g_dev_err : (int *) nullptr);
+        if (pj.n_narrow)
+            hipLaunchKernelGGL(k_inflate<false>, dim3(h0, (unsigned) pj.n_narrow), dim3(256), lds, b->stream, pj.d_dev, w0, w1, l, max_level, g_selfcheck ? g_dev_err : (int *) nullptr);
+        if (pj.n_wide())
+            hipLaunchKernelGGL(k_inflate<true>, dim3(h0, (unsigned) pj.n_wide()), dim3(256), lds, b->stream, pj.d_wide(), w0, w1, l, max_level, g_selfcheck ? g_dev_err : (int *) nullptr);
         HIPCK(hipGetLastError());
         HIPCK(hipStreamSynchronize(b->stream));
         return check_dev_error();           // a failed level check: nothing is adopted, the host rolls the session back
@@ -1970,11 +1949,11 @@ extern "C" int lqrhip_flatten(LqrHipBatch *b, int w0, int h0, int w, int level)
                 if ((rc = pj.add(a, c->vs, nullptr, (size_t) w * h0))) return rc;
             if ((rc = pj.add(c, c->vs, nullptr, (size_t) w * h0))) return rc;
         }
-        if ((rc = pj.split(b->stream, true))) return rc;
-        if (!pj.dev8.empty())
-            hipLaunchKernelGGL(k_compact_jobs, dim3(h0, (unsigned) pj.dev8.size()), dim3(256), 0, b->stream, pj.d_jobs8, w0, w, level);
-        if (!pj.devw.empty())
-            hipLaunchKernelGGL(k_compact_jobs_wide, dim3(h0, (unsigned) pj.devw.size()), dim3(256), 0, b->stream, pj.d_jobsw, w0, w, level);
+        if ((rc = pj.stage(b->stream, true))) return rc;
+        if (pj.n_narrow)
+            hipLaunchKernelGGL(k_compact_jobs<false>, dim3(h0, (unsigned) pj.n_narrow), dim3(256), 0, b->stream, pj.d_dev, w0, w, level);
+        if (pj.n_wide())
+            hipLaunchKernelGGL(k_compact_jobs<true>, dim3(h0, (unsigned) pj.n_wide()), dim3(256), 0, b->stream, pj.d_wide(), w0, w, level);
         HIPCK(hipGetLastError());
         HIPCK(hipStreamSynchronize(b->stream));
         return 0;
@@ -1995,11 +1974,11 @@ extern "C" int lqrhip_transpose(LqrHipBatch *b, int w, int h)
             if ((rc = pj.add(c, nullptr, nullptr, (size_t) w * h))) return rc;
             HIPCK(hipMemsetAsync(c->vs, 0, (size_t) w * h * sizeof(int32_t), b->stream));   // flat carver: all zero already
         }
-        if ((rc = pj.split(b->stream, true))) return rc;
-        if (!pj.dev8.empty())
-            hipLaunchKernelGGL(k_transpose, dim3((w + 31) / 32, (h + 31) / 32, (unsigned) pj.dev8.size()), dim3(32, 8), 0, b->stream, pj.d_jobs8, w, h);
-        if (!pj.devw.empty())
-            hipLaunchKernelGGL(k_transpose_px, dim3((w + 31) / 32, (h + 31) / 32, (unsigned) pj.devw.size()), dim3(32, 8), 0, b->stream, pj.d_jobsw, w, h);
+        if ((rc = pj.stage(b->stream, true))) return rc;
+        if (pj.n_narrow)
+            hipLaunchKernelGGL(k_transpose, dim3((w + 31) / 32, (h + 31) / 32, (unsigned) pj.n_narrow), dim3(32, 8), 0, b->stream, pj.d_dev, w, h);
+        if (pj.n_wide())
+            hipLaunchKernelGGL(k_transpose_px, dim3((w + 31) / 32, (h + 31) / 32, (unsigned) pj.n_wide()), dim3(32, 8), 0, b->stream, pj.d_wide(), w, h);
         HIPCK(hipGetLastError());
         HIPCK(hipStreamSynchronize(b->stream));
         return 0;
@@ -2010,6 +1989,14 @@ extern "C" int lqrhip_transpose(LqrHipBatch *b, int w, int h)
 }
 
 // ---- read-back ---------------------------------------------------------------
+// the pixels of carver c visible at `level`, compacted into device memory (w x h0 pixels); on g_stream0, not synchronised
+static void launch_read_visible(const LqrHipCarver *c, int w0, int h0, int w, int level, uint8_t *d)
+{
+#define LAUNCH_RV(DEEP) hipLaunchKernelGGL(k_compact<DEEP>, dim3(h0), dim3(256), 0, g_stream0, c->rgb0, c->vs, (const float *) nullptr, (const float *) nullptr, \
+                                           d, (float *) nullptr, (float *) nullptr, (int32_t *) nullptr, w0, w, (int) px_bytes(c), level, 0)
+    if (px_bytes(c) > 4) LAUNCH_RV(true); else LAUNCH_RV(false);
+#undef LAUNCH_RV
+}
 extern "C" int lqrhip_read_visible(LqrHipCarver *c, int w0, int h0, int w, int level, unsigned char *out)
 {
     int rc = batch_sync_of(c);
@@ -2018,11 +2005,7 @@ extern "C" int lqrhip_read_visible(LqrHipCarver *c, int w0, int h0, int w, int l
     size_t n = (size_t) w * h0 * px_bytes(c);
     if ((rc = dmalloc(&d, n))) return rc;
     auto run = [&]() -> int {
-        if (px_bytes(c) > 4)
-            hipLaunchKernelGGL(k_compact_wide, dim3(h0), dim3(256), 0, g_stream0, c->rgb0, c->vs, d, w0, w, (int) px_bytes(c), level);
-        else
-        hipLaunchKernelGGL(k_compact, dim3(h0), dim3(256), 0, g_stream0, c->rgb0, c->vs, (const float *) nullptr, (const float *) nullptr,
-                           d, (float *) nullptr, (float *) nullptr, (int32_t *) nullptr, w0, w, (int) px_bytes(c), level, 0);
+        launch_read_visible(c, w0, h0, w, level, d);
         HIPCK(hipGetLastError());
         return d2h_staged(out, d, n);
     };
@@ -2036,11 +2019,7 @@ extern "C" int lqrhip_read_visible_device(LqrHipCarver *c, int w0, int h0, int w
 {
     int rc = batch_sync_of(c);
     if (rc) return rc;
-    if (px_bytes(c) > 4)
-        hipLaunchKernelGGL(k_compact_wide, dim3(h0), dim3(256), 0, g_stream0, c->rgb0, c->vs, (uint8_t *) device_out, w0, w, (int) px_bytes(c), level);
-    else
-    hipLaunchKernelGGL(k_compact, dim3(h0), dim3(256), 0, g_stream0, c->rgb0, c->vs, (const float *) nullptr, (const float *) nullptr,
-                       (uint8_t *) device_out, (float *) nullptr, (float *) nullptr, (int32_t *) nullptr, w0, w, (int) px_bytes(c), level, 0);
+    launch_read_visible(c, w0, h0, w, level, (uint8_t *) device_out);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(g_stream0));
     return 0;
@@ -2093,7 +2072,7 @@ extern "C" int lqrhip_read_vmap(LqrHipCarver *c, int w0, int h0, int w, int leve
     size_t n = (size_t) w * h0;
     if ((rc = dmalloc(&d, n))) return rc;
     auto run = [&]() -> int {
-        hipLaunchKernelGGL(k_compact, dim3(h0), dim3(256), 0, g_stream0, (const uint8_t *) nullptr, c->vs, (const float *) nullptr,
+        hipLaunchKernelGGL(k_compact<false>, dim3(h0), dim3(256), 0, g_stream0, (const uint8_t *) nullptr, c->vs, (const float *) nullptr,
                            (const float *) nullptr, (uint8_t *) nullptr, (float *) nullptr, (float *) nullptr, d, w0, w, c->ch, level,
                            depth);
         HIPCK(hipGetLastError());

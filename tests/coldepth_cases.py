@@ -288,7 +288,7 @@ def plane_cases():
 def boundaries(spec, K, group=1):
     """the structural boundaries of the deep kernels that running `spec` crosses, as a set of labels; from the spec alone, by liblqr's
     own bookkeeping (resize order, enl_step, the cached map, flatten before a transpose).  K: EU_ROWS, EU_LOGB, FROZEN_LAG_MAX and
-    NT (ascending [largest delta_x, samples] pairs of k_emap_update_deep's instantiations) as the sources define them; group:
+    NT (ascending [largest delta_x, samples] pairs of k_emap_update's instantiations) as the sources define them; group:
     carvers resized together (the frozen lag is FROZEN_LAG_MAX / 4 up to 4 carvers).
 
       shrink:cN enlarge:cN   a session whose carved frame spans N 256-column chunks (3 = three or more)

@@ -1,7 +1,7 @@
 """Register / scratch / LDS figures of every kernel in a built liblqr-hip.so, read from the code objects' metadata
 (the .hip_fatbin section holds one clang offload bundle per translation unit; each gfx950 code object carries an
 amdhsa metadata note with .vgpr_count, .sgpr_count, .vgpr_spill_count, .private_segment_fixed_size, ... per kernel).
-Used by tests/test_kernel_budgets.py; `python tests/kernel_meta.py [lib.so]` prints the table."""
+Used by tests/test_kernel_budgets.py and scripts/kernel_diff.py; `python tests/kernel_meta.py [lib.so]` prints the table."""
 import os
 import re
 import shutil
@@ -19,24 +19,34 @@ def tools_available():
     return all(os.path.exists(os.path.join(LLVM_BIN, t)) for t in ("clang-offload-bundler", "llvm-readelf", "llvm-objdump")) and shutil.which("objcopy") and shutil.which("c++filt")
 
 
+def _demangle(mangled):
+    """kernel names without 'void ' and the parameter list, in the order given"""
+    names = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True, check=True).stdout.split("\n")
+    return [re.sub(r"\(.*", "", re.sub(r"^void ", "", n)) for n in names[:len(mangled)]]
+
+
+def _code_objects(so_path, td):
+    """the gfx950 code object of every translation unit of the library, unbundled into directory td: paths"""
+    fat = os.path.join(td, "fat.bin")
+    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", so_path, fat])
+    blob = open(fat, "rb").read()
+    starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
+    assert starts, "no offload bundle in %s" % so_path
+    for i, a in enumerate(starts):
+        b = starts[i + 1] if i + 1 < len(starts) else len(blob)
+        piece, co = os.path.join(td, "b%d.bin" % i), os.path.join(td, "b%d.co" % i)
+        open(piece, "wb").write(blob[a:b])
+        subprocess.check_call([os.path.join(LLVM_BIN, "clang-offload-bundler"), "--unbundle", "--type=o",
+                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + piece, "--output=" + co])
+        if os.path.getsize(co):
+            yield co
+
+
 def kernels(so_path):
     """{demangled kernel name (without the parameter list): {key: int}}"""
-    out = {}
+    mangled = []
     with tempfile.TemporaryDirectory() as td:
-        fat = os.path.join(td, "fat.bin")
-        subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", so_path, fat])
-        blob = open(fat, "rb").read()
-        starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
-        assert starts, "no offload bundle in %s" % so_path
-        mangled = []
-        for i, a in enumerate(starts):
-            b = starts[i + 1] if i + 1 < len(starts) else len(blob)
-            piece, co = os.path.join(td, "b%d.bin" % i), os.path.join(td, "b%d.co" % i)
-            open(piece, "wb").write(blob[a:b])
-            subprocess.check_call([os.path.join(LLVM_BIN, "clang-offload-bundler"), "--unbundle", "--type=o",
-                                   "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + piece, "--output=" + co])
-            if os.path.getsize(co) == 0:
-                continue
+        for co in _code_objects(so_path, td):
             notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
             for blk in re.split(r"\n  - \.agpr_count", notes)[1:]:
                 blk = ".agpr_count" + blk
@@ -46,56 +56,43 @@ def kernels(so_path):
                     d[k] = int(m.group(1)) if m else 0
                 name = re.search(r"\.name:\s+(\S+)", blk).group(1)
                 mangled.append((name, d))
-        names = subprocess.run(["c++filt"], input="\n".join(n for n, _ in mangled), capture_output=True, text=True, check=True).stdout.split("\n")
-        for (_, d), n in zip(mangled, names):
-            n = re.sub(r"^void ", "", n)
-            n = re.sub(r"\(.*", "", n)
-            out[n] = d
-    return out
+    return dict(zip(_demangle([n for n, _ in mangled]), (d for _, d in mangled)))
 
 
-def instruction_counts(so_path, mnemonics=("s_nop", "v_readfirstlane_b32", "flat_load_dword", "flat_store_dword")):
-    """{demangled kernel name: {mnemonic: count}} from the disassembly of every gfx950 code object in the library"""
-    out = {}
+def disassembly(so_path):
+    """{demangled kernel name: [instruction, ...]} of every gfx950 code object in the library: mnemonic and operands as llvm-objdump
+    prints them, without the address / encoding comment (branch targets are relative, so equal code reads equal wherever it lies)"""
+    text = {}
     with tempfile.TemporaryDirectory() as td:
-        fat = os.path.join(td, "fat.bin")
-        subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", so_path, fat])
-        blob = open(fat, "rb").read()
-        starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
-        counts = {}
-        for i, a in enumerate(starts):
-            b = starts[i + 1] if i + 1 < len(starts) else len(blob)
-            piece, co = os.path.join(td, "b%d.bin" % i), os.path.join(td, "b%d.co" % i)
-            open(piece, "wb").write(blob[a:b])
-            subprocess.check_call([os.path.join(LLVM_BIN, "clang-offload-bundler"), "--unbundle", "--type=o",
-                                   "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + piece, "--output=" + co])
-            if os.path.getsize(co) == 0:
-                continue
+        for co in _code_objects(so_path, td):
             dis = subprocess.run([os.path.join(LLVM_BIN, "llvm-objdump"), "-d", "--no-show-raw-insn", co], capture_output=True, text=True, check=True).stdout
             cur = None
             for line in dis.split("\n"):
                 m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
                 if m:
-                    cur = counts.setdefault(m.group(1), dict.fromkeys(mnemonics, 0))
+                    cur = text.setdefault(m.group(1), [])
                     continue
-                if cur is None:
-                    continue
-                t = line.split()
-                if not t:
-                    continue
-                if t[0] in cur:
-                    cur[t[0]] += 1
-                # (ADVICE r5: every width of FLAT access counts -- flat_load_dwordx2, _ubyte, _short ... -- under the dword key's family)
-                elif t[0].startswith("flat_load_") and "flat_load_dword" in cur:
-                    cur["flat_load_dword"] += 1
-                elif t[0].startswith("flat_store_") and "flat_store_dword" in cur:
-                    cur["flat_store_dword"] += 1
-        mangled = sorted(counts)
-        names = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True, check=True).stdout.split("\n")
-        for mn, n in zip(mangled, names):
-            n = re.sub(r"^void ", "", n)
-            n = re.sub(r"\(.*", "", n)
-            out[n] = counts[mn]
+                ins = " ".join(line.split("//")[0].split())
+                if cur is not None and ins:
+                    cur.append(ins)
+    mangled = sorted(text)
+    return dict(zip(_demangle(mangled), (text[m] for m in mangled)))
+
+
+def instruction_counts(so_path, mnemonics=("s_nop", "v_readfirstlane_b32", "flat_load_dword", "flat_store_dword")):
+    """{demangled kernel name: {mnemonic: count}} from the disassembly of every gfx950 code object in the library"""
+    out = {}
+    for name, ins in disassembly(so_path).items():
+        cur = out[name] = dict.fromkeys(mnemonics, 0)
+        for line in ins:
+            t = line.split()[0]
+            if t in cur:
+                cur[t] += 1
+            # (ADVICE r5: every width of FLAT access counts -- flat_load_dwordx2, _ubyte, _short ... -- under the dword key's family)
+            elif t.startswith("flat_load_") and "flat_load_dword" in cur:
+                cur["flat_load_dword"] += 1
+            elif t.startswith("flat_store_") and "flat_store_dword" in cur:
+                cur["flat_store_dword"] += 1
     return out
 
 

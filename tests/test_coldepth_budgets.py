@@ -1,7 +1,8 @@
-"""Register budgets of the colour-depth kernels (csrc/k_deep.hip), checked at build time from the library's code-object
-metadata (tests/kernel_meta.py), as tests/test_kernel_budgets.py does for the 8-bit ones: none may use scratch, the energy
-update next to the seam keeps the 8 waves per SIMD of its 8-bit form, and every kernel the shim launches for a deep carver
-is there under its name."""
+"""Register budgets of the kernels a colour-depth carver runs -- the value / deep forms (csrc/lqr_pixel.h) of the kernels in
+csrc/k_energy.hip and csrc/k_oneoff.hip -- checked at build time from the library's code-object metadata (tests/kernel_meta.py),
+as tests/test_kernel_budgets.py does for the 8-bit ones: none may use scratch, the energy update next to the seam keeps the
+8 waves per SIMD of its 8-bit form, and every kernel the shim launches for a deep carver is there under its name, and no other:
+the value forms exist for energies 0, 1, 2 and 6 (on the value plane 3, 4, 5 are 0, 1, 2; plane_nrg in csrc/lqr_shim.hip)."""
 import os
 import re
 
@@ -14,16 +15,16 @@ LIB = os.environ.get("LQR_BUDGET_LIB") or os.path.join(ROOT, "gimp-lqr-plugin_am
 
 # (regular expression on the demangled name, max VGPRs + AGPRs, instances expected, why)
 BUDGETS = [
-    (r"^k_wk_init_deep<[123]>$", 48, 3, "E1 on the value plane: a streaming pass"),
-    (r"^k_wk_init_visible_deep<[123]>$", 64, 3, "E1 on a multi-size image: one block per row"),
-    (r"^k_emap_full_deep<[0-6]>$", 32, 7, "E3/E4: one pixel per thread"),
-    (r"^k_emap_update_deep<[0-6], 12>$", 64, 7, "delta_x <= 2: 8 waves per SIMD, as k_emap_update<N, 12>"),
-    (r"^k_emap_update_deep<[0-6], (36|68)>$", 512, 14, "delta_x 3 .. 16: the 8-bit kernel's staging, 8-byte samples"),
-    (r"^k_frozen_catchup_deep$", 48, 1, "the frozen value plane brought forward"),
-    (r"^k_inflate_deep$", 64, 1, "E14 with the depth's averaging and the fused level check"),
+    (r"^k_wk_init<PixValue<[123]> ?>$", 48, 3, "E1 on the value plane: a streaming pass"),
+    (r"^k_wk_init_visible<PixValue<[123]> ?>$", 64, 3, "E1 on a multi-size image: one block per row"),
+    (r"^k_emap_full<[0-6], true>$", 32, 4, "E3/E4: one pixel per thread"),
+    (r"^k_emap_update<[0-6], 12, true>$", 64, 4, "delta_x <= 2: 8 waves per SIMD, as k_emap_update<N, 12, false>"),
+    (r"^k_emap_update<[0-6], (36|68), true>$", 512, 8, "delta_x 3 .. 16: the 8-bit kernel's staging, 8-byte samples"),
+    (r"^k_frozen_catchup<true>$", 48, 1, "the frozen value plane brought forward"),
+    (r"^k_inflate<true>$", 64, 1, "E14 with the depth's averaging and the fused level check"),
     (r"^k_transpose_px$", 48, 1, "E11 for pixels wider than 4 bytes"),
-    (r"^k_compact_wide$", 64, 1, "E12 read-out of pixels wider than 4 bytes"),
-    (r"^k_compact_jobs_wide$", 64, 1, "E11 flatten of pixels wider than 4 bytes"),
+    (r"^k_compact<true>$", 64, 1, "E12 read-out of pixels wider than 4 bytes"),
+    (r"^k_compact_jobs<true>$", 64, 1, "E11 flatten of pixels wider than 4 bytes"),
 ]
 
 

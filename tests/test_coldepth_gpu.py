@@ -185,7 +185,7 @@ SMALL, WIDE = (44, 30, 38, 31, 26), (300, 70, 262, 225, 64)
 def test_energy_function_changed_between_resizes(eng, first, second, size):
     """brightness and luma are different read values: a deep carver whose energy function changes kind between two resizes
     lays its value plane out again (lift identity against the 8-bit oracle, which reads pixels afresh every time).  wide: the
-    carver that is laid out again has a base layout of 338 columns and is not flat (k_wk_init_visible_deep over two chunks), and
+    carver that is laid out again has a base layout of 338 columns and is not flat (k_wk_init_visible<PixValue<D>> over two chunks), and
     the session that follows is longer than the frozen lag; 16I as well as 64F"""
     orc = L.oracle_api()
     w, h, w1, w2, h2 = size

@@ -1,6 +1,6 @@
 """Deep-colour carvers (16I, 32F, 64F) past the sizes where their kernels change structure: base layouts of more than 256 and 512
-columns (second and third chunk of the rank loops of k_wk_init_visible_deep, k_frozen_catchup_deep, k_inflate_deep, k_compact_wide,
-k_compact_jobs_wide), more than 62 and 124 rows (blocks of k_emap_update_deep), sessions longer than the frozen lag (32 seams up to
+columns (second and third chunk of the rank loops of k_wk_init_visible<PixValue<D>>, k_frozen_catchup<true>, k_inflate<true>, k_compact<true>,
+k_compact_jobs<true>), more than 62 and 124 rows (blocks of k_emap_update<N, NT, true>), sessions longer than the frozen lag (32 seams up to
 four carvers, 128 beyond: catch-up in mid-session, log walks from an epoch > 0), delta_x 3 .. 10 (the 36- and 68-sample
 instantiations).  tests/test_coldepth_abi.py asserts from the specs that the vectors cross each of these.  Every comparison is
 bit for bit.
@@ -120,7 +120,7 @@ def against_vector(c, z, what):
 
 @pytest.mark.parametrize("depth,n", [(1, 5), (1, 8), (2, 5), (3, 5)])
 def test_family_carved_as_one_group_equals_each_vector(eng, depth, n):
-    """140 seams in a group of 5 (8): past the lag of 128 such a group has; 8: k_band_levels feeding k_carve + k_emap_update_deep"""
+    """140 seams in a group of 5 (8): past the lag of 128 such a group has; 8: k_band_levels feeding k_carve + k_emap_update<N, NT, true>"""
     names = CD.family_names(depth)[:n]
     loaded = [load(x) for x in names]
     spec = loaded[0][0]
@@ -155,7 +155,7 @@ def test_mixed_list_of_all_four_depths_at_one_geometry(eng):
 
 @pytest.mark.parametrize("depth", [1, 2, 3])
 def test_batch_then_enlarge_then_flatten_equals_single_carvers(eng, depth):
-    """a group of 5 wide deep carvers through shrink (read-out: k_compact_jobs_wide), enlarge (k_inflate_deep with five jobs) and flatten"""
+    """a group of 5 wide deep carvers through shrink (read-out: k_compact_jobs<true>), enlarge (k_inflate<true> with five jobs) and flatten"""
     rng = np.random.default_rng(300 + depth)
     imgs = [CD.to_depth(rng, CD.base_image(rng, 300, 24, 3), depth, edge=(i % 2 == 0)) for i in range(5)]
 
@@ -241,7 +241,7 @@ def test_injected_fault_in_a_wide_session_that_is_not_flat_is_rolled_back_and_ex
     """lqrhip_debug_inject(3, 40, 1): a seam-log entry out of the frame at seam step 40 of the first session that has one.  The
     vector's first session has 38 seams, so the fault falls into the second (42 seams), after its catch-up in mid-session, on a
     carver with a base layout of more than 256 (512) columns that is not flat: the levels are rolled back and the value plane laid
-    out again from the visible pixels (k_wk_init_visible_deep over more than one chunk) for the session carved again"""
+    out again from the visible pixels (k_wk_init_visible<PixValue<D>> over more than one chunk) for the session carved again"""
     lb = eng.lib
     lb.lqrhip_debug_inject.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lb.lqrhip_fault_stats.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
@@ -262,7 +262,7 @@ def test_injected_fault_in_a_wide_session_that_is_not_flat_is_rolled_back_and_ex
 
 # ---- 8. full size -------------------------------------------------------------------------------------------------------------------
 def fullsize_lift_check():
-    """3840 x 2160 RGBA -> 3640: parallel backtrack, k_carve and k_emap_update_deep on 35 blocks of rows; 265 MB of 64F pixels.
+    """3840 x 2160 RGBA -> 3640: parallel backtrack, k_carve and k_emap_update<N, 12, true> on 35 blocks of rows; 265 MB of 64F pixels.
     One deep carver at a time"""
     import datasets as D
     eng = L.bind_coldepth(L.engine_api())

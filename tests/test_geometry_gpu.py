@@ -159,7 +159,7 @@ def test_an_injected_fault_in_a_16384_column_session_is_redone_on_the_recovery_k
 
 def test_a_16_bit_lift_of_a_16384_column_image_carves_the_8_bit_seams(oracle, lib):
     """coldepth_cases' lift identity at the widest frame: the 16I image v * 257 carves the seams of v, its pixels are the 8-bit
-    result lifted the same way (the value-plane kernels: k_carve + k_emap_update_deep, k_frozen_catchup_deep)"""
+    result lifted the same way (the value-plane kernels: k_carve + k_emap_update<N, NT, true>, k_frozen_catchup<true>)"""
     c = G.BY_NAME["w16384x16_lift16"]
     eng = L.engine_coldepth_api()
     img, kw = G.image(c), G.run_kw(c)

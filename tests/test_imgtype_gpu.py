@@ -182,7 +182,7 @@ def batch_against_singles(eng, inputs, steps, nrg=1):
 
 @pytest.mark.parametrize("n,depth,ch,ops", [(5, 0, 5, []), (8, 2, 7, [{"alpha": 5}, {"black": 2}]), (5, 1, 4, [IT.CMYK]), (8, 0, 6, [])])
 def test_same_shape_typed_carvers_as_a_group(eng, n, depth, ch, ops):
-    """shrink (read-out of odd pixels by k_compact_wide), then enlarge (k_inflate_deep with n jobs), past 256 columns"""
+    """shrink (read-out of odd pixels by k_compact<true>), then enlarge (k_inflate<true> with n jobs), past 256 columns"""
     rng = np.random.default_rng(500 + n + depth)
     inputs = [(CD.to_depth(rng, CD.base_image(rng, 280, 20, ch), depth, edge=(i % 2 == 0)), depth, ops) for i in range(n)]
     batch_against_singles(eng, inputs, [(246, 20), (300, 20)])
@@ -209,7 +209,7 @@ def test_injected_fault_on_an_8i_cmyka_carver_that_is_not_flat_is_rolled_back_an
     """lqrhip_debug_inject(3, 40, 1): a seam-log entry out of the frame at seam step 40.  The vector's first session has 38 seams, so
     the fault falls into the second (42 seams, after the type change that laid the planes out again), on a carver of 5-byte pixels
     with a base layout of 378 columns that is not flat: the levels are rolled back, the value plane is laid out again from the
-    visible pixels (k_wk_init_visible_deep<0> over two chunks) and the session carved again.  The type is not session state"""
+    visible pixels (k_wk_init_visible<PixValue<0>> over two chunks) and the session carved again.  The type is not session state"""
     lb = eng.lib
     lb.lqrhip_debug_inject.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lb.lqrhip_fault_stats.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]

@@ -35,7 +35,7 @@ BUDGETS = [
     (r"^k_vp_solve<", 160, 0, 0, "one workgroup per image; a stage's loads are all issued before the first is stored (12 x 16 bytes in registers)"),
     (r"^k_vpath1<1>$", 192, 0, 0, "one wave chases, 2 waves per SIMD of the 4-wave workgroup"),
     (r"^k_vpath1<[234567]>$", 128, 0, 0, "shorter chunks"),
-    (r"^k_emap_update<\d, 12>$", 64, 0, 0, "delta_x <= 2: 8 waves per SIMD"),
+    (r"^k_emap_update<\d, 12, (true|false)>$", 64, 0, 0, "delta_x <= 2: 8 waves per SIMD, packed pixels and value plane alike"),
     (r"^k_dp_tile<", 96, 0, 0, "one wave per tile, 5 per SIMD"),
 ]
 # kernels that are allowed to use scratch at all (slow paths for rows wider than 8192 px / known, outside the row loops)
