@@ -423,14 +423,11 @@ __global__ __launch_bounds__(VPATH_THREADS) void k_vp_solve(const DevCarver *cs,
     publish_side(c, org, total, w, h, lane, moved_unit);
 }
 
-// ---- the instantiations the shim launches (lqr_kernels.h declares them)
-#define INST_VP(D) template __global__ void k_vp_maps<D>(const DevCarver *, int, int, int); \
+// ---- the instantiations the shim launches (lqr_kernels.h lists them)
+#define INST(D) template __global__ void k_vp_maps<D>(const DevCarver *, int, int, int); \
     template __global__ void k_vp_solve<D>(const DevCarver *, int, int, int, int, int, int);
-INST_VP(1) INST_VP(2) INST_VP(3) INST_VP(4) INST_VP(5) INST_VP(6) INST_VP(7) INST_VP(8) INST_VP(9) INST_VP(10)
-template __global__ void k_vpath1<1>(const DevCarver *, int, int, int, int, int, int);
-template __global__ void k_vpath1<2>(const DevCarver *, int, int, int, int, int, int);
-template __global__ void k_vpath1<3>(const DevCarver *, int, int, int, int, int, int);
-template __global__ void k_vpath1<4>(const DevCarver *, int, int, int, int, int, int);
-template __global__ void k_vpath1<5>(const DevCarver *, int, int, int, int, int, int);
-template __global__ void k_vpath1<6>(const DevCarver *, int, int, int, int, int, int);
-template __global__ void k_vpath1<7>(const DevCarver *, int, int, int, int, int, int);
+K_VP_FORMS(INST)
+#undef INST
+#define INST(D) template __global__ void k_vpath1<D>(const DevCarver *, int, int, int, int, int, int);
+K_VPATH1_FORMS(INST)
+#undef INST

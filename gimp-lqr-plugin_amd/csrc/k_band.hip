@@ -836,11 +836,13 @@ __global__ __launch_bounds__(128 * NW) void k_band_update_tw(const DevCarver *cs
 }
 
 
-// ---- the instantiations the shim launches (lqr_kernels.h declares them)
-#define INST_SWEEP(P) template __global__ void k_dp_sweep<P, false, DP_THREADS>(const DevCarver *, DpK, int, int, int, int); template __global__ void k_dp_sweep<P, true, DP_THREADS>(const DevCarver *, DpK, int, int, int, int); \
+// ---- the instantiations the shim launches (lqr_kernels.h lists them)
+#define INST(P) template __global__ void k_dp_sweep<P, false, DP_THREADS>(const DevCarver *, DpK, int, int, int, int); template __global__ void k_dp_sweep<P, true, DP_THREADS>(const DevCarver *, DpK, int, int, int, int); \
     template __global__ void k_dp_sweep<P, true, 256>(const DevCarver *, DpK, int, int, int, int);
-INST_SWEEP(1) INST_SWEEP(2) INST_SWEEP(4) INST_SWEEP(8) INST_SWEEP(16)
-#define INST_BAND(LRV, RIGV) template __global__ void k_band_update_tw<4, LRV, RIGV>(const DevCarver *, DpK, int, int, int, int *); \
+K_DP_SWEEP_PXT_FORMS(INST)
+#undef INST
+#define INST(LRV, RIGV) template __global__ void k_band_update_tw<4, LRV, RIGV>(const DevCarver *, DpK, int, int, int, int *); \
     template __global__ void k_band_update_mw<2, 8, 8, LRV, RIGV>(const DevCarver *, DpK, int, int, int); \
     template __global__ void k_band_update_mw<2, 16, 8, LRV, RIGV>(const DevCarver *, DpK, int, int, int);
-INST_BAND(false, false) INST_BAND(false, true) INST_BAND(true, false) INST_BAND(true, true)
+K_LR_RIG_FORMS(INST)
+#undef INST

@@ -321,7 +321,8 @@ __global__ __launch_bounds__(256) void k_carve_e(const DevCarver *cs, DpK p, int
     }
 }
 
-// ---- the instantiations the shim launches (lqr_kernels.h declares them)
+// ---- the instantiations the shim launches (lqr_kernels.h lists them)
 // (k_carve is not a template)
-#define INST_CE(N) template __global__ void k_carve_e<N>(const DevCarver *, DpK, int, int, int, int, int, int);
-INST_CE(0) INST_CE(1) INST_CE(2) INST_CE(3) INST_CE(4) INST_CE(5) INST_CE(6)
+#define INST(N) template __global__ void k_carve_e<N>(const DevCarver *, DpK, int, int, int, int, int, int);
+K_CARVE_E_FORMS(INST)
+#undef INST

@@ -208,16 +208,15 @@ __global__ __launch_bounds__(256) void k_frozen_catchup(const DevCarver *cs, int
 }
 
 
-// ---- the instantiations the shim launches (lqr_kernels.h declares them).  The value forms exist for energies 0, 1, 2 and 6 only:
+// ---- the instantiations the shim launches (lqr_kernels.h lists them).  The value forms exist for energies 0, 1, 2 and 6 only:
 // the plane already holds brightness or luma, so 3, 4, 5 would be the code of 0, 1, 2 again (plane_nrg in lqr_shim.hip)
 #define INST_WK(FORM) template __global__ void k_wk_init<FORM>(const DevCarver *, int, int, int, FORM::Arg); \
     template __global__ void k_wk_init_visible<FORM>(const DevCarver *, int, int, int, FORM::Arg);
 INST_WK(PixPacked) INST_WK(PixValue<0>) INST_WK(PixValue<1>) INST_WK(PixValue<2>) INST_WK(PixValue<3>)
-#define INST_EMAP(N, V) template __global__ void k_emap_full<N, V>(const DevCarver *, DpK, int, int, int); \
-    template __global__ void k_emap_update<N, 12, V>(const DevCarver *, DpK, int, int, int, int, int); \
-    template __global__ void k_emap_update<N, 36, V>(const DevCarver *, DpK, int, int, int, int, int); \
-    template __global__ void k_emap_update<N, 68, V>(const DevCarver *, DpK, int, int, int, int, int);
-INST_EMAP(0, false) INST_EMAP(1, false) INST_EMAP(2, false) INST_EMAP(3, false) INST_EMAP(4, false) INST_EMAP(5, false) INST_EMAP(6, false)
-INST_EMAP(0, true) INST_EMAP(1, true) INST_EMAP(2, true) INST_EMAP(6, true)
+#define INST_U(NT, N, V) template __global__ void k_emap_update<N, NT, V>(const DevCarver *, DpK, int, int, int, int, int);
+#define INST(N, V) template __global__ void k_emap_full<N, V>(const DevCarver *, DpK, int, int, int); K_EMAP_UPDATE_NT_FORMS(INST_U, N, V)
+K_EMAP_FORMS(INST)
+#undef INST
+#undef INST_U
 template __global__ void k_frozen_catchup<false>(const DevCarver *, int, int, int, int, int);
 template __global__ void k_frozen_catchup<true>(const DevCarver *, int, int, int, int, int);

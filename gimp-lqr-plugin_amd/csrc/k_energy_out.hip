@@ -192,10 +192,6 @@ __global__ __launch_bounds__(256) void k_energy_out(const DevCarver *cs, int w, 
     });
 }
 
-#define EO_INST(TYPE) \
-    template __global__ void k_energy_out<TYPE, 0>(const DevCarver *, int, int, int, int, const float *, int, uint8_t *); \
-    template __global__ void k_energy_out<TYPE, 1>(const DevCarver *, int, int, int, int, const float *, int, uint8_t *); \
-    template __global__ void k_energy_out<TYPE, 2>(const DevCarver *, int, int, int, int, const float *, int, uint8_t *); \
-    template __global__ void k_energy_out<TYPE, 3>(const DevCarver *, int, int, int, int, const float *, int, uint8_t *);
-EO_INST(0) EO_INST(1) EO_INST(2) EO_INST(3) EO_INST(4) EO_INST(5) EO_INST(6)
-#undef EO_INST
+#define INST(TYPE, D) template __global__ void k_energy_out<TYPE, D>(const DevCarver *, int, int, int, int, const float *, int, uint8_t *);
+K_ENERGY_OUT_FORMS(INST)
+#undef INST

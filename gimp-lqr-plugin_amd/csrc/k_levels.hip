@@ -511,13 +511,7 @@ extern "C" int lqrhip_band_levels_stats(unsigned long long *out, int reset)
     return 0;
 }
 
-// ---- the instantiations the shim launches (lqr_kernels.h declares them)
-#define INST_LV(...) template __global__ void k_band_levels<__VA_ARGS__>(DevCarver *, DpK, int, int, int, unsigned long long *, int, int *, int, int);
-#define INST_LV_LR(LRV) INST_LV(LRV, false, 1, false) INST_LV(LRV, true, 1, false) INST_LV(LRV, true, 1, true) \
-    INST_LV(LRV, false, 2, false) INST_LV(LRV, true, 2, false) INST_LV(LRV, true, 2, true) \
-    INST_LV(LRV, false, 3, false) INST_LV(LRV, true, 3, false) INST_LV(LRV, true, 3, true) \
-    INST_LV(LRV, false, 4, false) INST_LV(LRV, true, 4, false) INST_LV(LRV, true, 4, true) \
-    INST_LV(LRV, true, 5, false) INST_LV(LRV, true, 5, true) INST_LV(LRV, true, 6, false) INST_LV(LRV, true, 6, true) \
-    INST_LV(LRV, true, 7, false) INST_LV(LRV, true, 7, true) INST_LV(LRV, true, 8, false) INST_LV(LRV, true, 8, true) \
-    INST_LV(LRV, true, 9, false) INST_LV(LRV, true, 9, true) INST_LV(LRV, true, 10, false) INST_LV(LRV, true, 10, true)
-INST_LV_LR(false) INST_LV_LR(true)
+// ---- the instantiations the shim launches (lqr_kernels.h lists them)
+#define INST(...) template __global__ void k_band_levels<__VA_ARGS__>(DevCarver *, DpK, int, int, int, unsigned long long *, int, int *, int, int);
+K_BAND_LEVELS_FORMS(INST)
+#undef INST

@@ -495,19 +495,10 @@ extern "C" void lqrhip_dp_tile_debug(int v) { if (lqrhip_init() < 0) return; (vo
 extern "C" int lqrhip_tile_timing(unsigned long long *out) { (void) hipDeviceSynchronize(); return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tile_dbg), sizeof(unsigned long long) * 32) == hipSuccess ? 0 : -1; }
 #endif
 
-// ---- the instantiations the shim launches (lqr_kernels.h declares them)
-#define INST_TILE(LRV, RIGV) template __global__ void k_dp_tile<LRV, RIGV>(const DevCarver *, DpK, int, int, int, int);
-INST_TILE(false, false) INST_TILE(false, true) INST_TILE(true, false) INST_TILE(true, true)
-#define INST_P(...) template __global__ void k_dp_tile_p<__VA_ARGS__>(DevCarver *, DpK, int, int, int, unsigned long long *, int, int *);
-#define INST_P_WIDE(LRV, RIGV, UPD) INST_P(2, LRV, RIGV, UPD, 1, false, 24)
-#define INST_P_LR(LRV, UPD) INST_P(4, LRV, false, UPD) INST_P(4, LRV, true, UPD) INST_P(2, LRV, false, UPD) INST_P(2, LRV, true, UPD) \
-    INST_P(2, LRV, true, UPD, 1, true) \
-    INST_P(2, LRV, false, UPD, 2, false) INST_P(2, LRV, true, UPD, 2, false) INST_P(2, LRV, true, UPD, 2, true) \
-    INST_P(2, LRV, false, UPD, 3, false) INST_P(2, LRV, true, UPD, 3, false) INST_P(2, LRV, true, UPD, 3, true) \
-    INST_P(2, LRV, false, UPD, 4, false) INST_P(2, LRV, true, UPD, 4, false) INST_P(2, LRV, true, UPD, 4, true) \
-    INST_P(2, LRV, true, UPD, 5, false) INST_P(2, LRV, true, UPD, 5, true) INST_P(2, LRV, true, UPD, 6, false) INST_P(2, LRV, true, UPD, 6, true) \
-    INST_P(2, LRV, true, UPD, 7, false) INST_P(2, LRV, true, UPD, 7, true) INST_P(2, LRV, true, UPD, 8, false) INST_P(2, LRV, true, UPD, 8, true) \
-    INST_P(2, LRV, true, UPD, 9, false) INST_P(2, LRV, true, UPD, 9, true) INST_P(2, LRV, true, UPD, 10, false) INST_P(2, LRV, true, UPD, 10, true)
-INST_P_LR(false, false) INST_P_LR(false, true) INST_P_LR(true, false) INST_P_LR(true, true)
-INST_P_WIDE(false, false, false) INST_P_WIDE(false, true, false) INST_P_WIDE(true, false, false) INST_P_WIDE(true, true, false)
-INST_P_WIDE(false, false, true) INST_P_WIDE(false, true, true) INST_P_WIDE(true, false, true) INST_P_WIDE(true, true, true)
+// ---- the instantiations the shim launches (lqr_kernels.h lists them)
+#define INST(LRV, RIGV) template __global__ void k_dp_tile<LRV, RIGV>(const DevCarver *, DpK, int, int, int, int);
+K_LR_RIG_FORMS(INST)
+#undef INST
+#define INST(CLASS, ...) template __global__ void k_dp_tile_p<__VA_ARGS__>(DevCarver *, DpK, int, int, int, unsigned long long *, int, int *);
+K_DP_TILE_P_FORMS(INST)
+#undef INST

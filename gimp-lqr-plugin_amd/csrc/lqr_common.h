@@ -280,19 +280,6 @@ __device__ __forceinline__ float energy_at(const GCarver &c, const DpK &p, int s
     return e;
 }
 
-// resolve the run-time energy selector to a kernel instantiation
-#define NRG_DISPATCH(nrg, LAUNCH)                 \
-    switch (nrg) {                                \
-        case 0: { LAUNCH(0); break; }             \
-        case 1: { LAUNCH(1); break; }             \
-        case 2: { LAUNCH(2); break; }             \
-        case 3: { LAUNCH(3); break; }             \
-        case 4: { LAUNCH(4); break; }             \
-        case 5: { LAUNCH(5); break; }             \
-        default: { LAUNCH(6); break; }            \
-    }
-
-
 #define DPP_WAVE_SHL1 0x130
 #define DPP_WAVE_SHR1 0x138
 

@@ -1,7 +1,9 @@
 // lqr_kernels.h -- every kernel of the engine, declared for the host shim (lqr_shim.hip), which launches them, and included by
-// the file that defines each (so that declaration and definition cannot drift apart).  The template kernels are instantiated
-// explicitly at the end of their files for exactly the parameter sets the shim launches; a missing one is a link error
-// (-Wl,-z,defs in the Makefile).
+// the file that defines each (so that declaration and definition cannot drift apart).  A template family with more than one
+// instantiation has its set written ONCE, as an X-macro list (K_*_FORMS) next to its declaration.  Three things derive from it: the
+// explicit instantiations at the end of the family's k_*.hip, the shim's launch (it picks the entry that equals the run-time values,
+// and refuses values no entry has) and, for the two spinning families, the occupancy queries behind the residency bounds
+// (dpp_resident_workgroups) -- so a kernel that can be launched cannot be missing from either.
 #pragma once
 #include "lqr_common.h"
 #include "lqr_pixel.h"
@@ -12,6 +14,9 @@
 // k_energy.hip
 template <class FORM> __global__ void k_wk_init(const DevCarver *cs, int w, int h, int stride, typename FORM::Arg a);
 template <class FORM> __global__ __launch_bounds__(256) void k_wk_init_visible(const DevCarver *cs, int w0, int h, int stride, typename FORM::Arg a);
+// X(NRG, VALUE): k_emap_full, and k_emap_update at each sample count.  The value forms exist for energies 0, 1, 2 and 6 only (plane_nrg in lqr_shim.hip)
+#define K_EMAP_FORMS(X) X(0, false) X(1, false) X(2, false) X(3, false) X(4, false) X(5, false) X(6, false) X(0, true) X(1, true) X(2, true) X(6, true)
+#define K_EMAP_UPDATE_NT_FORMS(X, ...) X(12, __VA_ARGS__) X(36, __VA_ARGS__) X(68, __VA_ARGS__)      // brightness samples per row (eu_samples in lqr_shim.hip)
 template <int NRG, bool VALUE> __global__ void k_emap_full(const DevCarver *cs, DpK p, int w, int h, int stride);
 __global__ void k_mask_add(float *plane, int w0, const uint8_t *mask, int channels, int mw, int x0, int y0, int x1, int y1,
                            int nx, int ny, int transposed, int is_rig, int bias_factor);
@@ -20,6 +25,8 @@ template <bool VALUE> __global__ __launch_bounds__(256) void k_frozen_catchup(co
 
 // k_backtrack.hip
 __global__ __launch_bounds__(VPATH_THREADS) void k_vpath(const DevCarver *cs, int w, int h, int stride, int lr, int delta, int log_index, int moved_unit);
+#define K_VPATH1_FORMS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
+#define K_VP_FORMS(X) K_VPATH1_FORMS(X) X(8) X(9) X(10)         // k_vp_maps and k_vp_solve: delta_x 1 .. LQR_FAST_MAX_DELTA
 template <int DELTA> __global__ __launch_bounds__(VPATH_THREADS) void k_vpath1(const DevCarver *cs, int w, int h, int stride, int lr, int log_index, int moved_unit);
 
 template <int DELTA> __global__ __launch_bounds__(256) void k_vp_maps(const DevCarver *cs, int w, int h, int stride);
@@ -27,9 +34,12 @@ template <int DELTA> __global__ __launch_bounds__(VPATH_THREADS) void k_vp_solve
 
 // k_carve.hip
 __global__ __launch_bounds__(256) void k_carve(const DevCarver *cs, int w, int h, int stride, int delta, int move_dp);
+#define K_CARVE_E_FORMS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6)      // LqrEnergyFuncBuiltinType
 template <int NRG> __global__ __launch_bounds__(256) void k_carve_e(const DevCarver *cs, DpK p, int w, int h, int stride, int move_dp, int k, int epoch);
 
 // k_band.hip
+#define K_DP_SWEEP_PXT_FORMS(X) X(1) X(2) X(4) X(8) X(16)       // each as <P, false, DP_THREADS>, <P, true, DP_THREADS> and <P, true, 256>
+#define K_LR_RIG_FORMS(X) X(false, false) X(false, true) X(true, false) X(true, true)       // k_dp_tile, k_band_update_tw<4, ..>, k_band_update_mw<2, 8 | 16, 8, ..>
 template <int PXT, bool UPDATE, int NTH = DP_THREADS> __global__ __launch_bounds__(NTH) void k_dp_sweep(const DevCarver *cs, DpK p, int w, int h, int stride, int lr);
 __global__ __launch_bounds__(64) void k_band_update(const DevCarver *cs, DpK p, int w, int h, int stride, int lr);
 template <int PXL, int NW, int R, bool LR, bool RIG> __global__ __launch_bounds__(64 * NW) void k_band_update_mw(const DevCarver *cs, DpK p, int w, int h, int stride);
@@ -37,10 +47,29 @@ template <int NW, bool LR, bool RIG> __global__ __launch_bounds__(128 * NW) void
 
 // k_tiles.hip
 template <bool LR, bool RIG> __global__ __launch_bounds__(64) void k_dp_tile(const DevCarver *cs, DpK p, int w, int h, int stride, int y0);
+// X(CLASS, PX, LR, RIG, UPDATE, DELTA, RIGM, HLN).  CLASS is the residency class (dpp_resident_workgroups): PX4 the plain 4-px forms,
+// PLAIN the plain 2-px forms and their 24-halo-lane geometry (px code 3), GENERAL delta_x 2 .. 10 and / or a rigidity mask (2 px only).
+// delta_x 5 .. 10 exist in the rigidity form only (dp_form in lqr_shim.hip).  (The order is the one they have always been instantiated in:
+// a kernel's pc-relative offset to the file's globals is part of its code, and scripts/kernel_diff.py compares code.)
+#define K_DP_TILE_P_FORMS_D(X, LR, UPD, D) X(GENERAL, 2, LR, false, UPD, D, false, 16) X(GENERAL, 2, LR, true, UPD, D, false, 16) X(GENERAL, 2, LR, true, UPD, D, true, 16)
+#define K_DP_TILE_P_FORMS_W(X, LR, UPD, D) X(GENERAL, 2, LR, true, UPD, D, false, 16) X(GENERAL, 2, LR, true, UPD, D, true, 16)
+#define K_DP_TILE_P_FORMS_LR(X, LR, UPD) \
+    X(PX4, 4, LR, false, UPD, 1, false, 16) X(PX4, 4, LR, true, UPD, 1, false, 16) X(PLAIN, 2, LR, false, UPD, 1, false, 16) X(PLAIN, 2, LR, true, UPD, 1, false, 16) \
+    X(GENERAL, 2, LR, true, UPD, 1, true, 16) K_DP_TILE_P_FORMS_D(X, LR, UPD, 2) K_DP_TILE_P_FORMS_D(X, LR, UPD, 3) K_DP_TILE_P_FORMS_D(X, LR, UPD, 4) \
+    K_DP_TILE_P_FORMS_W(X, LR, UPD, 5) K_DP_TILE_P_FORMS_W(X, LR, UPD, 6) K_DP_TILE_P_FORMS_W(X, LR, UPD, 7) K_DP_TILE_P_FORMS_W(X, LR, UPD, 8) K_DP_TILE_P_FORMS_W(X, LR, UPD, 9) K_DP_TILE_P_FORMS_W(X, LR, UPD, 10)
+#define K_DP_TILE_P_FORMS_24(X, UPD) X(PLAIN, 2, false, false, UPD, 1, false, 24) X(PLAIN, 2, false, true, UPD, 1, false, 24) X(PLAIN, 2, true, false, UPD, 1, false, 24) X(PLAIN, 2, true, true, UPD, 1, false, 24)
+#define K_DP_TILE_P_FORMS(X) K_DP_TILE_P_FORMS_LR(X, false, false) K_DP_TILE_P_FORMS_LR(X, false, true) K_DP_TILE_P_FORMS_LR(X, true, false) K_DP_TILE_P_FORMS_LR(X, true, true) \
+    K_DP_TILE_P_FORMS_24(X, false) K_DP_TILE_P_FORMS_24(X, true)
 template <int PX, bool LR, bool RIG, bool UPDATE, int DELTA = 1, bool RIGM = false, int HLN = 16>
 __global__ __launch_bounds__(64 * DPP_W) void k_dp_tile_p(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long long *exch, int epoch, int *dev_err);
 
 // k_levels.hip
+// X(LR, RIG, DELTA, RIGM): one residency class
+#define K_BAND_LEVELS_FORMS_D(X, LR, D) X(LR, false, D, false) X(LR, true, D, false) X(LR, true, D, true)
+#define K_BAND_LEVELS_FORMS_W(X, LR, D) X(LR, true, D, false) X(LR, true, D, true)
+#define K_BAND_LEVELS_FORMS_LR(X, LR) K_BAND_LEVELS_FORMS_D(X, LR, 1) K_BAND_LEVELS_FORMS_D(X, LR, 2) K_BAND_LEVELS_FORMS_D(X, LR, 3) K_BAND_LEVELS_FORMS_D(X, LR, 4) \
+    K_BAND_LEVELS_FORMS_W(X, LR, 5) K_BAND_LEVELS_FORMS_W(X, LR, 6) K_BAND_LEVELS_FORMS_W(X, LR, 7) K_BAND_LEVELS_FORMS_W(X, LR, 8) K_BAND_LEVELS_FORMS_W(X, LR, 9) K_BAND_LEVELS_FORMS_W(X, LR, 10)
+#define K_BAND_LEVELS_FORMS(X) K_BAND_LEVELS_FORMS_LR(X, false) K_BAND_LEVELS_FORMS_LR(X, true)
 template <bool LR, bool RIG, int DELTA, bool RIGM>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_band_levels(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long long *exch, int epoch, int *dev_err, int P, int n_img);
 
@@ -67,5 +96,7 @@ __global__ __launch_bounds__(256) void k_plane_transpose(const float *plane, flo
 template <bool PIC> __global__ __launch_bounds__(256) void k_energy_range(const DevCarver *cs, int w, int h, int stride, float *partials);
 __global__ __launch_bounds__(256) void k_energy_plane(const DevCarver *cs, int w, int h, int stride, int transposed, int normalised,
                                                       const float *partials, int n_partials, float *out);
+#define K_ENERGY_OUT_FORMS_T(X, T) X(T, 0) X(T, 1) X(T, 2) X(T, 3)
+#define K_ENERGY_OUT_FORMS(X) K_ENERGY_OUT_FORMS_T(X, 0) K_ENERGY_OUT_FORMS_T(X, 1) K_ENERGY_OUT_FORMS_T(X, 2) K_ENERGY_OUT_FORMS_T(X, 3) K_ENERGY_OUT_FORMS_T(X, 4) K_ENERGY_OUT_FORMS_T(X, 5) K_ENERGY_OUT_FORMS_T(X, 6)
 template <int TYPE, int DEPTH> __global__ __launch_bounds__(256) void k_energy_out(const DevCarver *cs, int w, int h, int stride, int transposed,
                                                                                     const float *partials, int n_partials, uint8_t *out);

@@ -24,7 +24,6 @@ static int *g_dev_err = nullptr;           // its device address
     } while (0)
 
 // co-residency bounds for the spin waits of the persistent kernels, set from the occupancy queries in lqrhip_init (dpp_resident_workgroups)
-static int g_dpp_max_wgs = 0;
 static int g_dpp_max_wgs_plain = 0, g_dpp_max_wgs_general = 0;      // ... of the plain / the delta_x = 2..4, rigidity-mask instantiations
 static int g_dpp_max_wgs_px4 = 0;                                   // ... of the plain 4-px instantiations alone (fewer registers than the 2-px ones)
 static int g_dpp_max_wgs_levels = 0;                                // ... of k_band_levels
@@ -99,63 +98,37 @@ extern "C" int lqrhip_launch_census(unsigned long long *out, int n, int reset)
 
 extern "C" const char *lqrhip_last_error(void) { return g_err.c_str(); }
 
-// Workgroups of k_dp_tile_p the device holds at once.  Its tiles spin on their neighbours, so the grid
-// must be co-resident: the bound comes from the occupancy query of every instantiation that can be
-// launched (the minimum over them), less one workgroup per CU of margin -- the API is known to answer
-// one block per CU too many at some SGPR counts (MI355X_MICROARCH.md, residency) -- times the CU count.
-// A grid above the bound goes to k_dp_tile (kernel boundaries instead of spin waits).
-static int dpp_resident_workgroups(int dev)
+// Workgroups of the spinning kernels (k_dp_tile_p, k_band_levels) the device holds at once.  Their workgroups spin on their
+// neighbours, so a grid must be co-resident: each bound is the minimum of the occupancy query over EVERY instantiation of its
+// residency class -- the family's one list in lqr_kernels.h, from which the launch picks too, so no kernel can be launched that
+// was not asked about -- less one workgroup per CU of margin (the API is known to answer one block per CU too many at some SGPR
+// counts: MI355X_MICROARCH.md, residency), times the CU count.  A grid above the bound goes to k_dp_tile (kernel boundaries
+// instead of spin waits).
+static void dpp_resident_workgroups(int dev)
 {
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount <= 0) return 0;
-    int per_cu = 1 << 20;
-    auto q = [&](auto kern) {
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount <= 0) return;
+    enum { PX4, PLAIN, GENERAL, LEVELS, N_CLASSES };
+    int per_cu[N_CLASSES] = {1 << 20, 1 << 20, 1 << 20, 1 << 20};
+    auto q = [&](int cls, auto kern, int threads) {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 64 * DPP_W, 0) != hipSuccess) { (void) hipGetLastError(); n = 0; }
-        per_cu = std::min(per_cu, n);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, threads, 0) != hipSuccess) { (void) hipGetLastError(); n = 0; }
+        per_cu[cls] = std::min(per_cu[cls], n);
     };
-    q(k_dp_tile_p<4, false, false, false>); q(k_dp_tile_p<4, false, true, false>); q(k_dp_tile_p<4, true, false, false>); q(k_dp_tile_p<4, true, true, false>);
-    q(k_dp_tile_p<4, false, false, true>); q(k_dp_tile_p<4, false, true, true>); q(k_dp_tile_p<4, true, false, true>); q(k_dp_tile_p<4, true, true, true>);
-    // the 2-px instantiations stage a whole 32-row block (193 VGPRs): their bound is lower, and a grid that is too large for
-    // them but fits the 4-px ones must not be sent to k_dp_tile for it
-    g_dpp_max_wgs_px4 = std::max(0, per_cu - 1) * prop.multiProcessorCount;
-    q(k_dp_tile_p<2, false, false, false>); q(k_dp_tile_p<2, false, true, false>); q(k_dp_tile_p<2, true, false, false>); q(k_dp_tile_p<2, true, true, false>);
-    q(k_dp_tile_p<2, false, false, true>); q(k_dp_tile_p<2, false, true, true>); q(k_dp_tile_p<2, true, false, true>); q(k_dp_tile_p<2, true, true, true>);
-    // (round 6: the 24-halo-lane geometry of the plain 2-px kernels, px code 3)
-    q(k_dp_tile_p<2, false, false, false, 1, false, 24>); q(k_dp_tile_p<2, false, true, false, 1, false, 24>); q(k_dp_tile_p<2, true, false, false, 1, false, 24>); q(k_dp_tile_p<2, true, true, false, 1, false, 24>);
-    q(k_dp_tile_p<2, false, false, true, 1, false, 24>); q(k_dp_tile_p<2, false, true, true, 1, false, 24>); q(k_dp_tile_p<2, true, false, true, 1, false, 24>); q(k_dp_tile_p<2, true, true, true, 1, false, 24>);
-    g_dpp_max_wgs_plain = std::max(0, per_cu - 1) * prop.multiProcessorCount;
+#define QUERY(CLASS, ...) q(CLASS, k_dp_tile_p<__VA_ARGS__>, 64 * DPP_W);
+    K_DP_TILE_P_FORMS(QUERY)
+#undef QUERY
+#define QUERY(...) q(LEVELS, k_band_levels<__VA_ARGS__>, 128);
+    K_BAND_LEVELS_FORMS(QUERY)
+#undef QUERY
+    auto bound = [&](int blocks) { return std::max(0, blocks - 1) * prop.multiProcessorCount; };
     g_n_cu = prop.multiProcessorCount;
-    // the delta_x = 2 / rigidity-mask instantiations (2 px per lane only) hold more registers
-    per_cu = 1 << 20;
-#define QG(LRV, UPD) q(k_dp_tile_p<2, LRV, true, UPD, 1, true>); q(k_dp_tile_p<2, LRV, false, UPD, 2, false>); q(k_dp_tile_p<2, LRV, true, UPD, 2, false>); q(k_dp_tile_p<2, LRV, true, UPD, 2, true>); \
-    q(k_dp_tile_p<2, LRV, false, UPD, 3, false>); q(k_dp_tile_p<2, LRV, true, UPD, 3, false>); q(k_dp_tile_p<2, LRV, true, UPD, 3, true>); \
-    q(k_dp_tile_p<2, LRV, false, UPD, 4, false>); q(k_dp_tile_p<2, LRV, true, UPD, 4, false>); q(k_dp_tile_p<2, LRV, true, UPD, 4, true>)
-    QG(false, false); QG(false, true); QG(true, false); QG(true, true);
-#undef QG
-#define QW(DV) q(k_dp_tile_p<2, false, true, false, DV, false>); q(k_dp_tile_p<2, false, true, true, DV, false>); q(k_dp_tile_p<2, true, true, false, DV, true>); q(k_dp_tile_p<2, true, true, true, DV, true>)
-    QW(5); QW(6); QW(7); QW(8); QW(9); QW(10);         // delta_x 5 .. 10 (round 6): few staged rows, wide candidate scans
-#undef QW
-    g_dpp_max_wgs_general = std::max(0, per_cu - 1) * prop.multiProcessorCount;
-    {
-        int per_cu = 1 << 20;
-        auto ql = [&](auto kern) {
-            int n = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 128, 0) != hipSuccess) { (void) hipGetLastError(); n = 0; }
-            per_cu = std::min(per_cu, n);
-        };
-#define QL(LRV) ql(k_band_levels<LRV, false, 1, false>); ql(k_band_levels<LRV, true, 1, false>); ql(k_band_levels<LRV, true, 1, true>); \
-    ql(k_band_levels<LRV, false, 2, false>); ql(k_band_levels<LRV, true, 2, false>); ql(k_band_levels<LRV, true, 2, true>); \
-    ql(k_band_levels<LRV, false, 3, false>); ql(k_band_levels<LRV, true, 3, false>); ql(k_band_levels<LRV, true, 3, true>); \
-    ql(k_band_levels<LRV, false, 4, false>); ql(k_band_levels<LRV, true, 4, false>); ql(k_band_levels<LRV, true, 4, true>)
-        QL(false); QL(true);
-#undef QL
-#define QLW(DV) ql(k_band_levels<false, true, DV, false>); ql(k_band_levels<true, true, DV, false>); ql(k_band_levels<false, true, DV, true>); ql(k_band_levels<true, true, DV, true>)
-        QLW(5); QLW(6); QLW(7); QLW(8); QLW(9); QLW(10);
-#undef QLW
-        g_dpp_max_wgs_levels = std::max(0, per_cu - 1) * prop.multiProcessorCount;
-    }
-    return g_dpp_max_wgs_plain;
+    // the plain 2-px instantiations stage a whole 32-row block (193 VGPRs): their bound is lower, and a grid that is too large for
+    // them but fits the 4-px ones must not be sent to k_dp_tile for it.  The general ones (2 px per lane only) hold more registers still
+    g_dpp_max_wgs_px4 = bound(per_cu[PX4]);
+    g_dpp_max_wgs_plain = bound(std::min(per_cu[PX4], per_cu[PLAIN]));
+    g_dpp_max_wgs_general = bound(per_cu[GENERAL]);
+    g_dpp_max_wgs_levels = bound(per_cu[LEVELS]);
 }
 
 // Large lock-step groups are carved on 4 streams, and those need hardware queues of their own: the HIP runtime's
@@ -204,7 +177,7 @@ extern "C" int lqrhip_init(void)
     HIPCK(hipHostMalloc((void **) &g_dev_err_host, sizeof(int), hipHostMallocMapped));
     *g_dev_err_host = 0;
     HIPCK(hipHostGetDevicePointer((void **) &g_dev_err, g_dev_err_host, 0));
-    g_dpp_max_wgs = dpp_resident_workgroups(dev);
+    dpp_resident_workgroups(dev);
     g_device = dev;
     return dev;
 }
@@ -560,6 +533,14 @@ template <class F> static inline void with_form(const LqrHipCarver *c, F f)
 // plane already holds brightness or luma (DeepRead.luma decided it when the plane was laid out) and grad_energy_f only looks at
 // NRG % 3, so the six would compile to three pairs of identical kernels.  The value forms are instantiated for 0, 1, 2 and 6 only.
 constexpr int plane_nrg(bool value, int nrg) { return value && nrg >= 3 && nrg <= 5 ? nrg - 3 : nrg; }
+static inline int nrg_index(int nrg_func) { return nrg_func >= 0 && nrg_func <= 5 ? nrg_func : 6; }      // LqrEnergyFuncBuiltinType; anything else is 6
+// Launching a template kernel: the run-time values are matched against the family's list in lqr_kernels.h, by a chain of
+// `#define CASE(...) if (<values equal the entry>) <launch that entry>; else` ending in no_form -- values no entry has cannot come
+// out of the choices above the launch sites, but they must not launch nothing silently.
+static int no_form(const char *family) { g_err = std::string(family) + ": no instantiation for the parameters asked for"; return LQRHIP_EARG; }
+// ... for a list of ints: f(std::integral_constant<int, v>{}) and true if the list has v
+#define LISTED_CASE_(N) if (v__ == N) { f__(std::integral_constant<int, N>{}); return true; }
+#define with_listed(LIST, v, f) [&](int v__, auto f__) { LIST(LISTED_CASE_) return false; }(v, f)
 // liblqr's default image type for a channel count, as a read mode
 static void default_read(LqrHipCarver *c)
 {
@@ -1028,6 +1009,15 @@ extern "C" void lqrhip_set_dp_persistent_px(int px) { g_dpp_px_override = (px ==
 // -1: the occupancy-derived bound (dpp_resident_workgroups); >= 0: at most that many workgroups for the persistent
 // tiled sweep -- 0 sends every full DP to k_dp_tile and every incremental update to a band kernel
 extern "C" void lqrhip_set_dp_persistent_limit(int workgroups) { g_dpp_limit_override = workgroups; }
+static inline int dpp_limit(int bound) { return g_dpp_limit_override >= 0 ? std::min(g_dpp_limit_override, bound) : bound; }     // a residency bound under that cap
+static bool has_rigmask(const LqrHipBatch *b)
+{
+    bool any = false;
+    for (auto *c : b->cs) any |= (c->rig != nullptr);
+    return any;
+}
+// `rigm`: a rigidity mask that matters to the batch's DP (without rigidity the mask multiplies nothing)
+static inline bool rigmask_matters(const LqrHipBatch *b, bool use_rig) { return use_rig && has_rigmask(b); }
 extern "C" void lqrhip_prof_reset(void)
 {
     for (auto &kv : g_profrec) for (auto &e : kv.second.ev) { (void) hipEventDestroy(e.first); (void) hipEventDestroy(e.second); }
@@ -1107,11 +1097,11 @@ extern "C" int lqrhip_emap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w,
     LqrHipCarver *c0 = b->cs[0];
     dim3 grid((w + 255) / 256, h, (unsigned) b->cs.size());
     DpK k = make_dpk(p, c0->ch);
-    with_form(c0, [&](auto value) {
-#define LAUNCH_EMAP(N) hipLaunchKernelGGL((k_emap_full<plane_nrg(value, N), value>), grid, dim3(256), 0, b->stream, b->d_desc, k, w, h, c0->stride)
-        NRG_DISPATCH(p->nrg_func, LAUNCH_EMAP)
-#undef LAUNCH_EMAP
-    });
+    const bool value = reads_value(c0);
+    const int nrg = plane_nrg(value, nrg_index(p->nrg_func));
+#define CASE(N, V) if (nrg == N && value == V) hipLaunchKernelGGL((k_emap_full<N, V>), grid, dim3(256), 0, b->stream, b->d_desc, k, w, h, c0->stride); else
+    K_EMAP_FORMS(CASE) return no_form("k_emap_full");
+#undef CASE
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -1142,21 +1132,11 @@ extern "C" int lqrhip_energy_out(LqrHipBatch *b, int w, int h, int transposed, i
         if (form == 2) hipLaunchKernelGGL(k_energy_range<true>, dim3(n_partials), dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, partials);
         const int W = transposed ? h : w, H = transposed ? w : h;
         const dim3 grid((W + EO_TILE - 1) / EO_TILE, (H + EO_TILE - 1) / EO_TILE);
-#define LAUNCH_EO(T, D) hipLaunchKernelGGL((k_energy_out<T, D>), grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, transposed, partials, n_partials, dst)
-#define LAUNCH_EO_D(T) do { if (depth == 0) LAUNCH_EO(T, 0); else if (depth == 1) LAUNCH_EO(T, 1); else if (depth == 2) LAUNCH_EO(T, 2); else LAUNCH_EO(T, 3); } while (0)
+#define CASE(T, D) if (image_type == T && depth == D) hipLaunchKernelGGL((k_energy_out<T, D>), grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, transposed, partials, n_partials, dst); else
         if (form != 2)
             hipLaunchKernelGGL(k_energy_plane, grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, transposed, form, partials, n_partials, (float *) dst);
-        else switch (image_type) {
-            case 0: LAUNCH_EO_D(0); break;
-            case 1: LAUNCH_EO_D(1); break;
-            case 2: LAUNCH_EO_D(2); break;
-            case 3: LAUNCH_EO_D(3); break;
-            case 4: LAUNCH_EO_D(4); break;
-            case 5: LAUNCH_EO_D(5); break;
-            default: LAUNCH_EO_D(6); break;
-        }
-#undef LAUNCH_EO_D
-#undef LAUNCH_EO
+        else K_ENERGY_OUT_FORMS(CASE) return no_form("k_energy_out");
+#undef CASE
         return 0;
     };
     rc = run();
@@ -1177,13 +1157,12 @@ static int launch_dp_tiled(LqrHipBatch *b, const DpK &k, int w, int h, int lr)
 {
     LqrHipCarver *c0 = b->cs[0];
     const dim3 grid((w + DPT_OWN - 1) / DPT_OWN, (unsigned) b->cs.size());
-#define LAUNCH_TILE(LRV, RIGV) hipLaunchKernelGGL((k_dp_tile<LRV, RIGV>), grid, dim3(64), 0, b->stream, b->d_desc, k, w, h, c0->stride, y0)
     for (int y0 = 0; y0 < h; y0 += DPT_ROWS) {
         CENSUS(LQRHIP_CENSUS_DP_TILE);
-        if (lr) { if (k.use_rig) LAUNCH_TILE(true, true); else LAUNCH_TILE(true, false); }
-        else { if (k.use_rig) LAUNCH_TILE(false, true); else LAUNCH_TILE(false, false); }
+#define CASE(LRV, RIGV) if ((lr != 0) == LRV && (k.use_rig != 0) == RIGV) hipLaunchKernelGGL((k_dp_tile<LRV, RIGV>), grid, dim3(64), 0, b->stream, b->d_desc, k, w, h, c0->stride, y0); else
+        K_LR_RIG_FORMS(CASE) return no_form("k_dp_tile");
+#undef CASE
     }
-#undef LAUNCH_TILE
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -1197,8 +1176,8 @@ static int launch_dp_tiled(LqrHipBatch *b, const DpK &k, int w, int h, int lr)
 static int dp_persistent_px(const LqrHipBatch *b, int w, bool general = false, int delta = 1, int count = -1)
 {
     if (b->shared || no_spin(b)) return 0;
-    const int bound = general ? g_dpp_max_wgs_general : g_dpp_max_wgs;
-    const int limit = g_dpp_limit_override >= 0 ? std::min(g_dpp_limit_override, bound) : bound;
+    const int bound = general ? g_dpp_max_wgs_general : g_dpp_max_wgs_plain;
+    const int limit = dpp_limit(bound);
     const size_t n = count < 0 ? b->cs.size() : (size_t) count;
     const int hh = b->cs[0]->wk_h;                            // the block index is DPP_BLK_BITS bits of the granule tag
     const int maxblk = (1 << DPP_BLK_BITS) - 1;
@@ -1207,7 +1186,7 @@ static int dp_persistent_px(const LqrHipBatch *b, int w, bool general = false, i
     if (!general && delta == 1 && (g_dpp_px_override == 3 || g_dpp_px_override == 0) && hh <= maxblk * dpp_rb(3, 1) &&
         (size_t) ((w + dpp_own(3) - 1) / dpp_own(3)) * n <= (size_t) std::min(limit, g_dpp_px_override == 3 ? limit : g_n_cu)) return 3;
     if ((general || (g_dpp_px_override != 4 && g_dpp_px_override != 3)) && hh <= maxblk * dpp_rb(2, delta) && (size_t) ((w + dpp_own(2) - 1) / dpp_own(2)) * n <= (size_t) limit) return 2;
-    const int limit4 = g_dpp_limit_override >= 0 ? std::min(g_dpp_limit_override, g_dpp_max_wgs_px4) : g_dpp_max_wgs_px4;
+    const int limit4 = dpp_limit(g_dpp_max_wgs_px4);
     if (!general && g_dpp_px_override != 2 && g_dpp_px_override != 3 && hh <= maxblk * dpp_halo(4) && (size_t) ((w + dpp_own(4) - 1) / dpp_own(4)) * n <= (size_t) limit4) return 4;
     return 0;
 }
@@ -1221,7 +1200,7 @@ extern "C" int lqrhip_general_batch_limit(int w) { return lqrhip_general_batch_l
 extern "C" int lqrhip_general_batch_limit_delta(int w, int delta)
 {
     if (lqrhip_init() < 0 || w < 1) return 0;
-    const int limit = g_dpp_limit_override >= 0 ? std::min(g_dpp_limit_override, g_dpp_max_wgs_general) : g_dpp_max_wgs_general;
+    const int limit = dpp_limit(g_dpp_max_wgs_general);
     const int tiled = limit / ((w + dpp_own(2) - 1) / dpp_own(2));
     // round 5: groups of 8 and more such carvers run on k_band_levels (7 or more slots per image, rows up to 4096 px), which takes
     // far larger groups than the full-width tiled kernels; its full DPs (3 per resize) then go to k_dp_sweep, one workgroup per image
@@ -1229,12 +1208,40 @@ extern "C" int lqrhip_general_batch_limit_delta(int w, int delta)
     // width after a few hundred rows and the level kernel's images stop at a collision: 16 x 4K at delta_x 8 spent 6.6 of 9.6 ms per seam
     // in the sweep that takes over)
     if (delta <= 4 && g_band_levels != 0 && g_update_mode < 0 && (w + 63) / 64 <= LV_MAX_TILES) {
-        const int lim_lv = g_dpp_limit_override >= 0 ? std::min(g_dpp_limit_override, g_dpp_max_wgs_levels) : g_dpp_max_wgs_levels;
+        const int lim_lv = dpp_limit(g_dpp_max_wgs_levels);
         const int lv = lim_lv / 7;
         if (lv >= 8) return std::max(tiled, lv);
     }
     return tiled;
 }
+
+// Grow and (re)lay a batch's exchange area for a spinning kernel: `need_elems` words for `ntiles` tiles of each of `n` images, in the
+// layout `layout` (k_dp_tile_p: its px code; k_band_levels: 103, that kernel's own layout and tags).  Tags and finished-tile
+// counters start at 0; afterwards nothing is ever cleared: tags carry the launch epoch, the last tile re-arms the counter
+static int exch_ensure(LqrHipBatch *b, size_t need_elems, int ntiles, int n, int layout)
+{
+    int rc;
+    if (b->exch_elems < need_elems) {
+        HIPCK(hipStreamSynchronize(b->stream));
+        dfree(b->exch);
+        b->exch_elems = 0;
+        if ((rc = dmalloc(&b->exch, need_elems))) return rc;
+        b->exch_elems = need_elems;
+        b->exch_ntiles = 0;
+    }
+    if (b->exch_ntiles != ntiles || b->exch_n != n || b->exch_px != layout) {
+        HIPCK(hipMemsetAsync(b->exch, 0, need_elems * sizeof(unsigned long long), b->stream));
+        b->exch_ntiles = ntiles; b->exch_n = n; b->exch_px = layout;
+    }
+    return 0;
+}
+
+// The <LR, RIG, DELTA, RIGM> of the spinning DP kernels (k_dp_tile_p, k_band_levels) for a batch's run-time values.
+// delta_x 5 .. 10 (round 6): the rigidity form only -- without rigidity the host's table is all zeros, and x + 0.0f is x for every
+// candidate (no cumulative minimum is -0.0f: energies are sums of non-negative gradients and finite biases).
+// A mask matters with rigidity only (rigmask_matters), so a mask at delta_x 1 is <true, true, 1, true> and nothing else.
+struct DpForm { bool lr, rig; int delta; bool rigm; };
+static inline DpForm dp_form(const DpK &k, int lr, bool rigm) { return DpForm{lr != 0, k.use_rig != 0 || k.delta >= 5, k.delta, rigm}; }
 
 // E5 (UPDATE = false) or the full-width form of E9 (UPDATE = true) as one persistent launch
 // (first, count): a range of the batch's images (E5 only: a general batch too large for one persistent grid is swept group after group)
@@ -1244,9 +1251,7 @@ static int launch_dp_persistent(LqrHipBatch *b, const DpK &k, int w, int h, int 
     LqrHipCarver *c0 = b->cs[0];
     const size_t n = count < 0 ? b->cs.size() : (size_t) count;
     if (UPDATE && count >= 0) return LQRHIP_EARG;
-    bool rigm = false;
-    for (auto *c : b->cs) rigm |= (c->rig != nullptr);
-    rigm = rigm && k.use_rig;                                  // without rigidity the mask multiplies nothing
+    const bool rigm = rigmask_matters(b, k.use_rig);
     const bool general = k.delta != 1 || rigm;
     if (k.delta < 1 || k.delta > LQR_FAST_MAX_DELTA) return LQRHIP_EARG;
     const int px = dp_persistent_px(b, w, general, k.delta, count);
@@ -1254,20 +1259,7 @@ static int launch_dp_persistent(LqrHipBatch *b, const DpK &k, int w, int h, int 
     const int ntiles = (w + dpp_own(px) - 1) / dpp_own(px);
     int rc;
     const size_t need_elems = 2 * ((size_t) ntiles * dpp_ex_tile(px) + 8) * n;      // (granules + finished-tile counter, and the near copies: k_tiles.hip)
-    if (b->exch_elems < need_elems) {
-        HIPCK(hipStreamSynchronize(b->stream));
-        dfree(b->exch);
-        b->exch_elems = 0;
-        if ((rc = dmalloc(&b->exch, need_elems))) return rc;
-        b->exch_elems = need_elems;
-        b->exch_ntiles = 0;
-    }
-    if (b->exch_ntiles != ntiles || b->exch_n != (int) n || b->exch_px != px) {
-        // (re)lay the exchange area out: tags and finished-tile counters start at 0 (afterwards nothing is ever
-        // cleared: tags carry the launch epoch, the last tile re-arms the counter)
-        HIPCK(hipMemsetAsync(b->exch, 0, need_elems * sizeof(unsigned long long), b->stream));
-        b->exch_ntiles = ntiles; b->exch_n = (int) n; b->exch_px = px;
-    }
+    if ((rc = exch_ensure(b, need_elems, ntiles, (int) n, px))) return rc;
     if (UPDATE) {
         // second planes, allocated on first use -- per carver: a batch may mix carvers that already went
         // through a tiled update on their own with fresh ones
@@ -1291,46 +1283,21 @@ static int launch_dp_persistent(LqrHipBatch *b, const DpK &k, int w, int h, int 
     const int epoch = 1 + ((b->tile_epoch++) % ((1 << (31 - DPP_BLK_BITS)) - 2));          // never 0; above the block index in the 32-bit tag
     const dim3 grid(ntiles, (unsigned) n);
     CENSUS(general ? LQRHIP_CENSUS_TILE_P_GENERAL : px == 3 ? LQRHIP_CENSUS_TILE_P_G3 : px == 2 ? LQRHIP_CENSUS_TILE_P_G2 : LQRHIP_CENSUS_TILE_P_G4);
-#define LAUNCH_TILE(PXV, LRV, RIGV) hipLaunchKernelGGL((k_dp_tile_p<PXV, LRV, RIGV, UPDATE>), grid, dim3(64 * DPP_W), 0, b->stream, b->d_desc + first, k, w, h, c0->stride, b->exch, epoch, g_dev_err)
-#define LAUNCH_TILE_PX(PXV)                                                                 \
-    do {                                                                                    \
-        if (lr) { if (k.use_rig) LAUNCH_TILE(PXV, true, true); else LAUNCH_TILE(PXV, true, false); }     \
-        else { if (k.use_rig) LAUNCH_TILE(PXV, false, true); else LAUNCH_TILE(PXV, false, false); }      \
-    } while (0)
-#define LAUNCH_TILE_G(LRV, RIGV, DV, RMV) hipLaunchKernelGGL((k_dp_tile_p<2, LRV, RIGV, UPDATE, DV, RMV>), grid, dim3(64 * DPP_W), 0, b->stream, b->d_desc + first, k, w, h, c0->stride, b->exch, epoch, g_dev_err)
-#define LAUNCH_TILE_G_LR(RIGV, DV, RMV) do { if (lr) LAUNCH_TILE_G(true, RIGV, DV, RMV); else LAUNCH_TILE_G(false, RIGV, DV, RMV); } while (0)
-    if (general) {
-#define LAUNCH_TILE_G_D(DV) do { if (!k.use_rig) LAUNCH_TILE_G_LR(false, DV, false); else if (!rigm) LAUNCH_TILE_G_LR(true, DV, false); else LAUNCH_TILE_G_LR(true, DV, true); } while (0)
-        // delta_x 5 .. 10 (round 6): the rigidity form only -- without rigidity the host's table is all zeros, and x + 0.0f is x for every
-        // candidate (no cumulative minimum is -0.0f: energies are sums of non-negative gradients and finite biases)
-#define LAUNCH_TILE_G_W(DV) do { if (rigm) LAUNCH_TILE_G_LR(true, DV, true); else LAUNCH_TILE_G_LR(true, DV, false); } while (0)
-        switch (k.delta) {
-        case 1: LAUNCH_TILE_G_LR(true, 1, true); break;
-        case 2: LAUNCH_TILE_G_D(2); break;
-        case 3: LAUNCH_TILE_G_D(3); break;
-        case 4: LAUNCH_TILE_G_D(4); break;
-        case 5: LAUNCH_TILE_G_W(5); break;
-        case 6: LAUNCH_TILE_G_W(6); break;
-        case 7: LAUNCH_TILE_G_W(7); break;
-        case 8: LAUNCH_TILE_G_W(8); break;
-        case 9: LAUNCH_TILE_G_W(9); break;
-        default: LAUNCH_TILE_G_W(10); break;
-        }
-#undef LAUNCH_TILE_G_W
-#undef LAUNCH_TILE_G_D
-    }
-    else if (px == 2) LAUNCH_TILE_PX(2);
-    else if (px == 3) {
-#define LAUNCH_TILE_W(LRV, RIGV) hipLaunchKernelGGL((k_dp_tile_p<2, LRV, RIGV, UPDATE, 1, false, 24>), grid, dim3(64 * DPP_W), 0, b->stream, b->d_desc + first, k, w, h, c0->stride, b->exch, epoch, g_dev_err)
-        if (lr) { if (k.use_rig) LAUNCH_TILE_W(true, true); else LAUNCH_TILE_W(true, false); }
-        else { if (k.use_rig) LAUNCH_TILE_W(false, true); else LAUNCH_TILE_W(false, false); }
-#undef LAUNCH_TILE_W
-    }
-    else LAUNCH_TILE_PX(4);
-#undef LAUNCH_TILE_G_LR
-#undef LAUNCH_TILE_G
-#undef LAUNCH_TILE_PX
-#undef LAUNCH_TILE
+    // px code 3 is 2 px per lane with the 24-halo-lane geometry; the general forms exist for 2 px per lane only (dp_persistent_px)
+    const DpForm f = dp_form(k, lr, rigm);
+    const int px_lane = px == 4 ? 4 : 2, hln = px == 3 ? 24 : 16;
+    const bool found = [&] {
+#define CASE(CLASS, PX, LR, RIG, UPD, DELTA, RIGM, HLN)                                                                         \
+        if constexpr (UPD == UPDATE)                                                                                            \
+            if (px_lane == PX && f.lr == LR && f.rig == RIG && f.delta == DELTA && f.rigm == RIGM && hln == HLN) {              \
+                hipLaunchKernelGGL((k_dp_tile_p<PX, LR, RIG, UPD, DELTA, RIGM, HLN>), grid, dim3(64 * DPP_W), 0, b->stream, b->d_desc + first, k, w, h, c0->stride, b->exch, epoch, g_dev_err); \
+                return true;                                                                                                    \
+            }
+        K_DP_TILE_P_FORMS(CASE)
+#undef CASE
+        return false;
+    }();
+    if (!found) return no_form("k_dp_tile_p");
     HIPCK(hipGetLastError());
     if (UPDATE)       // the kernel's last tile swapped the pointers in the device descriptors: mirror it
         for (auto *c : b->cs) { std::swap(c->m, c->m2); std::swap(c->least, c->least2); }
@@ -1342,9 +1309,7 @@ static int launch_dp(LqrHipBatch *b, const DpK &k, int w, int h, int lr)
 {
     LqrHipCarver *c0 = b->cs[0];
     if (!UPDATE) {
-        bool rigm = false;
-        for (auto *c : b->cs) rigm |= (c->rig != nullptr);
-        rigm = rigm && k.use_rig;
+        const bool rigm = rigmask_matters(b, k.use_rig);
         if (k.delta == 1 && !rigm) return dp_persistent_ok(b, w) ? launch_dp_persistent<false>(b, k, w, h, lr) : launch_dp_tiled(b, k, w, h, lr);
         if (k.delta >= 1 && k.delta <= LQR_FAST_MAX_DELTA && dp_persistent_px(b, w, true, k.delta)) return launch_dp_persistent<false>(b, k, w, h, lr);
         // round 5: a general batch too large for one persistent grid (it runs its incremental updates on k_band_levels): the full DP
@@ -1368,28 +1333,23 @@ static int launch_dp(LqrHipBatch *b, const DpK &k, int w, int h, int lr)
     int pxt = (w + nth - 1) / nth;
     size_t lds = (size_t) 2 * ((w + 3) & ~3) * sizeof(float);
     dim3 grid((unsigned) b->cs.size());
-#define LAUNCH_DP_T(P, T)                                                                                             \
-    do {                                                                                                              \
-        if (lds > 64 * 1024) {                                                                                        \
-            HIPCK(hipFuncSetAttribute((const void *) k_dp_sweep<P, UPDATE, T>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      (int) lds));                                                                    \
-            CENSUS(LQRHIP_CENSUS_LDS_ATTR_SWEEP);                                                                     \
-        }                                                                                                             \
-        CENSUS(LQRHIP_CENSUS_SWEEP + 2 * (P == 1 ? 0 : P == 2 ? 1 : P == 4 ? 2 : P == 8 ? 3 : 4) + (T == DP_THREADS ? 1 : 0)); \
-        CENSUS(UPDATE ? LQRHIP_CENSUS_SWEEP_UPDATE : LQRHIP_CENSUS_SWEEP_FULL);                                       \
-        hipLaunchKernelGGL((k_dp_sweep<P, UPDATE, T>), grid, dim3(T), lds, b->stream, b->d_desc, k, w, h, c0->stride, lr); \
-    } while (0)
-#define LAUNCH_DP(P) do { if constexpr (UPDATE) { if (nth == 256) LAUNCH_DP_T(P, 256); else LAUNCH_DP_T(P, DP_THREADS); } else LAUNCH_DP_T(P, DP_THREADS); } while (0)
-    if (pxt <= 1) LAUNCH_DP(1);
-    else if (pxt <= 2) LAUNCH_DP(2);
-    else if (pxt <= 4) LAUNCH_DP(4);
-    else if (pxt <= 8) LAUNCH_DP(8);
-    else if (pxt <= 16) LAUNCH_DP(16);
-    else { g_err = "image wider than 16384 px is not supported"; return LQRHIP_EARG; }
-#undef LAUNCH_DP_T
-#undef LAUNCH_DP
-    HIPCK(hipGetLastError());
-    return 0;
+    auto launch = [&](auto kern, int P, int T) -> int {
+        if (lds > 64 * 1024) {
+            HIPCK(hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+            CENSUS(LQRHIP_CENSUS_LDS_ATTR_SWEEP);
+        }
+        CENSUS(LQRHIP_CENSUS_SWEEP + 2 * (P == 1 ? 0 : P == 2 ? 1 : P == 4 ? 2 : P == 8 ? 3 : 4) + (T == DP_THREADS ? 1 : 0));
+        CENSUS(UPDATE ? LQRHIP_CENSUS_SWEEP_UPDATE : LQRHIP_CENSUS_SWEEP_FULL);
+        hipLaunchKernelGGL(kern, grid, dim3(T), lds, b->stream, b->d_desc, k, w, h, c0->stride, lr);
+        HIPCK(hipGetLastError());
+        return 0;
+    };
+    // the first listed px per thread that covers the row; only the update has the 256-thread forms
+#define CASE(P) if (pxt <= P) { if constexpr (UPDATE) { if (nth == 256) return launch(k_dp_sweep<P, true, 256>, P, 256); } return launch(k_dp_sweep<P, UPDATE, DP_THREADS>, P, DP_THREADS); }
+    K_DP_SWEEP_PXT_FORMS(CASE)
+#undef CASE
+    g_err = "image wider than 16384 px is not supported";
+    return LQRHIP_EARG;
 }
 
 extern "C" int lqrhip_mmap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h, int leftright)
@@ -1400,6 +1360,9 @@ extern "C" int lqrhip_mmap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w,
     ProfScope ps("dp_sweep", b->stream, 9.0 * w * h * b->cs.size());
     return launch_dp<false>(b, make_dpk(p, b->cs[0]->ch), w, h, leftright);
 }
+
+// brightness samples a row of k_emap_update takes (EU_NT): the window a seam of this delta_x can have moved
+constexpr int eu_samples(int delta_x) { return delta_x <= 2 ? 12 : delta_x <= 8 ? 36 : 68; }
 
 #ifndef FROZEN_LAG_MAX
 #define FROZEN_LAG_MAX 128      // seams the frozen planes may lag behind before they are compacted
@@ -1430,7 +1393,7 @@ extern "C" void lqrhip_set_band_levels(int slots) { g_band_levels = slots; }
 static int band_levels_P(const LqrHipBatch *b, int w, int h, int delta)
 {
     if (no_spin(b) || g_band_levels == 0 || delta < 1 || delta > LQR_FAST_MAX_DELTA || (h + lv_rows(delta, true) - 1) / lv_rows(delta, true) > LV_MAX_LEVELS || (w + 63) / 64 > LV_MAX_TILES) return 0;
-    const int limit = g_dpp_limit_override >= 0 ? std::min(g_dpp_limit_override, g_dpp_max_wgs_levels) : g_dpp_max_wgs_levels;
+    const int limit = dpp_limit(g_dpp_max_wgs_levels);
     const int per_batch = limit / std::max(b->shared_n, 1);
     int P = std::min(LV_PMAX, per_batch / (int) std::max<size_t>(b->cs.size(), 1));
     // automatic: 12 slots while the group's workgroups stay below ~384 (beyond that the sibling kernels are starved of registers,
@@ -1447,41 +1410,15 @@ static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr
     int rc;
     const int ntiles = (w + 63) / 64;
     const size_t need_elems = 2 * ((size_t) 4 * LV_PMAX + (size_t) 2 * ntiles * 64) * n;    // (two copies of each word: k_levels.hip, near_off)
-    if (b->exch_elems < need_elems) {
-        HIPCK(hipStreamSynchronize(b->stream));
-        dfree(b->exch);
-        b->exch_elems = 0;
-        if ((rc = dmalloc(&b->exch, need_elems))) return rc;
-        b->exch_elems = need_elems;
-        b->exch_ntiles = 0;
-    }
-    if (b->exch_ntiles != ntiles || b->exch_n != (int) n || b->exch_px != 103) {       // 103: this kernel's layout and tags
-        HIPCK(hipMemsetAsync(b->exch, 0, need_elems * sizeof(unsigned long long), b->stream));
-        b->exch_ntiles = ntiles; b->exch_n = (int) n; b->exch_px = 103;
-    }
+    if ((rc = exch_ensure(b, need_elems, ntiles, (int) n, 103))) return rc;
     const int epoch = 1 + ((b->tile_epoch++) % ((1 << 22) - 2));           // never 0; 22 bits above the 10 bits of level + 1
     const dim3 grid((unsigned) (8 * ((n + 7) / 8) * P));          // the slots of an image on one XCD (k_levels.hip)
     CENSUS(LQRHIP_CENSUS_BAND_LEVELS);
-#define LAUNCH_LV(LRV, RIGV, DV, RMV) hipLaunchKernelGGL((k_band_levels<LRV, RIGV, DV, RMV>), grid, dim3(128), 0, b->stream, b->d_desc, k, w, h, c0->stride, b->exch, epoch, g_dev_err, P, (int) n)
-#define LAUNCH_LV_LR(RIGV, DV, RMV) do { if (lr) LAUNCH_LV(true, RIGV, DV, RMV); else LAUNCH_LV(false, RIGV, DV, RMV); } while (0)
-#define LAUNCH_LV_D(DV) do { if (!k.use_rig) LAUNCH_LV_LR(false, DV, false); else if (!rigm) LAUNCH_LV_LR(true, DV, false); else LAUNCH_LV_LR(true, DV, true); } while (0)
-#define LAUNCH_LV_W(DV) do { if (rigm) LAUNCH_LV_LR(true, DV, true); else LAUNCH_LV_LR(true, DV, false); } while (0)      // delta_x 5 .. 10: the rigidity form (zero table without rigidity)
-    switch (k.delta) {
-    case 1: LAUNCH_LV_D(1); break;
-    case 2: LAUNCH_LV_D(2); break;
-    case 3: LAUNCH_LV_D(3); break;
-    case 4: LAUNCH_LV_D(4); break;
-    case 5: LAUNCH_LV_W(5); break;
-    case 6: LAUNCH_LV_W(6); break;
-    case 7: LAUNCH_LV_W(7); break;
-    case 8: LAUNCH_LV_W(8); break;
-    case 9: LAUNCH_LV_W(9); break;
-    default: LAUNCH_LV_W(10); break;
-    }
-#undef LAUNCH_LV_W
-#undef LAUNCH_LV_D
-#undef LAUNCH_LV_LR
-#undef LAUNCH_LV
+    const DpForm f = dp_form(k, lr, rigm);
+#define CASE(LR, RIG, DELTA, RIGM) if (f.lr == LR && f.rig == RIG && f.delta == DELTA && f.rigm == RIGM) \
+        hipLaunchKernelGGL((k_band_levels<LR, RIG, DELTA, RIGM>), grid, dim3(128), 0, b->stream, b->d_desc, k, w, h, c0->stride, b->exch, epoch, g_dev_err, P, (int) n); else
+    K_BAND_LEVELS_FORMS(CASE) return no_form("k_band_levels");
+#undef CASE
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -1539,11 +1476,10 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
     const int stride = c0->stride;
     const int wnew = w - 1;
     const int move_dp = (wnew > 1 && !full_rebuild) ? 1 : 0;
-    bool has_rigmask = false;
-    for (auto *c : b->cs) has_rigmask |= (c->rig != nullptr);
+    const bool rigmask = has_rigmask(b);
     // bytes the carve moves per pixel of the side it moves, read + write: en 4 (+ m 4 + back pointer 1 unless a full DP follows,
     // + the rigidity mask 4) -- k_vpath* knows how many pixels that is for the seam it finds and keeps the sum (lqrhip_moved_bytes)
-    const int moved_unit = 2 * (4 + (move_dp ? 5 : 0) + (has_rigmask ? 4 : 0));
+    const int moved_unit = 2 * (4 + (move_dp ? 5 : 0) + (rigmask ? 4 : 0));
     // Backtrack: for single images the two-kernel parallel form (k_vp_maps / k_vp_solve, k_backtrack.hip: the chip walks every column
     // through every chunk of rows, the serial part is one step per chunk); for groups the one-wave-per-image walk, whose launches
     // keep the chip busy anyway.  Measured on one box, us per seam with every kernel event-timed, k_vpath1 / parallel: 4K 70 / 41 (single4k
@@ -1568,48 +1504,38 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
         if (grew) { b->dirty = true; if ((rc = batch_upload(b))) return rc; }
         ProfScope ps("vpath", b->stream, 0);
         CENSUS(LQRHIP_CENSUS_VP_PARALLEL);
-#define LAUNCH_VP(DV) do { \
-        hipLaunchKernelGGL(k_vp_maps<DV>, dim3((w + 255) / 256, nchunks, n), dim3(256), 0, b->stream, b->d_desc, w, h, stride); \
-        hipLaunchKernelGGL(k_vp_solve<DV>, dim3(n), dim3(VPATH_THREADS), (size_t) (nchunks + 2) * sizeof(int), b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit); } while (0)
-        switch (p->delta_x) {
-        case 1: LAUNCH_VP(1); break; case 2: LAUNCH_VP(2); break; case 3: LAUNCH_VP(3); break; case 4: LAUNCH_VP(4); break; case 5: LAUNCH_VP(5); break;
-        case 6: LAUNCH_VP(6); break; case 7: LAUNCH_VP(7); break; case 8: LAUNCH_VP(8); break; case 9: LAUNCH_VP(9); break; default: LAUNCH_VP(10); break;
-        }
-#undef LAUNCH_VP
+        if (!with_listed(K_VP_FORMS, p->delta_x, [&](auto delta) {
+                hipLaunchKernelGGL(k_vp_maps<delta>, dim3((w + 255) / 256, nchunks, n), dim3(256), 0, b->stream, b->d_desc, w, h, stride);
+                hipLaunchKernelGGL(k_vp_solve<delta>, dim3(n), dim3(VPATH_THREADS), (size_t) (nchunks + 2) * sizeof(int), b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit);
+            })) return no_form("k_vp_maps");
     } else {
         ProfScope ps("vpath", b->stream, 0);
         CENSUS(p->delta_x <= 7 ? LQRHIP_CENSUS_VPATH1 : LQRHIP_CENSUS_VPATH);
-        if (p->delta_x == 1)
-            hipLaunchKernelGGL(k_vpath1<1>, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit);
-        else if (p->delta_x == 2)
-            hipLaunchKernelGGL(k_vpath1<2>, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit);
-        else if (p->delta_x == 3)
-            hipLaunchKernelGGL(k_vpath1<3>, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit);
-        else if (p->delta_x == 4)
-            hipLaunchKernelGGL(k_vpath1<4>, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit);
-        else if (p->delta_x == 5)
-            hipLaunchKernelGGL(k_vpath1<5>, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit);
-        else if (p->delta_x == 6)
-            hipLaunchKernelGGL(k_vpath1<6>, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit);
-        else if (p->delta_x == 7)
-            hipLaunchKernelGGL(k_vpath1<7>, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit);
-        else
+        // the one-wave walk: unrolled for the listed delta_x, the loop over candidates beyond (and for delta_x 0)
+        if (!with_listed(K_VPATH1_FORMS, p->delta_x, [&](auto delta) {
+                hipLaunchKernelGGL(k_vpath1<delta>, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit);
+            }))
             hipLaunchKernelGGL(k_vpath, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, leftright_pick, p->delta_x,
                                log_index, moved_unit);
     }
     // Single images and groups up to 4: the carve and the energy update in one launch (k_carve_e, k_carve.hip) -- the wave that has moved
     // a row refreshes that row's energies; one dependent launch less per seam.  delta_x <= 2 (12 brightness samples per row).
     // (value-plane carvers: the two kernels, k_carve and k_emap_update<.., true>)
+    // The frozen planes' lag.  The energy update walks the seam log back to the frozen frame (O(lag) per sample); compacting the frozen
+    // planes costs a pass over them.  Few images: the walk is on the critical path and the pass is cheap -> short lag
+    auto frozen_within_lag = [&]() -> int {
+        const int lag_max = n <= 4 ? FROZEN_LAG_MAX / 4 : FROZEN_LAG_MAX;
+        return log_index + 1 - c0->frozen_epoch > lag_max ? frozen_catchup(b, log_index + 1, wnew, h) : 0;
+    };
     const bool fuse_e = p->delta_x <= 2 && vp_group <= (size_t) g_carve_fused && wnew > 1 && !reads_value(c0);
     if (fuse_e) {
-        const int lag_max = n <= 4 ? FROZEN_LAG_MAX / 4 : FROZEN_LAG_MAX;
-        if (log_index + 1 - c0->frozen_epoch > lag_max && (rc = frozen_catchup(b, log_index + 1, wnew, h))) return rc;      // (needs the seam log only: before the carve)
+        if ((rc = frozen_within_lag())) return rc;      // (needs the seam log only: before the carve)
         const int epoch = c0->frozen_epoch;
         ProfScope ps("carve", b->stream, 4.0 * (double) w * h * n);
         CENSUS(LQRHIP_CENSUS_CARVE_E);
-#define LAUNCH_CE(N) hipLaunchKernelGGL((k_carve_e<N>), dim3((h + 3) / 4, n), dim3(256), 0, b->stream, b->d_desc, k, w, h, stride, move_dp, log_index, epoch)
-        NRG_DISPATCH(p->nrg_func, LAUNCH_CE)
-#undef LAUNCH_CE
+        if (!with_listed(K_CARVE_E_FORMS, nrg_index(p->nrg_func), [&](auto nrg) {
+                hipLaunchKernelGGL((k_carve_e<nrg>), dim3((h + 3) / 4, n), dim3(256), 0, b->stream, b->d_desc, k, w, h, stride, move_dp, log_index, epoch);
+            })) return no_form("k_carve_e");
     } else {
         // algorithmic bytes of one carve launch: read + write of one 4-byte
         // plane over the half of each row right of the seam = 8 B * w*h/2 per image
@@ -1625,18 +1551,15 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
     }
     if (!fuse_e) {
         ProfScope ps("emap_update", b->stream, 0);
-        // the energy update walks the seam log back to the frozen frame (O(lag) per sample); compacting the frozen planes
-        // costs a pass over them.  Few images: the walk is on the critical path and the pass is cheap -> short lag
-        const int lag_max = n <= 4 ? FROZEN_LAG_MAX / 4 : FROZEN_LAG_MAX;
-        if (log_index + 1 - c0->frozen_epoch > lag_max && (rc = frozen_catchup(b, log_index + 1, wnew, h))) return rc;
+        if ((rc = frozen_within_lag())) return rc;
         const int epoch = c0->frozen_epoch;
-        with_form(c0, [&](auto value) {
-#define LAUNCH_EUPD_NT(N, NT) hipLaunchKernelGGL((k_emap_update<plane_nrg(value, N), NT, value>), dim3((h + EU_ROWS - 1) / EU_ROWS, n), dim3(64), 0, b->stream, b->d_desc, k, wnew, h, stride, log_index, epoch)
-#define LAUNCH_EUPD(N) do { if (p->delta_x <= 2) LAUNCH_EUPD_NT(N, 12); else if (p->delta_x <= 8) LAUNCH_EUPD_NT(N, 36); else LAUNCH_EUPD_NT(N, 68); } while (0)
-            NRG_DISPATCH(p->nrg_func, LAUNCH_EUPD)
-#undef LAUNCH_EUPD
-#undef LAUNCH_EUPD_NT
-        });
+        const bool value = reads_value(c0);
+        const int nrg = plane_nrg(value, nrg_index(p->nrg_func)), nt = eu_samples(p->delta_x);
+#define CASE_NT(NT, N, V) if (nrg == N && value == V && nt == NT) hipLaunchKernelGGL((k_emap_update<N, NT, V>), dim3((h + EU_ROWS - 1) / EU_ROWS, n), dim3(64), 0, b->stream, b->d_desc, k, wnew, h, stride, log_index, epoch); else
+#define CASE(N, V) K_EMAP_UPDATE_NT_FORMS(CASE_NT, N, V)
+        K_EMAP_FORMS(CASE) return no_form("k_emap_update");
+#undef CASE
+#undef CASE_NT
     }
     if (full_rebuild) {
         ProfScope ps("dp_sweep", b->stream, 9.0 * wnew * h * n);
@@ -1649,7 +1572,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
     // "plain": delta_x = 1 and no rigidity mask that matters -- every fast kernel.  delta_x = 2 and rigidity masks run on the
     // tiled full-width update (k_dp_tile_p's general instantiations) whenever its grid fits; only beyond that do they fall
     // to the one-wave-per-image band kernel and the one-workgroup-per-image sweep (measured at 8K: 37x slower)
-    const bool rigm = has_rigmask && p->use_rigidity;
+    const bool rigm = rigmask_matters(b, p->use_rigidity);
     const bool fast_ok = p->delta_x == 1 && !rigm && g_update_mode != 3;
     const bool tiled_update = fast_ok ? ((g_update_mode < 0 ? (size_t) n * (size_t) w * (size_t) h <= (size_t) g_tiled_update_px : g_update_mode == 1) &&
                                          dp_persistent_ok(b, w))
@@ -1692,21 +1615,21 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
     if (band_tw) {
         ProfScope ps("band_update", b->stream, 0);
         CENSUS(LQRHIP_CENSUS_BAND_TW);
-#define LAUNCH_TW(LRV, RIGV) hipLaunchKernelGGL((k_band_update_tw<4, LRV, RIGV>), dim3(n), dim3(128 * 4), (size_t) 2 * h * sizeof(int), b->stream, b->d_desc, k, wnew, h, stride, g_dev_err)
-        if (leftright_next) { if (p->use_rigidity) LAUNCH_TW(true, true); else LAUNCH_TW(true, false); }
-        else { if (p->use_rigidity) LAUNCH_TW(false, true); else LAUNCH_TW(false, false); }
-#undef LAUNCH_TW
+#define CASE(LRV, RIGV) if ((leftright_next != 0) == LRV && (p->use_rigidity != 0) == RIGV) hipLaunchKernelGGL((k_band_update_tw<4, LRV, RIGV>), dim3(n), dim3(128 * 4), (size_t) 2 * h * sizeof(int), b->stream, b->d_desc, k, wnew, h, stride, g_dev_err); else
+        K_LR_RIG_FORMS(CASE) return no_form("k_band_update_tw");
+#undef CASE
         // (round 5: the kernel finishing the rows its window cannot hold itself, without the (almost always empty) k_dp_sweep<UPDATE>
         // launch behind it, was built and measured on one box: 527.5 / 523.5 k against 531 / 528 k -- the launch's 22 us reappear in
         // the kernels around it (k_vpath1 74 -> 92 us, k_carve 149 -> 162), the step is not the sum of a chain's kernels; removed)
     } else if (fast_band) {
         ProfScope ps("band_update", b->stream, 0);
-#define LAUNCH_MW(NWV, LRV, RIGV) do { CENSUS(NWV == 16 ? LQRHIP_CENSUS_BAND_MW16 : LQRHIP_CENSUS_BAND_MW8); hipLaunchKernelGGL((k_band_update_mw<2, NWV, 8, LRV, RIGV>), dim3(n), dim3(64 * NWV), (size_t) h * sizeof(int), b->stream, b->d_desc, k, wnew, h, stride); } while (0)
-#define LAUNCH_MW_N(LRV, RIGV) do { if (wnew > 4200) LAUNCH_MW(16, LRV, RIGV); /* 8K: dirty regions up to ~900 px */ else LAUNCH_MW(8, LRV, RIGV); } while (0)
-        if (leftright_next) { if (p->use_rigidity) LAUNCH_MW_N(true, true); else LAUNCH_MW_N(true, false); }
-        else { if (p->use_rigidity) LAUNCH_MW_N(false, true); else LAUNCH_MW_N(false, false); }
-#undef LAUNCH_MW_N
-#undef LAUNCH_MW
+        const int nw = wnew > 4200 ? 16 : 8;           // waves (8K: dirty regions up to ~900 px)
+        CENSUS(nw == 16 ? LQRHIP_CENSUS_BAND_MW16 : LQRHIP_CENSUS_BAND_MW8);
+#define CASE_NW(NWV, LRV, RIGV) if (nw == NWV && (leftright_next != 0) == LRV && (p->use_rigidity != 0) == RIGV) hipLaunchKernelGGL((k_band_update_mw<2, NWV, 8, LRV, RIGV>), dim3(n), dim3(64 * NWV), (size_t) h * sizeof(int), b->stream, b->d_desc, k, wnew, h, stride); else
+#define CASE(LRV, RIGV) CASE_NW(8, LRV, RIGV) CASE_NW(16, LRV, RIGV)
+        K_LR_RIG_FORMS(CASE) return no_form("k_band_update_mw");
+#undef CASE
+#undef CASE_NW
     } else {
         ProfScope ps("band_update", b->stream, 0);
         CENSUS(LQRHIP_CENSUS_BAND_GENERIC);

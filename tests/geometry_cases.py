@@ -73,7 +73,7 @@ def rigm(case):
 
 
 def sweep_form(case, update, w):
-    """launch_dp: k_dp_sweep's threads (nth) and px per thread (the LAUNCH_DP chain); None: its last else, refused"""
+    """launch_dp: k_dp_sweep's threads (nth) and px per thread (the first of K_DP_SWEEP_PXT_FORMS that covers the row); None: past the last, refused"""
     nth = 256 if (update and hook(case, "sweep_threads", 256) == 256 and w <= 16 * 256) else DP_THREADS
     pxt = (w + nth - 1) // nth
     for p in (1, 2, 4, 8, 16):
@@ -111,7 +111,7 @@ def levels_ok(case, w, h, delta):
 
 
 def band_form(case, wnew, h):
-    """seam_step_impl (fast_band, band_tw, LAUNCH_MW_N): which band kernel an update that reached the band kernels runs"""
+    """seam_step_impl (fast_band, band_tw, nw): which band kernel an update that reached the band kernels runs"""
     mode, delta = hook(case, "update_mode", -1), case["kw"].get("delta_x", 1)
     fast_ok = delta == 1 and not rigm(case) and mode != 3
     fast_band = fast_ok and h * 4 <= 60 * 1024
@@ -245,7 +245,7 @@ THRESHOLDS = {
                            lambda c: 4096 if (_band_case(c) or _levels_case(c)) else None, _wnews, True),
     "band_tw_width_4200": ("seam_step_impl: band_tw, wnew <= 4200",
                            lambda c: 4200 if _band_case(c) and _mode(c) == 0 and _delta(c) == 1 and not rigm(c) else None, _wnews, True),
-    "band_mw_waves_4200": ("seam_step_impl: LAUNCH_MW_N, wnew > 4200 -> 16 waves",
+    "band_mw_waves_4200": ("seam_step_impl: nw, wnew > 4200 -> 16 waves",
                            lambda c: 4200 if _band_case(c) and _mode(c) == 2 and _delta(c) == 1 and not rigm(c) else None, _wnews, True),
     "sweep_px_lds_8192": ("launch_dp: pxt <= 8, lds > 64 KB",
                           lambda c: 8192 if _band_case(c) else None, _wnews, True),

@@ -162,18 +162,17 @@ def test_mid_manifest_lists_every_vector_with_its_checksum_and_size_limits():
 
 def kernel_constants():
     """EU_ROWS, EU_LOGB, FROZEN_LAG_MAX and the delta_x thresholds of k_emap_update's instantiations (both forms of the working
-    plane go through the one launch macro), from the sources"""
+    plane go through the one function, eu_samples), from the sources"""
     common = open(os.path.join(CSRC, "lqr_common.h")).read()
     shim = open(os.path.join(CSRC, "lqr_shim.hip")).read()
     K = {}
     for name, src in (("EU_ROWS", common), ("EU_LOGB", common), ("FROZEN_LAG_MAX", shim)):
         (K[name],) = {int(v) for v in re.findall(r"^#define\s+%s\s+(\d+)" % name, src, re.M)}
-    (m,) = re.findall(r"#define LAUNCH_EUPD\(N\) do \{ if \(p->delta_x <= (\d+)\) LAUNCH_EUPD_NT\(N, (\d+)\); "
-                      r"else if \(p->delta_x <= (\d+)\) LAUNCH_EUPD_NT\(N, (\d+)\); else LAUNCH_EUPD_NT\(N, (\d+)\); \}", shim)
+    (m,) = re.findall(r"constexpr int eu_samples\(int delta_x\) \{ return delta_x <= (\d+) \? (\d+) : delta_x <= (\d+) \? (\d+) : (\d+); \}", shim)
     a, na, b, nb, nc = map(int, m)
     K["NT"] = [(a, na), (b, nb), (10 ** 9, nc)]
-    # the lag of a group: a quarter up to 4 carvers (both places the seam loop decides it)
-    assert len(re.findall(r"const int lag_max = n <= 4 \? FROZEN_LAG_MAX / 4 : FROZEN_LAG_MAX;", shim)) == 2
+    # the lag of a group: a quarter up to 4 carvers (the one helper both places of the seam loop call)
+    assert len(re.findall(r"const int lag_max = n <= 4 \? FROZEN_LAG_MAX / 4 : FROZEN_LAG_MAX;", shim)) == 1
     # the chunk of every rank loop a deep carver runs: k_wk_init_visible and k_frozen_catchup; k_vs_commit, k_inflate, k_compact, k_compact_jobs
     for unit, loops in (("k_energy.hip", 2), ("k_oneoff.hip", 4)):
         src = open(os.path.join(CSRC, unit)).read()
