@@ -1,6 +1,6 @@
 // lqr_common.h -- what every translation unit of the gfx950 engine shares: the device descriptors and the
 // origin-advanced plane view, the exactly-rounded arithmetic helpers and the energy function, the DP row (dp_row4 / dp_row /
-// dp_row_g) that all the halo kernels run, and the geometry constants of the tiled kernels that their launchers need.
+// dp_row_g) that all the halo kernels run.  The geometry constants of the tiled kernels that their launchers need too are in lqr_plan.h.
 //
 // Translation units (one per stage, so that a change to one protocol rebuilds -- and re-register-allocates -- only that one):
 //   k_energy.hip     E1/E2/E3/E4/E6  k_wk_init(_visible), k_mask_add, k_emap_full, k_emap_update, k_frozen_catchup
@@ -13,6 +13,7 @@
 //   k_masks.hip      E2 (lqr_masks.h) k_mask_add_f (float / double masks, host or device), k_mask_scatter (queued _xy calls), k_plane_transpose
 //   k_energy_out.hip energy read-outs (lqr_energy.h) k_energy_range (squash, min / max per workgroup), k_energy_out (normalise, expand to pixels, image orientation)
 //   lqr_shim.hip     the lqrhip_* C ABI of include/lqr_hip.h: allocation cache, batches, the per-seam launch sequence
+//   lqr_plan.h       which form of each stage that sequence runs (plain C++17, no HIP: also compiled alone by tests/test_plan.py)
 // lqr_kernels.h declares every kernel for the shim; each kernel file instantiates the templates the shim launches.
 // lqr_pixel.h (k_energy.hip, k_oneoff.hip): the packed 8-bit and the value / deep form of a pixel as compile-time policies, so that
 // every kernel that touches pixels exists once and serves 8-bit grey / RGB carvers and those of any other depth, type or channel count
@@ -56,6 +57,7 @@
 #include <unistd.h>
 
 #include "../../include/lqr_hip.h"
+#include "lqr_plan.h"        // the geometry constants of the tiled kernels and the launch shim's choices, plain C++
 
 // ---------------------------------------------------------------------------
 // constants / descriptors
@@ -72,7 +74,6 @@
 #define FLAG_SIDE 5             // 0: the part right of the seam moves left; 1: the part left of it moves right
 #define FLAG_COUNT 8
 #define FLAG_WORDS 64           // size of a carver's flag block
-#define DP_THREADS 1024
 #define VPATH_THREADS 256
 #define BAND_PXL 4
 #define BAND_WIN (64 * BAND_PXL)
@@ -371,7 +372,7 @@ __device__ __forceinline__ void dp_row4(const float (&mp)[4], const float left, 
 }
 
 // dp_row4's arithmetic for PX (2 or 4) consecutive pixels per lane; lo / lnew hold PX back-pointer bytes.  With 2 pixels
-// per lane a row is ~33 instructions per wave instead of ~58, and twice as many waves cover the columns.
+// per lane a row is ~33 instructions per wave instead of ~58, and twice as many waves cover the columns (NOTES/rounds-1-5.md 4.5).
 template <int PX, bool LR, bool RIG, bool UPDATE, bool MASK>
 __device__ __forceinline__ void dp_row(const float (&mp)[PX], const float left, const float right, const float (&e)[PX], const float (&mo)[PX],
                                        const uint32_t lo, const bool (&in)[PX], const float rig_l, const float rig_r, float (&mc)[PX],
@@ -496,30 +497,6 @@ template <int PX> struct LaneVec;
 template <> struct LaneVec<2> { typedef float F __attribute__((ext_vector_type(2))); typedef uint16_t L; };
 template <> struct LaneVec<4> { typedef f32x4 F; typedef uint32_t L; };
 
-// ---- geometry of the persistent tiled kernels (k_tiles.hip), needed by their launchers too
-// PX pixels per lane (4, or 2 when the device has room for twice the tiles: half the instructions per wave and row):
-// a tile is 64 * PX columns of which the 16 outer lanes on each side are halo
-// `px` below is a geometry code: 2 / 4 = pixels per lane with 16 halo lanes per side; 3 (round 6) = 2 pixels per lane with 24 halo lanes per
-// side -- 32 own columns + 48-column halos, blocks of 48 rows: the hand-over through memory (a third of a 32-row level) is paid 45
-// times per 4K sweep instead of 68, for twice the tiles; used while every tile still has a compute unit to itself (single images)
-constexpr int dppx_px(int px) { return px == 3 ? 2 : px; }
-constexpr int dppx_hl(int px) { return px == 3 ? 24 : 16; }
-constexpr int dpp_halo(int px) { return dppx_hl(px) * dppx_px(px); }              // halo columns on each side = rows per block
-constexpr int dpp_own(int px) { return 64 * dppx_px(px) - 2 * dpp_halo(px); }     // columns a tile owns
-constexpr int dpp_ex_tile(int px) { return px == 3 ? 2 * dpp_own(3) : 2 * 2 * dpp_halo(px); }       // granules a tile publishes: [block parity][side: 0 to the left, 1 to the right][column]; px 3: [block parity][own column]
-constexpr int dpp_rb(int px, int delta) { return delta >= 5 ? dpp_halo(2) / delta : delta >= 3 ? 8 : dpp_halo(px) / delta; }      // rows per block (delta_x 5 .. 10: 6, 5, 4, 4, 3, 3)
-constexpr int DPP_R = 16;                       // rows per batch
-constexpr int DPP_W = 2;                        // waves taking turns
-static_assert(dpp_halo(2) % (2 * DPP_R) == 0 && dpp_halo(4) % (2 * DPP_R) == 0, "a block (halo / delta_x rows, delta_x <= 2) is a whole number of batches");
-constexpr int DPP_BLK_BITS = 12;                // bits of the block index in a granule's tag
-#define DPT_ROWS 32
-#define DPT_OWN 192
-// k_band_levels (k_levels.hip): slots per image at most, tiles per image at most (one 64-bit mask: rows up to 4096 px)
-constexpr int LV_PMAX = 16;
-constexpr int LV_MAX_TILES = 64;
-constexpr int LV_MAX_LEVELS = 1020;       // levels per image at most (10 bits of the tags hold level + 1; 4K rows at delta_x 10: 720 levels of 3 rows)
-constexpr int lv_rows(int delta, bool rigm = false) { return delta == 1 ? (rigm ? 16 : 32) : delta == 2 ? 16 : delta <= 4 ? 8 : 32 / delta; }      // rows per level: halo (32 columns) / delta_x (a rigidity mask: 16, for the registers)
-constexpr int LQR_FAST_MAX_DELTA = 10;    // delta_x up to which the tiled kernels have instantiations (the plug-in's UI: src/interface.c:47, MAX_DELTA_X 10)
 
 // a job of the one-launch plane passes (inflate, flatten, transpose): one carver (root or attached) of a batch
 struct InflateDev {
@@ -546,11 +523,6 @@ struct DeepRead {
 #ifndef EU_LOGB
 #define EU_LOGB 8           // k_emap_update / k_carve_e: log entries fetched per round of the walk back to the frozen frame
 #endif
-// parallel backtrack (k_backtrack.hip, k_vp_*): a chunk is VP_REACH / delta_x rows, so that a path moves at most VP_REACH columns
-// inside a chunk (the displacement fits a byte); k_vp_solve walks VP_STAGE chunks per LDS-resident stage
-constexpr int VP_REACH = 56;
-constexpr int VP_STAGE = 20;        // (4K: 39 chunks = 2 stages; the cone of a stage is 2 * 56 * 20 columns wide: 45 KB of LDS)
-constexpr int vp_chunk_rows(int delta) { return VP_REACH / delta; }
 #define VP_ROWS 62
 // energy read-outs (k_energy_out.hip): a workgroup of k_energy_range takes EO_CHUNK pixels of a frame row at a time and there are at
 // most EO_MAX_PARTIALS of them (each leaves one min / max pair, which every workgroup of k_energy_out folds: 2 pairs per thread);

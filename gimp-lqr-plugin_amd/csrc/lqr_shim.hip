@@ -1,6 +1,6 @@
 // lqr_shim.hip -- the host side: the lqrhip_* C ABI of include/lqr_hip.h (plain pointers and sizes) on top of the kernels of
 // k_*.hip: device selection, the allocation cache, host <-> device transfers through a pinned ring, batches and their streams,
-// lqrhip_seam_step's per-seam launch sequence and the choice of update_mmap form, read-out, reset from device memory,
+// lqrhip_seam_step's per-seam launch sequence (which form of each stage it runs is lqr_plan.h's choice), read-out, reset from device memory,
 // the copy ceiling and the seam-map colour ramp.  The three kernels that live here (k_poison_random, k_copy16, k_vmap_ramp)
 // are debugging / measuring / one-off aids next to their only callers.
 #include "lqr_common.h"
@@ -23,11 +23,10 @@ static int *g_dev_err = nullptr;           // its device address
         }                                                                             \
     } while (0)
 
-// co-residency bounds for the spin waits of the persistent kernels, set from the occupancy queries in lqrhip_init (dpp_resident_workgroups)
-static int g_dpp_max_wgs_plain = 0, g_dpp_max_wgs_general = 0;      // ... of the plain / the delta_x = 2..4, rigidity-mask instantiations
-static int g_dpp_max_wgs_px4 = 0;                                   // ... of the plain 4-px instantiations alone (fewer registers than the 2-px ones)
-static int g_dpp_max_wgs_levels = 0;                                // ... of k_band_levels
-static int g_n_cu = 0;
+// What lqr_plan.h chooses from: the knobs of the lqrhip_set_* hooks, and what the device said -- the co-residency bounds for the spin
+// waits of the persistent kernels, set from the occupancy queries in lqrhip_init (dpp_resident_workgroups)
+static PlanKnobs g_knobs;
+static PlanDevice g_dev;
 
 // ===========================================================================
 // host side of the shim
@@ -77,7 +76,6 @@ struct LqrHipBatch {
 };
 static void discard_pending(LqrHipBatch *b);
 static bool g_no_spin = false;             // set by a spin time-out (check_dev_error): the process stays on the non-spinning kernels
-static inline bool no_spin(const LqrHipBatch *b) { return b->safe || g_no_spin; }
 
 struct ProfRec {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
@@ -122,13 +120,13 @@ static void dpp_resident_workgroups(int dev)
     K_BAND_LEVELS_FORMS(QUERY)
 #undef QUERY
     auto bound = [&](int blocks) { return std::max(0, blocks - 1) * prop.multiProcessorCount; };
-    g_n_cu = prop.multiProcessorCount;
+    g_dev.n_cu = prop.multiProcessorCount;
     // the plain 2-px instantiations stage a whole 32-row block (193 VGPRs): their bound is lower, and a grid that is too large for
     // them but fits the 4-px ones must not be sent to k_dp_tile for it.  The general ones (2 px per lane only) hold more registers still
-    g_dpp_max_wgs_px4 = bound(per_cu[PX4]);
-    g_dpp_max_wgs_plain = bound(std::min(per_cu[PX4], per_cu[PLAIN]));
-    g_dpp_max_wgs_general = bound(per_cu[GENERAL]);
-    g_dpp_max_wgs_levels = bound(per_cu[LEVELS]);
+    g_dev.wgs_px4 = bound(per_cu[PX4]);
+    g_dev.wgs_plain = bound(std::min(per_cu[PX4], per_cu[PLAIN]));
+    g_dev.wgs_general = bound(per_cu[GENERAL]);
+    g_dev.wgs_levels = bound(per_cu[LEVELS]);
 }
 
 // Large lock-step groups are carved on 4 streams, and those need hardware queues of their own: the HIP runtime's
@@ -156,8 +154,7 @@ static bool kfd_is_open(void)
 }
 __attribute__((constructor)) static void lqrhip_on_load(void)
 {
-    if (getenv("GPU_MAX_HW_QUEUES") || kfd_is_open()) return;
-    setenv("GPU_MAX_HW_QUEUES", "8", 0);
+    if (!kfd_is_open()) setenv("GPU_MAX_HW_QUEUES", "8", 0);        // (0: a value that is set stays)
 }
 
 extern "C" int lqrhip_init(void)
@@ -859,23 +856,13 @@ extern "C" int lqrhip_read_mask_plane(LqrHipCarver *c, int is_rigmask, int trans
 // launch of 16 images takes 0.20 ms next to the others' kernels (2.6 TB/s algorithmic) instead of 0.13 ms alone -- and
 // it needs a hardware queue per stream: with the HIP runtime's default of 4 queues per process (GPU_MAX_HW_QUEUES) the
 // streams share queues and the same split is 30 % SLOWER.  lqrhip_set_sub_batches (bench.py --sub-batches) pins the
-// number of streams; the default is automatic (lqrhip_sub_batches below).  DESIGN.md 4.11.
-static int g_sub_batches = 0;           // 0: automatic (below)
-extern "C" void lqrhip_set_sub_batches(int n) { g_sub_batches = n > 0 ? n : 0; }
-// Streams a lock-step group of n carvers is split over.  Automatic: 4 for groups of 49 and more, 2 for 32 to 48 (round 5) WHEN the process has the
-// hardware queues for them -- the HIP runtime's GPU_MAX_HW_QUEUES (default 4, read when HIP initialises, shared with every
-// other stream of the process) must be 8 or more; with fewer, streams share queues and the split is 30 % slower than
-// one stream, so it is not made.
+// number of streams; the default is automatic (plan_streams).  NOTES/rounds-1-5.md 4.11.
+extern "C" void lqrhip_set_sub_batches(int n) { g_knobs.sub_batches = n > 0 ? n : 0; }
 extern "C" int lqrhip_sub_batches(int n)
 {
-    int nb = g_sub_batches;
-    if (nb == 0) {
-        const char *q = getenv("GPU_MAX_HW_QUEUES");
-        // 4 streams for the groups that run k_band_update_tw (49 images and more), 2 for the groups of 32 to 48 that run k_band_levels
-        // (round 5, one box, Mseams*px/s with 2 / 4 streams: 32 images 360 / 352 k, 48 images 432 / 404 k)
-        nb = (q && atoi(q) >= 8) ? (n >= 49 ? 4 : n >= 32 ? 2 : 1) : 1;
-    }
-    return n >= 2 * nb ? nb : 1;
+    const char *q = getenv("GPU_MAX_HW_QUEUES");        // (at every call: a host may still set it until the GPU runtime comes up)
+    g_dev.hw_queues = q ? atoi(q) : 0;
+    return plan_streams(g_knobs, g_dev, n);
 }
 
 extern "C" void lqrhip_batch_set_shared(LqrHipBatch *b, int shared) { b->shared = shared != 0; b->shared_n = shared > 1 ? shared : 1; }
@@ -990,34 +977,6 @@ struct ProfScope {
 };
 
 extern "C" void lqrhip_prof_enable(int on) { g_prof = on; }
-static int g_vpath_mode = -1;            // -1: the parallel backtrack for groups up to g_vpath_par_max images of at least g_vpath_min_rows rows; 0: never; 1: always (delta_x 1 .. 4)
-static int g_vpath_par_max = 3, g_vpath_min_rows = 1000;     // (3 x 4K: 58 -> 46 us per seam; 4: equal; 8: slower -- the maps of n images are n times the work)
-extern "C" void lqrhip_set_vpath_mode(int mode, int par_max) { g_vpath_mode = mode; if (par_max > 0) g_vpath_par_max = par_max; }
-static int g_sweep_threads = 256;        // threads of the k_dp_sweep<UPDATE> launch behind the band kernels (256, or 1024 as in rounds 1 - 5)
-extern "C" void lqrhip_set_sweep_threads(int n) { g_sweep_threads = n == 256 ? 256 : DP_THREADS; }
-static int g_carve_fused = 4;            // k_carve_e (carve + energy update in one launch) for groups up to this many images (0: the two kernels always)
-extern "C" void lqrhip_set_carve_fused(int max_images) { g_carve_fused = max_images == 1 ? 4 : max_images < 0 ? 0 : max_images; }
-static int g_update_mode = -1;
-static int g_band_levels = -1;           // k_band_levels: -1 automatic; 0 never; n: n slots per image (lqrhip_set_band_levels)
-// -1: by batch size (g_tiled_update_px); 0: band kernel (k_band_update_tw); 1: tiled full-width update whenever its
-// grid fits; 2: the per-row-barrier band kernel (k_band_update_mw); 3: the generic one-wave band kernel + sweep
-// (what delta_x > 2 runs on), whatever the parameters
-extern "C" void lqrhip_set_update_mode(int mode) { g_update_mode = mode; }
-static int g_dpp_limit_override = -1;
-static int g_dpp_px_override = 0;       // test hook: 2 or 4 pins the persistent sweep's pixels per lane (0 = by batch size)
-extern "C" void lqrhip_set_dp_persistent_px(int px) { g_dpp_px_override = (px == 2 || px == 3 || px == 4) ? px : 0; }
-// -1: the occupancy-derived bound (dpp_resident_workgroups); >= 0: at most that many workgroups for the persistent
-// tiled sweep -- 0 sends every full DP to k_dp_tile and every incremental update to a band kernel
-extern "C" void lqrhip_set_dp_persistent_limit(int workgroups) { g_dpp_limit_override = workgroups; }
-static inline int dpp_limit(int bound) { return g_dpp_limit_override >= 0 ? std::min(g_dpp_limit_override, bound) : bound; }     // a residency bound under that cap
-static bool has_rigmask(const LqrHipBatch *b)
-{
-    bool any = false;
-    for (auto *c : b->cs) any |= (c->rig != nullptr);
-    return any;
-}
-// `rigm`: a rigidity mask that matters to the batch's DP (without rigidity the mask multiplies nothing)
-static inline bool rigmask_matters(const LqrHipBatch *b, bool use_rig) { return use_rig && has_rigmask(b); }
 extern "C" void lqrhip_prof_reset(void)
 {
     for (auto &kv : g_profrec) for (auto &e : kv.second.ev) { (void) hipEventDestroy(e.first); (void) hipEventDestroy(e.second); }
@@ -1167,53 +1126,29 @@ static int launch_dp_tiled(LqrHipBatch *b, const DpK &k, int w, int h, int lr)
     return 0;
 }
 
-// can the persistent tiled sweep (k_dp_tile_p) take this batch?  Its tiles spin on each other, so the
-// whole grid has to be resident at once.
-// Pixels per lane of the persistent sweep for this batch: 2 while twice the tiles still fit the residency bound (the row
-// chain is then ~33 instructions per wave instead of ~58; measured per 4K seam round, 2 vs 4 px per lane:
-// 1 image 0.40 / 0.50 ms, 4: 0.45 / 0.55, 8: 0.58 / 0.62, 12: 0.76 / 0.77), else 4, 0 = not at all.
-// `general`: delta_x = 2 and / or a rigidity mask (with rigidity): those instantiations exist for 2 px per lane only
-static int dp_persistent_px(const LqrHipBatch *b, int w, bool general = false, int delta = 1, int count = -1)
+// ---- the choice of kernel forms: lqr_plan.h decides, from these ------------------------------------------------------------------
+// The test hooks' argument mappings (include/lqr_hip.h); what each knob does is said at its field of PlanKnobs
+extern "C" void lqrhip_set_vpath_mode(int mode, int par_max) { g_knobs.vpath_mode = mode; if (par_max > 0) g_knobs.vpath_par_max = par_max; }
+extern "C" void lqrhip_set_sweep_threads(int n) { g_knobs.sweep_threads = n == 256 ? 256 : DP_THREADS; }
+extern "C" void lqrhip_set_carve_fused(int max_images) { g_knobs.carve_fused = max_images == 1 ? 4 : max_images < 0 ? 0 : max_images; }
+extern "C" void lqrhip_set_update_mode(int mode) { g_knobs.update_mode = mode; }
+extern "C" void lqrhip_set_dp_persistent_px(int px) { g_knobs.dpp_px = (px == 2 || px == 3 || px == 4) ? px : 0; }
+// (0 sends every full DP to k_dp_tile and every incremental update to a band kernel)
+extern "C" void lqrhip_set_dp_persistent_limit(int workgroups) { g_knobs.dpp_limit = workgroups; }
+extern "C" void lqrhip_set_band_levels(int slots) { g_knobs.band_levels = slots; }
+static PlanBatch plan_batch(const LqrHipBatch *b)
 {
-    if (b->shared || no_spin(b)) return 0;
-    const int bound = general ? g_dpp_max_wgs_general : g_dpp_max_wgs_plain;
-    const int limit = dpp_limit(bound);
-    const size_t n = count < 0 ? b->cs.size() : (size_t) count;
-    const int hh = b->cs[0]->wk_h;                            // the block index is DPP_BLK_BITS bits of the granule tag
-    const int maxblk = (1 << DPP_BLK_BITS) - 1;
-    // px code 3 (round 6): 32-column tiles with 48-column halos, 48-row blocks -- a third fewer hand-overs through memory for twice the
-    // tiles; while every tile still gets a compute unit of its own (a single 4K image: 120 tiles; measured: DESIGN.md 4.2)
-    if (!general && delta == 1 && (g_dpp_px_override == 3 || g_dpp_px_override == 0) && hh <= maxblk * dpp_rb(3, 1) &&
-        (size_t) ((w + dpp_own(3) - 1) / dpp_own(3)) * n <= (size_t) std::min(limit, g_dpp_px_override == 3 ? limit : g_n_cu)) return 3;
-    if ((general || (g_dpp_px_override != 4 && g_dpp_px_override != 3)) && hh <= maxblk * dpp_rb(2, delta) && (size_t) ((w + dpp_own(2) - 1) / dpp_own(2)) * n <= (size_t) limit) return 2;
-    const int limit4 = dpp_limit(g_dpp_max_wgs_px4);
-    if (!general && g_dpp_px_override != 2 && g_dpp_px_override != 3 && hh <= maxblk * dpp_halo(4) && (size_t) ((w + dpp_own(4) - 1) / dpp_own(4)) * n <= (size_t) limit4) return 4;
-    return 0;
+    PlanBatch pb;
+    pb.images = (int) b->cs.size(); pb.shared = b->shared; pb.shared_n = b->shared_n; pb.spin = !(b->safe || g_no_spin);
+    pb.wk_h = b->cs[0]->wk_h; pb.value = reads_value(b->cs[0]);
+    for (auto *c : b->cs) pb.rigmask |= c->rig != nullptr;
+    return pb;
 }
-static bool dp_persistent_ok(const LqrHipBatch *b, int w) { return dp_persistent_px(b, w) != 0; }
-// How many images of frame width `w` (the direction being carved) one lock-step batch may hold and still run delta_x = 2 /
-// rigidity-mask carvers on the tiled kernels (k_dp_tile_p's general instantiations: one workgroup per 64 columns per image,
-// all co-resident).  Beyond it such a batch would fall to the one-wave-per-image band kernel (~30x slower), so the host
-// carves larger batches of such carvers group after group (host/lqr_carver.c, lqrx_carver_resize_batch).  0: no bound known.
-extern "C" int lqrhip_general_batch_limit_delta(int w, int delta);
-extern "C" int lqrhip_general_batch_limit(int w) { return lqrhip_general_batch_limit_delta(w, 2); }
 extern "C" int lqrhip_general_batch_limit_delta(int w, int delta)
 {
-    if (lqrhip_init() < 0 || w < 1) return 0;
-    const int limit = dpp_limit(g_dpp_max_wgs_general);
-    const int tiled = limit / ((w + dpp_own(2) - 1) / dpp_own(2));
-    // round 5: groups of 8 and more such carvers run on k_band_levels (7 or more slots per image, rows up to 4096 px), which takes
-    // far larger groups than the full-width tiled kernels; its full DPs (3 per resize) then go to k_dp_sweep, one workgroup per image
-    // (delta_x 5 .. 10, round 6: the full-width tiled kernels only -- a change moves up to ten columns per row, the band is the whole
-    // width after a few hundred rows and the level kernel's images stop at a collision: 16 x 4K at delta_x 8 spent 6.6 of 9.6 ms per seam
-    // in the sweep that takes over)
-    if (delta <= 4 && g_band_levels != 0 && g_update_mode < 0 && (w + 63) / 64 <= LV_MAX_TILES) {
-        const int lim_lv = dpp_limit(g_dpp_max_wgs_levels);
-        const int lv = lim_lv / 7;
-        if (lv >= 8) return std::max(tiled, lv);
-    }
-    return tiled;
+    return lqrhip_init() < 0 || w < 1 ? 0 : plan_general_batch_limit(g_knobs, g_dev, w, delta);         // 0: no bound known
 }
+extern "C" int lqrhip_general_batch_limit(int w) { return lqrhip_general_batch_limit_delta(w, 2); }
 
 // Grow and (re)lay a batch's exchange area for a spinning kernel: `need_elems` words for `ntiles` tiles of each of `n` images, in the
 // layout `layout` (k_dp_tile_p: its px code; k_band_levels: 103, that kernel's own layout and tags).  Tags and finished-tile
@@ -1239,23 +1174,20 @@ static int exch_ensure(LqrHipBatch *b, size_t need_elems, int ntiles, int n, int
 // The <LR, RIG, DELTA, RIGM> of the spinning DP kernels (k_dp_tile_p, k_band_levels) for a batch's run-time values.
 // delta_x 5 .. 10 (round 6): the rigidity form only -- without rigidity the host's table is all zeros, and x + 0.0f is x for every
 // candidate (no cumulative minimum is -0.0f: energies are sums of non-negative gradients and finite biases).
-// A mask matters with rigidity only (rigmask_matters), so a mask at delta_x 1 is <true, true, 1, true> and nothing else.
+// A mask matters with rigidity only (PlanBatch::rigm), so a mask at delta_x 1 is <true, true, 1, true> and nothing else.
 struct DpForm { bool lr, rig; int delta; bool rigm; };
 static inline DpForm dp_form(const DpK &k, int lr, bool rigm) { return DpForm{lr != 0, k.use_rig != 0 || k.delta >= 5, k.delta, rigm}; }
 
-// E5 (UPDATE = false) or the full-width form of E9 (UPDATE = true) as one persistent launch
+// E5 (UPDATE = false) or the full-width form of E9 (UPDATE = true) as one persistent launch in the plan's geometry
 // (first, count): a range of the batch's images (E5 only: a general batch too large for one persistent grid is swept group after group)
 template <bool UPDATE>
-static int launch_dp_persistent(LqrHipBatch *b, const DpK &k, int w, int h, int lr, int first = 0, int count = -1)
+static int launch_dp_persistent(LqrHipBatch *b, const DpK &k, const DpPlan &dp, bool rigm, int w, int h, int lr, int first, int count)
 {
     LqrHipCarver *c0 = b->cs[0];
-    const size_t n = count < 0 ? b->cs.size() : (size_t) count;
-    if (UPDATE && count >= 0) return LQRHIP_EARG;
-    const bool rigm = rigmask_matters(b, k.use_rig);
-    const bool general = k.delta != 1 || rigm;
-    if (k.delta < 1 || k.delta > LQR_FAST_MAX_DELTA) return LQRHIP_EARG;
-    const int px = dp_persistent_px(b, w, general, k.delta, count);
-    if (!px) return LQRHIP_EARG;
+    const size_t n = (size_t) count;
+    const int px = dp.px;
+    const bool general = dp.general;
+    if (!px || (UPDATE && n != b->cs.size())) return LQRHIP_EARG;
     const int ntiles = (w + dpp_own(px) - 1) / dpp_own(px);
     int rc;
     const size_t need_elems = 2 * ((size_t) ntiles * dpp_ex_tile(px) + 8) * n;      // (granules + finished-tile counter, and the near copies: k_tiles.hip)
@@ -1283,7 +1215,7 @@ static int launch_dp_persistent(LqrHipBatch *b, const DpK &k, int w, int h, int 
     const int epoch = 1 + ((b->tile_epoch++) % ((1 << (31 - DPP_BLK_BITS)) - 2));          // never 0; above the block index in the 32-bit tag
     const dim3 grid(ntiles, (unsigned) n);
     CENSUS(general ? LQRHIP_CENSUS_TILE_P_GENERAL : px == 3 ? LQRHIP_CENSUS_TILE_P_G3 : px == 2 ? LQRHIP_CENSUS_TILE_P_G2 : LQRHIP_CENSUS_TILE_P_G4);
-    // px code 3 is 2 px per lane with the 24-halo-lane geometry; the general forms exist for 2 px per lane only (dp_persistent_px)
+    // px code 3 is 2 px per lane with the 24-halo-lane geometry; the general forms exist for 2 px per lane only (plan_persistent_px)
     const DpForm f = dp_form(k, lr, rigm);
     const int px_lane = px == 4 ? 4 : 2, hln = px == 3 ? 24 : 16;
     const bool found = [&] {
@@ -1304,48 +1236,33 @@ static int launch_dp_persistent(LqrHipBatch *b, const DpK &k, int w, int h, int 
     return 0;
 }
 
+// One DP launch sequence as planned (plan_full_dp, plan_seam_step): E5 (UPDATE = false) or what E9 runs over the full width
 template <bool UPDATE>
-static int launch_dp(LqrHipBatch *b, const DpK &k, int w, int h, int lr)
+static int launch_dp(LqrHipBatch *b, const DpK &k, const DpPlan &dp, bool rigm, int w, int h, int lr)
 {
     LqrHipCarver *c0 = b->cs[0];
-    if (!UPDATE) {
-        const bool rigm = rigmask_matters(b, k.use_rig);
-        if (k.delta == 1 && !rigm) return dp_persistent_ok(b, w) ? launch_dp_persistent<false>(b, k, w, h, lr) : launch_dp_tiled(b, k, w, h, lr);
-        if (k.delta >= 1 && k.delta <= LQR_FAST_MAX_DELTA && dp_persistent_px(b, w, true, k.delta)) return launch_dp_persistent<false>(b, k, w, h, lr);
-        // round 5: a general batch too large for one persistent grid (it runs its incremental updates on k_band_levels): the full DP
-        // group after group of as many images as fit, instead of one 1024-thread workgroup per image (k_dp_sweep: 4 - 8 ms per sweep
-        // of 16 x 4K against 2 x 0.5)
-        if (k.delta >= 1 && k.delta <= LQR_FAST_MAX_DELTA && !b->shared) {
-            const int total = (int) b->cs.size();
-            int per = total;
-            while (per > 1 && !dp_persistent_px(b, w, true, k.delta, per)) per = (per + 1) / 2;
-            if (dp_persistent_px(b, w, true, k.delta, per)) {
-                int rc;
-                for (int first = 0; first < total; first += per)
-                    if ((rc = launch_dp_persistent<false>(b, k, w, h, lr, first, std::min(per, total - first)))) return rc;
-                return 0;
-            }
-        }
+    if (dp.form == LQRHIP_CENSUS_DP_TILE) return launch_dp_tiled(b, k, w, h, lr);
+    if (dp.form != LQRHIP_CENSUS_SWEEP_FULL && dp.form != LQRHIP_CENSUS_SWEEP_UPDATE) {
+        const int total = (int) b->cs.size();
+        int rc;
+        for (int first = 0; first < total; first += std::max(dp.per, 1))
+            if ((rc = launch_dp_persistent<UPDATE>(b, k, dp, rigm, w, h, lr, first, std::min(dp.per, total - first)))) return rc;
+        return 0;
     }
-    // the launch behind a band kernel (UPDATE) almost always only looks at flags[FLAG_OVF_ROW]: 256 threads for rows up to 4096 px (a
-    // workgroup that finds room at once beside the sibling streams' kernels), 1024 for the full sweeps and wider rows
-    const int nth = (UPDATE && g_sweep_threads == 256 && w <= 16 * 256) ? 256 : DP_THREADS;
-    int pxt = (w + nth - 1) / nth;
-    size_t lds = (size_t) 2 * ((w + 3) & ~3) * sizeof(float);
     dim3 grid((unsigned) b->cs.size());
     auto launch = [&](auto kern, int P, int T) -> int {
-        if (lds > 64 * 1024) {
-            HIPCK(hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+        if (lds_needs_attr(dp.lds)) {
+            HIPCK(hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dp.lds));
             CENSUS(LQRHIP_CENSUS_LDS_ATTR_SWEEP);
         }
         CENSUS(LQRHIP_CENSUS_SWEEP + 2 * (P == 1 ? 0 : P == 2 ? 1 : P == 4 ? 2 : P == 8 ? 3 : 4) + (T == DP_THREADS ? 1 : 0));
         CENSUS(UPDATE ? LQRHIP_CENSUS_SWEEP_UPDATE : LQRHIP_CENSUS_SWEEP_FULL);
-        hipLaunchKernelGGL(kern, grid, dim3(T), lds, b->stream, b->d_desc, k, w, h, c0->stride, lr);
+        hipLaunchKernelGGL(kern, grid, dim3(T), dp.lds, b->stream, b->d_desc, k, w, h, c0->stride, lr);
         HIPCK(hipGetLastError());
         return 0;
     };
-    // the first listed px per thread that covers the row; only the update has the 256-thread forms
-#define CASE(P) if (pxt <= P) { if constexpr (UPDATE) { if (nth == 256) return launch(k_dp_sweep<P, true, 256>, P, 256); } return launch(k_dp_sweep<P, UPDATE, DP_THREADS>, P, DP_THREADS); }
+    // only the update has the 256-thread forms
+#define CASE(P) if (dp.px == P) { if constexpr (UPDATE) { if (dp.threads == 256) return launch(k_dp_sweep<P, true, 256>, P, 256); } return launch(k_dp_sweep<P, UPDATE, DP_THREADS>, P, DP_THREADS); }
     K_DP_SWEEP_PXT_FORMS(CASE)
 #undef CASE
     g_err = "image wider than 16384 px is not supported";
@@ -1358,15 +1275,10 @@ extern "C" int lqrhip_mmap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w,
     if ((rc = batch_upload(b))) return rc;
     if (p->delta_x > LQRHIP_MAX_DELTA) return LQRHIP_EARG;
     ProfScope ps("dp_sweep", b->stream, 9.0 * w * h * b->cs.size());
-    return launch_dp<false>(b, make_dpk(p, b->cs[0]->ch), w, h, leftright);
+    const PlanBatch pb = plan_batch(b);
+    const bool use_rig = p->use_rigidity != 0;
+    return launch_dp<false>(b, make_dpk(p, b->cs[0]->ch), plan_full_dp(g_knobs, g_dev, pb, w, p->delta_x, use_rig), pb.rigm(use_rig), w, h, leftright);
 }
-
-// brightness samples a row of k_emap_update takes (EU_NT): the window a seam of this delta_x can have moved
-constexpr int eu_samples(int delta_x) { return delta_x <= 2 ? 12 : delta_x <= 8 ? 36 : 68; }
-
-#ifndef FROZEN_LAG_MAX
-#define FROZEN_LAG_MAX 128      // seams the frozen planes may lag behind before they are compacted
-#endif
 
 // remove seams [epoch, to) from the frozen planes of every carver of the batch
 static int frozen_catchup(LqrHipBatch *b, int to, int w_at_to, int h)
@@ -1385,24 +1297,6 @@ static int frozen_catchup(LqrHipBatch *b, int to, int w_at_to, int h)
     return 0;
 }
 
-// Slots (workgroups) per image for k_band_levels (0: not usable here): as many as the group's images leave room for within the
-// residency bound, at most LV_PMAX; lqrhip_set_band_levels pins it (tests, experiments).  The default for large groups is 6:
-// the active tiles of a 4K level are 4.5 on average, a window of 6 consecutive tiles never collides, and 64 x 6 workgroups hold
-// half the registers of round 4's 64 x 12.
-extern "C" void lqrhip_set_band_levels(int slots) { g_band_levels = slots; }
-static int band_levels_P(const LqrHipBatch *b, int w, int h, int delta)
-{
-    if (no_spin(b) || g_band_levels == 0 || delta < 1 || delta > LQR_FAST_MAX_DELTA || (h + lv_rows(delta, true) - 1) / lv_rows(delta, true) > LV_MAX_LEVELS || (w + 63) / 64 > LV_MAX_TILES) return 0;
-    const int limit = dpp_limit(g_dpp_max_wgs_levels);
-    const int per_batch = limit / std::max(b->shared_n, 1);
-    int P = std::min(LV_PMAX, per_batch / (int) std::max<size_t>(b->cs.size(), 1));
-    // automatic: 12 slots while the group's workgroups stay below ~384 (beyond that the sibling kernels are starved of registers,
-    // 48 images with 10 slots 452 k, with 8 slots 479 k), never fewer than 7 (6 and fewer put second tiles on a slot in 9 % of the tile-levels)
-    const size_t group_images = b->cs.size() * (size_t) std::max(b->shared_n, 1);
-    const int want = g_band_levels > 0 ? g_band_levels : std::max(7, std::min(12, (int) (384 / std::max<size_t>(group_images, 1))));
-    P = std::min(P, want);
-    return P >= (g_band_levels > 0 ? 1 : 7) ? P : 0;
-}
 static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr, int P, bool rigm)
 {
     LqrHipCarver *c0 = b->cs[0];
@@ -1422,10 +1316,6 @@ static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr
     HIPCK(hipGetLastError());
     return 0;
 }
-// batches up to this many pixels use the tiled full-width update (measured break-even with the band kernel at 4K, Mseams*px/s
-// tiled / band: 7 images 118 k / 97 k, 8: 130 / 109, 9: 119 / 121, 12: 130 / 139+, 16: 158 / 175+)
-static const long long g_tiled_update_px = 8LL * 3840 * 2160;
-
 // One seam of a lock-step batch: k_vpath* (pick + backtrack, publishes the side to move) -> k_carve ->
 // k_emap_update -> one form of update_mmap (or the full DP after a side switch), all on the batch's stream.
 static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h, int log_index, int leftright_pick,
@@ -1476,22 +1366,15 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
     const int stride = c0->stride;
     const int wnew = w - 1;
     const int move_dp = (wnew > 1 && !full_rebuild) ? 1 : 0;
-    const bool rigmask = has_rigmask(b);
+    // every choice of this step (lqr_plan.h): the launches below are one case of the plan each
+    const PlanBatch pb = plan_batch(b);
+    const StepPlan s = plan_seam_step(g_knobs, g_dev, pb, p->delta_x, p->use_rigidity != 0, w, h, full_rebuild != 0, log_index + 1 - c0->frozen_epoch);
+    const bool rigm = pb.rigm(p->use_rigidity != 0);
     // bytes the carve moves per pixel of the side it moves, read + write: en 4 (+ m 4 + back pointer 1 unless a full DP follows,
     // + the rigidity mask 4) -- k_vpath* knows how many pixels that is for the seam it finds and keeps the sum (lqrhip_moved_bytes)
-    const int moved_unit = 2 * (4 + (move_dp ? 5 : 0) + (rigmask ? 4 : 0));
-    // Backtrack: for single images the two-kernel parallel form (k_vp_maps / k_vp_solve, k_backtrack.hip: the chip walks every column
-    // through every chunk of rows, the serial part is one step per chunk); for groups the one-wave-per-image walk, whose launches
-    // keep the chip busy anyway.  Measured on one box, us per seam with every kernel event-timed, k_vpath1 / parallel: 4K 70 / 41 (single4k
-    // 20.9 -> 22.7 k Mseams*px/s), 8K 108 / 64 (config 5 55.5 -> 60.8 k), FHD 32 / 30, 2 x 4K 57 / 44 (51.0 -> 53.4 k), 4 x 4K 59 / 61,
-    // 8 x 4K 60 / 79: each launch is ~10 us of dependent-dispatch latency, and the maps of n images are n times the work.
-    const size_t vp_group = (size_t) n * (size_t) std::max(b->shared_n, 1);
-    // delta_x 5 .. 10: always -- the one-wave walks there take 0.2 (k_vpath1<5>) to 1.15 ms (k_vpath, delta_x 10) per 4K seam, the parallel
-    // form ~0.06 whatever delta_x is (a chunk is 56 / delta_x rows, the cone of a stage as wide as at delta_x 1)
-    const bool use_vp = p->delta_x >= 1 && p->delta_x <= LQR_FAST_MAX_DELTA && h >= 2 && g_vpath_mode != 0 &&
-                        (g_vpath_mode == 1 || p->delta_x >= 5 || (vp_group <= (size_t) g_vpath_par_max && h >= g_vpath_min_rows));
-    if (use_vp) {
-        const int R = vp_chunk_rows(p->delta_x), nchunks = (h - 1 + R - 1) / R, R4 = (R + 3) / 4;
+    const int moved_unit = 2 * (4 + (move_dp ? 5 : 0) + (pb.rigmask ? 4 : 0));
+    if (s.backtrack == LQRHIP_CENSUS_VP_PARALLEL) {
+        const int nchunks = s.vp_chunks, R4 = (s.vp_rows + 3) / 4;
         const size_t need = (size_t) (nchunks + 1) * stride + 64;
         bool grew = false;
         for (auto *c : b->cs) {
@@ -1510,7 +1393,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
             })) return no_form("k_vp_maps");
     } else {
         ProfScope ps("vpath", b->stream, 0);
-        CENSUS(p->delta_x <= 7 ? LQRHIP_CENSUS_VPATH1 : LQRHIP_CENSUS_VPATH);
+        CENSUS(s.backtrack);
         // the one-wave walk: unrolled for the listed delta_x, the loop over candidates beyond (and for delta_x 0)
         if (!with_listed(K_VPATH1_FORMS, p->delta_x, [&](auto delta) {
                 hipLaunchKernelGGL(k_vpath1<delta>, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit);
@@ -1518,16 +1401,8 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
             hipLaunchKernelGGL(k_vpath, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, leftright_pick, p->delta_x,
                                log_index, moved_unit);
     }
-    // Single images and groups up to 4: the carve and the energy update in one launch (k_carve_e, k_carve.hip) -- the wave that has moved
-    // a row refreshes that row's energies; one dependent launch less per seam.  delta_x <= 2 (12 brightness samples per row).
-    // (value-plane carvers: the two kernels, k_carve and k_emap_update<.., true>)
-    // The frozen planes' lag.  The energy update walks the seam log back to the frozen frame (O(lag) per sample); compacting the frozen
-    // planes costs a pass over them.  Few images: the walk is on the critical path and the pass is cheap -> short lag
-    auto frozen_within_lag = [&]() -> int {
-        const int lag_max = n <= 4 ? FROZEN_LAG_MAX / 4 : FROZEN_LAG_MAX;
-        return log_index + 1 - c0->frozen_epoch > lag_max ? frozen_catchup(b, log_index + 1, wnew, h) : 0;
-    };
-    const bool fuse_e = p->delta_x <= 2 && vp_group <= (size_t) g_carve_fused && wnew > 1 && !reads_value(c0);
+    auto frozen_within_lag = [&]() -> int { return s.catchup ? frozen_catchup(b, log_index + 1, wnew, h) : 0; };
+    const bool fuse_e = s.carve == LQRHIP_CENSUS_CARVE_E;
     if (fuse_e) {
         if ((rc = frozen_within_lag())) return rc;      // (needs the seam log only: before the carve)
         const int epoch = c0->frozen_epoch;
@@ -1545,7 +1420,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
         CENSUS(LQRHIP_CENSUS_CARVE);
         hipLaunchKernelGGL(k_carve, dim3((h + 3) / 4, n), dim3(256), 0, b->stream, b->d_desc, w, h, stride, p->delta_x, move_dp);
     }
-    if (wnew <= 1) {            // liblqr's finish_vsmap case: nothing left to update
+    if (s.dp.form < 0) {        // liblqr's finish_vsmap case: nothing left to update
         HIPCK(hipGetLastError());
         return 0;
     }
@@ -1553,66 +1428,24 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
         ProfScope ps("emap_update", b->stream, 0);
         if ((rc = frozen_within_lag())) return rc;
         const int epoch = c0->frozen_epoch;
-        const bool value = reads_value(c0);
-        const int nrg = plane_nrg(value, nrg_index(p->nrg_func)), nt = eu_samples(p->delta_x);
+        const bool value = pb.value;
+        const int nrg = plane_nrg(value, nrg_index(p->nrg_func)), nt = s.eu_nt;
 #define CASE_NT(NT, N, V) if (nrg == N && value == V && nt == NT) hipLaunchKernelGGL((k_emap_update<N, NT, V>), dim3((h + EU_ROWS - 1) / EU_ROWS, n), dim3(64), 0, b->stream, b->d_desc, k, wnew, h, stride, log_index, epoch); else
 #define CASE(N, V) K_EMAP_UPDATE_NT_FORMS(CASE_NT, N, V)
         K_EMAP_FORMS(CASE) return no_form("k_emap_update");
 #undef CASE
 #undef CASE_NT
     }
-    if (full_rebuild) {
-        ProfScope ps("dp_sweep", b->stream, 9.0 * wnew * h * n);
-        if ((rc = launch_dp<false>(b, k, wnew, h, leftright_next))) return rc;
+    if (s.full || s.band < 0) {         // the full DP after a side switch, or E9 as the tiled full-width update: that launch alone
+        ProfScope ps(s.full ? "dp_sweep" : "dp_update_tiled", b->stream, s.full ? 9.0 * wnew * h * n : 0);
+        if ((rc = s.full ? launch_dp<false>(b, k, s.dp, rigm, wnew, h, leftright_next) : launch_dp<true>(b, k, s.dp, rigm, wnew, h, leftright_next))) return rc;
         HIPCK(hipGetLastError());
         return 0;
     }
-    // How E9 (update_mmap) runs.  Small batches: the whole chip recomputing every row (tiled full-width keep-rule
-    // sweep) beats the one-workgroup-per-image band walk; for large batches its 14 B/px of traffic would not.
-    // "plain": delta_x = 1 and no rigidity mask that matters -- every fast kernel.  delta_x = 2 and rigidity masks run on the
-    // tiled full-width update (k_dp_tile_p's general instantiations) whenever its grid fits; only beyond that do they fall
-    // to the one-wave-per-image band kernel and the one-workgroup-per-image sweep (measured at 8K: 37x slower)
-    const bool rigm = rigmask_matters(b, p->use_rigidity);
-    const bool fast_ok = p->delta_x == 1 && !rigm && g_update_mode != 3;
-    const bool tiled_update = fast_ok ? ((g_update_mode < 0 ? (size_t) n * (size_t) w * (size_t) h <= (size_t) g_tiled_update_px : g_update_mode == 1) &&
-                                         dp_persistent_ok(b, w))
-                                      : (p->delta_x >= 1 && p->delta_x <= LQR_FAST_MAX_DELTA && g_update_mode != 0 && g_update_mode != 2 && g_update_mode != 3 && dp_persistent_px(b, w, true, p->delta_x) != 0);
-    {
-        // round 5: the band on P slots per image, tiles assigned level by level (k_band_levels): the default for groups of 8 to 64
-        // images (measured, Mseams*px/s at 4K, levels / k_band_update_tw: 8 images 148 / 127, 16: 256 / 180, 48: 479 / 404).  64 images
-        // on four streams with 7 slots: alternating 3-step runs on three boxes 516 / 495-516, 497 / 488, 520 / 504; the driver's
-        // 20-step command on two boxes of equal speed (every other figure within 1 %) 567.2 / 538.9 k.  Its 448 workgroups stretch
-        // the sibling streams' carves (k_carve 172 -> 203 us per launch) while the whole step's share of the HBM roof rises (0.279
-        // -> 0.293).  96 images run 585 / 622: groups above 64 keep k_band_update_tw; update mode 0 / 5 force either
-        // round 5: also delta_x 2 .. 4 and rigidity masks (k_band_levels' general instantiations): a batch of such carvers used to be
-        // carved in groups of as many as the full-width tiled kernels hold (16 x 4K, delta_x 2: 68 k Mseams*px/s)
-        const size_t group_images = (size_t) n * (size_t) std::max(b->shared_n, 1);
-        const bool lv_ok = p->delta_x >= 1 && (p->delta_x <= 4 || g_update_mode == 5) && p->delta_x <= LQR_FAST_MAX_DELTA && g_update_mode != 3;        // (delta_x 5 .. 10: on request only, see lqrhip_general_batch_limit_delta)
-        const int PL = (lv_ok && (g_update_mode == 5 || (g_update_mode < 0 && group_images >= 8 && (group_images <= 64 || !fast_ok)))) ? band_levels_P(b, wnew, h, p->delta_x) : 0;
-        if (PL > 0) {
-            {
-                ProfScope ps("band_levels", b->stream, 0);
-                if ((rc = launch_band_levels(b, k, wnew, h, leftright_next, PL, rigm))) return rc;
-            }
-#ifndef LQR_EXP_NO_SWEEP        // (experiment builds only: what the almost always empty launch costs; results are wrong when an image stopped)
-            ProfScope ps("dp_update", b->stream, 0);
-            if ((rc = launch_dp<true>(b, k, wnew, h, leftright_next))) return rc;
-#endif
-            HIPCK(hipGetLastError());
-            return 0;
-        }
-    }
-    if (tiled_update) {
-        ProfScope ps("dp_update_tiled", b->stream, 0);
-        if ((rc = launch_dp_persistent<true>(b, k, wnew, h, leftright_next))) return rc;
-        HIPCK(hipGetLastError());
-        return 0;
-    }
-    const bool fast_band = fast_ok && (size_t) h * sizeof(int) <= 60 * 1024;
-    // the trapezoid-wave band kernel takes rows up to ~4200 px (wider rows: the changes outgrow its 896-column window
-    // too often, and an 8-slot build spills registers); beyond that, and in update mode 2, k_band_update_mw
-    const bool band_tw = fast_band && g_update_mode != 2 && wnew <= 4200 && (size_t) 2 * h * sizeof(int) <= 64 * 1024;
-    if (band_tw) {
+    if (s.band == LQRHIP_CENSUS_BAND_LEVELS) {
+        ProfScope ps("band_levels", b->stream, 0);
+        if ((rc = launch_band_levels(b, k, wnew, h, leftright_next, s.levels_P, rigm))) return rc;
+    } else if (s.band == LQRHIP_CENSUS_BAND_TW) {
         ProfScope ps("band_update", b->stream, 0);
         CENSUS(LQRHIP_CENSUS_BAND_TW);
 #define CASE(LRV, RIGV) if ((leftright_next != 0) == LRV && (p->use_rigidity != 0) == RIGV) hipLaunchKernelGGL((k_band_update_tw<4, LRV, RIGV>), dim3(n), dim3(128 * 4), (size_t) 2 * h * sizeof(int), b->stream, b->d_desc, k, wnew, h, stride, g_dev_err); else
@@ -1621,9 +1454,9 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
         // (round 5: the kernel finishing the rows its window cannot hold itself, without the (almost always empty) k_dp_sweep<UPDATE>
         // launch behind it, was built and measured on one box: 527.5 / 523.5 k against 531 / 528 k -- the launch's 22 us reappear in
         // the kernels around it (k_vpath1 74 -> 92 us, k_carve 149 -> 162), the step is not the sum of a chain's kernels; removed)
-    } else if (fast_band) {
+    } else if (s.band == LQRHIP_CENSUS_BAND_MW8 || s.band == LQRHIP_CENSUS_BAND_MW16) {
         ProfScope ps("band_update", b->stream, 0);
-        const int nw = wnew > 4200 ? 16 : 8;           // waves (8K: dirty regions up to ~900 px)
+        const int nw = s.band == LQRHIP_CENSUS_BAND_MW16 ? 16 : 8;
         CENSUS(nw == 16 ? LQRHIP_CENSUS_BAND_MW16 : LQRHIP_CENSUS_BAND_MW8);
 #define CASE_NW(NWV, LRV, RIGV) if (nw == NWV && (leftright_next != 0) == LRV && (p->use_rigidity != 0) == RIGV) hipLaunchKernelGGL((k_band_update_mw<2, NWV, 8, LRV, RIGV>), dim3(n), dim3(64 * NWV), (size_t) h * sizeof(int), b->stream, b->d_desc, k, wnew, h, stride); else
 #define CASE(LRV, RIGV) CASE_NW(8, LRV, RIGV) CASE_NW(16, LRV, RIGV)
@@ -1638,7 +1471,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
     {
         // rows the band kernel handed over (flags[FLAG_OVF_ROW] .. h): the keep rule over the full width
         ProfScope ps("dp_update", b->stream, 0);
-        if ((rc = launch_dp<true>(b, k, wnew, h, leftright_next))) return rc;
+        if ((rc = launch_dp<true>(b, k, s.dp, rigm, wnew, h, leftright_next))) return rc;
     }
     HIPCK(hipGetLastError());
     return 0;
@@ -1659,7 +1492,7 @@ extern "C" int lqrhip_vs_commit(LqrHipBatch *b, int w0, int h0, int wc0, int n_s
     // (unreachable while the host refuses frames wider than LQRHIP_MAX_FRAME_WIDTH, host/lqr_carver.c: a session carves at most wc0 - 1
     // seams, so n_seams + wc0 <= 2 * 16384 - 1 ints = 128 KB)
     if (lds > 150 * 1024) { g_err = "vs_commit: session too large for LDS"; return LQRHIP_EARG; }
-    if (lds > 64 * 1024) {
+    if (lds_needs_attr(lds)) {
         HIPCK(hipFuncSetAttribute((const void *) k_vs_commit, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
         CENSUS(LQRHIP_CENSUS_LDS_ATTR_COMMIT);
     }

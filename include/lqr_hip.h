@@ -1,7 +1,7 @@
 /*
  * lqr_hip.h -- thin C-ABI shim between the C host side of the engine
  * (gimp-lqr-plugin_amd/host/lqr_carver.c, which implements include/lqr.h) and
- * the hand-written gfx950 kernels (gimp-lqr-plugin_amd/csrc/lqr_hip.hip).
+ * the hand-written gfx950 kernels (gimp-lqr-plugin_amd/csrc/k_*.hip, launched by csrc/lqr_shim.hip).
  *
  * Plain pointers and sizes only; no C++ or torch types.  Each entry point names
  * the liblqr engine stage it replaces and the
@@ -21,8 +21,9 @@
  * Threading: like the plug-in's use of liblqr (GTK main loop / PDB run), the library
  * is single-threaded by contract -- the allocation cache, the error word and the
  * profiling records are process globals without locks, and the device is selected
- * (hipSetDevice) for the thread that first calls in.  No environment variable is read
- * except LOCAL_RANK.
+ * (hipSetDevice) for the thread that first calls in.  The environment holds no tuning knob: LOCAL_RANK selects
+ * the device, GPU_MAX_HW_QUEUES is looked at (lqrhip_sub_batches), LQRHIP_POISON* and LQRHIP_DUMP are debugging
+ * aids.
  */
 #ifndef LQR_HIP_H
 #define LQR_HIP_H
@@ -116,8 +117,8 @@ int lqrhip_read_mask_plane(LqrHipCarver *c, int is_rigmask, int transposed, floa
 unsigned long long lqrhip_debug_mask_flushes(void);
 
 /* -- batch ------------------------------------------------------------------ */
-/* into how many device batches (HIP streams) the host splits a lock-step group of n carvers.  Automatic (set 0): 4 for
- * groups of 32 carvers and more when the process has the hardware queues for them (the HIP runtime's GPU_MAX_HW_QUEUES
+/* into how many device batches (HIP streams) the host splits a lock-step group of n carvers.  Automatic (set 0): 2 for
+ * groups of 32 to 48 carvers, 4 for 49 and more, when the process has the hardware queues for them (the HIP runtime's GPU_MAX_HW_QUEUES
  * >= 8 in the environment before HIP initialises; its default of 4 makes the split 30 % slower than one stream, so it is
  * then not made), else 1.  The library sets the variable to 8 itself when it is loaded with the variable unset into a
  * process whose GPU runtime is not up yet.  lqrhip_set_sub_batches(n > 0) pins the number of streams. */
@@ -247,7 +248,8 @@ void lqrhip_prof_enable(int on);
 /* how E9 (update_mmap) runs: -1 by batch size (tiled full-width keep-rule sweep up to 8 4K images, the band
  * kernel k_band_update_tw above), 0 band kernel always, 1 tiled sweep whenever its grid fits the device,
  * 2 the per-row-barrier band kernel k_band_update_mw (the default for rows wider than 4200 px), 3 the generic
- * one-wave band kernel k_band_update + k_dp_sweep (what delta_x > 4 runs on) whatever the parameters, 5 k_band_levels
+ * one-wave band kernel k_band_update + k_dp_sweep (what delta_x 0 and delta_x > 10 run on, and delta_x 2 .. 10 / rigidity
+ * masks where the tiled update's grid does not fit) whatever the parameters, 5 k_band_levels
  * (4 was round 4's k_band_tiles, removed in round 6: it now behaves as 0) */
 void lqrhip_set_update_mode(int mode);
 /* Test hook: threads of the k_dp_sweep<UPDATE> launch behind the band kernels: 256 (default) or 1024 */

@@ -1,7 +1,8 @@
 """The launch shim's width and height thresholds, restated, and the cases that stand on both sides of each.
 
-csrc/lqr_shim.hip chooses kernels, thread counts, pixels per lane and LDS sizes from the carved frame's width and height.  This file
-holds (1) those choices as plain Python, each with the function or expression of the shim it mirrors, (2) THRESHOLDS: every switch as a quantity and a
+csrc/lqr_plan.h chooses kernels, thread counts, pixels per lane and LDS sizes from the carved frame's width and height (the launch
+shim, csrc/lqr_shim.hip, launches what it plans).  This file holds (1) those choices as plain Python, each with the function or
+expression of the planner it mirrors -- written independently of it: tests/test_plan.py compares the two without a GPU --, (2) THRESHOLDS: every switch as a quantity and a
 limit, and (3) CASES: thin frames -- 6 to 40 rows or columns in the dimension that does not matter -- that reach every switch from
 both sides.  tests/test_geometry_cases.py checks the table against the thresholds and runs the oracle on every case (no GPU);
 tests/test_geometry_gpu.py runs the engine on them and compares the launch census (lqrhip_launch_census) with census().
@@ -12,21 +13,21 @@ import numpy as np
 
 import datasets as D
 
-# ---- constants of csrc/lqr_common.h ---------------------------------------------------------------------------------------------
+# ---- constants of csrc/lqr_plan.h -----------------------------------------------------------------------------------------------
 DP_THREADS = 1024
 LV_MAX_TILES = 64                  # one 64-bit mask of 64-column tiles
 LV_MAX_LEVELS = 1020
 DPP_BLK_BITS = 12
 LQR_FAST_MAX_DELTA = 10
 VP_REACH, VP_STAGE = 56, 20
-MAX_FRAME_WIDTH = 16384            # include/lqr_hip.h LQRHIP_MAX_FRAME_WIDTH; lqr_shim.hip launch_dp's last else
-MI355X_CUS = 256                   # g_n_cu on the device the suite runs on (lqr_shim.hip)
-TILED_UPDATE_PX = 8 * 3840 * 2160  # lqr_shim.hip g_tiled_update_px
-FROZEN_CARVE_FUSED = 4             # g_carve_fused
-VPATH_PAR_MAX, VPATH_MIN_ROWS = 3, 1000
+MAX_FRAME_WIDTH = 16384            # include/lqr_hip.h LQRHIP_MAX_FRAME_WIDTH; lqr_plan.h plan_sweep: px 0
+MI355X_CUS = 256                   # PlanDevice.n_cu on the device the suite runs on
+TILED_UPDATE_PX = 8 * 3840 * 2160  # PlanKnobs.tiled_update_px
+FROZEN_CARVE_FUSED = 4             # PlanKnobs.carve_fused
+VPATH_PAR_MAX, VPATH_MIN_ROWS = 3, 1000          # PlanKnobs.vpath_par_max, vpath_min_rows
 
 
-def dpp_own(px):                   # lqr_common.h dpp_own / dpp_halo
+def dpp_own(px):                   # dpp_own / dpp_halo
     return {2: 64, 3: 32, 4: 128}[px]
 
 
@@ -38,7 +39,7 @@ def dpp_rb(px, delta):             # dpp_rb: rows per block
     return dpp_halo(2) // delta if delta >= 5 else 8 if delta >= 3 else dpp_halo(px) // delta
 
 
-def lv_rows(delta):                # lv_rows as band_levels_P calls it (rigm = true)
+def lv_rows(delta):                # lv_rows as plan_levels_P calls it (rigm = true)
     return 16 if delta <= 2 else 8 if delta <= 4 else 32 // delta
 
 
@@ -62,18 +63,18 @@ def sweep_slot(px, threads):
     return SWEEP + 2 * (1, 2, 4, 8, 16).index(px) + (1 if threads == DP_THREADS else 0)
 
 
-# ---- the shim's choices, restated (each names the function of csrc/lqr_shim.hip it mirrors) ------------------------------------
+# ---- the planner's choices, restated (each names the function of csrc/lqr_plan.h it mirrors) ---------------------------------
 def hook(case, name, default):
     return case.get("hooks", {}).get(name, default)
 
 
 def rigm(case):
-    """a rigidity mask that matters (seam_step_impl: has_rigmask && use_rigidity)"""
+    """a rigidity mask that matters (PlanBatch::rigm)"""
     return bool(case["kw"].get("rigmask")) and case["kw"].get("rigidity", 0.0) != 0.0
 
 
 def sweep_form(case, update, w):
-    """launch_dp: k_dp_sweep's threads (nth) and px per thread (the first of K_DP_SWEEP_PXT_FORMS that covers the row); None: past the last, refused"""
+    """plan_sweep: k_dp_sweep's threads and px per thread (the first of 1, 2, 4, 8, 16 that covers the row); None: past the last, refused"""
     nth = 256 if (update and hook(case, "sweep_threads", 256) == 256 and w <= 16 * 256) else DP_THREADS
     pxt = (w + nth - 1) // nth
     for p in (1, 2, 4, 8, 16):
@@ -83,12 +84,12 @@ def sweep_form(case, update, w):
 
 
 def sweep_lds(w):
-    """launch_dp: lds"""
+    """plan_sweep: lds"""
     return 2 * ((w + 3) & ~3) * 4
 
 
 def persistent_px(case, w, h, general, delta):
-    """dp_persistent_px for ONE image on an otherwise idle MI355X: the residency bounds are at least one workgroup per compute unit
+    """plan_persistent_px for ONE image on an otherwise idle MI355X: the residency bounds are at least one workgroup per compute unit
     whenever the persistent kernels run at all, and a frame of 16384 columns is 256 tiles of 64"""
     if hook(case, "no_spin", 0) or hook(case, "limit", -1) == 0 or case.get("redo"):
         return 0
@@ -104,14 +105,14 @@ def persistent_px(case, w, h, general, delta):
 
 
 def levels_ok(case, w, h, delta):
-    """band_levels_P, its geometry part"""
+    """plan_levels_P, its geometry part"""
     if hook(case, "no_spin", 0) or hook(case, "band_levels", -1) == 0 or not 1 <= delta <= LQR_FAST_MAX_DELTA:
         return False
     return (h + lv_rows(delta) - 1) // lv_rows(delta) <= LV_MAX_LEVELS and (w + 63) // 64 <= LV_MAX_TILES
 
 
 def band_form(case, wnew, h):
-    """seam_step_impl (fast_band, band_tw, nw): which band kernel an update that reached the band kernels runs"""
+    """plan_seam_step (band): which band kernel an update that reached the band kernels runs"""
     mode, delta = hook(case, "update_mode", -1), case["kw"].get("delta_x", 1)
     fast_ok = delta == 1 and not rigm(case) and mode != 3
     fast_band = fast_ok and h * 4 <= 60 * 1024
@@ -185,19 +186,19 @@ def census(case):
         full_dp(s["fw"], h)
         for wb, wnew, full in seam_steps(case, s):
             use_vp = 1 <= delta <= LQR_FAST_MAX_DELTA and h >= 2 and vmode != 0 and (vmode == 1 or delta >= 5 or (n <= VPATH_PAR_MAX and h >= VPATH_MIN_ROWS))
-            c[VP_PARALLEL if use_vp else VPATH1 if delta <= 7 else VPATH] += 1          # seam_step_impl: the backtrack
+            c[VP_PARALLEL if use_vp else VPATH1 if delta <= 7 else VPATH] += 1          # plan_seam_step: backtrack
             c[CARVE_E if (delta <= 2 and n <= FROZEN_CARVE_FUSED and wnew > 1) else CARVE] += 1      # the carve
             if wnew <= 1:
                 continue
             if full:
                 full_dp(wnew, h)
                 continue
-            fast_ok = delta == 1 and not rigm(case) and mode != 3                       # fast_ok, tiled_update
+            fast_ok = delta == 1 and not rigm(case) and mode != 3                       # plan_seam_step: plain, tiled
             if fast_ok:
                 tiled = (n * wb * h <= TILED_UPDATE_PX if mode < 0 else mode == 1) and persistent_px(case, wb, h, False, 1) != 0
             else:
                 tiled = 1 <= delta <= LQR_FAST_MAX_DELTA and mode not in (0, 2, 3) and persistent_px(case, wb, h, True, delta) != 0
-            if mode == 5 and (delta <= LQR_FAST_MAX_DELTA) and levels_ok(case, wnew, h, delta):      # band_levels_P (a single image: on request only)
+            if mode == 5 and (delta <= LQR_FAST_MAX_DELTA) and levels_ok(case, wnew, h, delta):      # plan_levels_P (a single image: on request only)
                 c[BAND_LEVELS] += 1
                 sweep_update(wnew)
             elif tiled:
@@ -239,37 +240,37 @@ def _levels_case(case):
 
 
 THRESHOLDS = {
-    "levels_tiles_4096": ("band_levels_P: (w + 63) / 64 > LV_MAX_TILES",
+    "levels_tiles_4096": ("plan_levels_P: tiles_of(w, 64) > LV_MAX_TILES",
                           lambda c: 4096 if _levels_case(c) else None, _wnews, True),
-    "sweep_threads_4096": ("launch_dp: nth, w <= 16 * 256",
+    "sweep_threads_4096": ("plan_sweep: threads, w <= 16 * 256",
                            lambda c: 4096 if (_band_case(c) or _levels_case(c)) else None, _wnews, True),
-    "band_tw_width_4200": ("seam_step_impl: band_tw, wnew <= 4200",
+    "band_tw_width_4200": ("plan_seam_step: band, wnew <= 4200",
                            lambda c: 4200 if _band_case(c) and _mode(c) == 0 and _delta(c) == 1 and not rigm(c) else None, _wnews, True),
-    "band_mw_waves_4200": ("seam_step_impl: nw, wnew > 4200 -> 16 waves",
+    "band_mw_waves_4200": ("plan_seam_step: band, wnew > 4200 -> 16 waves",
                            lambda c: 4200 if _band_case(c) and _mode(c) == 2 and _delta(c) == 1 and not rigm(c) else None, _wnews, True),
-    "sweep_px_lds_8192": ("launch_dp: pxt <= 8, lds > 64 KB",
+    "sweep_px_lds_8192": ("plan_sweep: px <= 8; lds_needs_attr, lds > 64 KB",
                           lambda c: 8192 if _band_case(c) else None, _wnews, True),
-    "tile_geometry3_8192": ("dp_persistent_px: 32-column tiles <= compute units",
+    "tile_geometry3_8192": ("plan_persistent_px: 32-column tiles <= compute units",
                             lambda c: 8192 if _one(c) and sum(census(c)[TILE_P_G3:TILE_P_G4 + 1]) > 0 and hook(c, "px", 0) == 0 else None,
                             lambda c, s: [s["fw"]], False),
     "commit_lds_16384": ("lqrhip_vs_commit: (n_seams + wc0) * 4 > 64 KB",
                          lambda c: 16384 if c["kind"] != "refused" else None, lambda c, s: [s["fw"], s["fw"] + s["seams"]], True),
-    "frame_limit_16384": ("launch_dp's last else; host/lqr_carver.c frame_refused",
+    "frame_limit_16384": ("plan_sweep: px 0; host/lqr_carver.c frame_refused",
                           lambda c: 16384, lambda c, s: [s["fw"]], False),
-    "band_tw_lds_8192_rows": ("seam_step_impl: band_tw, 2 * h * 4 <= 64 KB",
+    "band_tw_lds_8192_rows": ("plan_seam_step: band, 2 * h * 4 <= 64 KB",
                               lambda c: 8192 if _band_case(c) and _mode(c) == 0 and _delta(c) == 1 and max(c["w"], c["nw"]) <= 4200 else None,
                               lambda c, s: [s["fh"]], False),
-    "fast_band_15360_rows": ("seam_step_impl: fast_band, h * 4 <= 60 KB",
+    "fast_band_15360_rows": ("plan_seam_step: band, h * 4 <= 60 KB",
                              lambda c: 15360 if _band_case(c) and _mode(c) in (0, 2) and _delta(c) == 1 else None, lambda c, s: [s["fh"]], False),
-    "block_field_12285_rows": ("dp_persistent_px: hh <= 4095 * dpp_rb(2, delta), delta 9 and 10",
+    "block_field_12285_rows": ("plan_persistent_px: wk_h <= 4095 * dpp_rb(2, delta), delta 9 and 10",
                                lambda c: 4095 * dpp_rb(2, 10) if _one(c) and _delta(c) in (9, 10) and _mode(c) < 0 else None,
                                lambda c, s: [s["fh"]], False),
-    "block_field_16380_rows": ("dp_persistent_px: the same, delta 7 and 8",
+    "block_field_16380_rows": ("plan_persistent_px: the same, delta 7 and 8",
                                lambda c: 4095 * dpp_rb(2, 8) if _one(c) and _delta(c) in (7, 8) and _mode(c) < 0 else None,
                                lambda c, s: [s["fh"]], False),
-    "levels_8160_rows": ("band_levels_P: LV_MAX_LEVELS * lv_rows, delta 3 and 4",
+    "levels_8160_rows": ("plan_levels_P: LV_MAX_LEVELS * lv_rows, delta 3 and 4",
                          lambda c: LV_MAX_LEVELS * lv_rows(3) if _levels_case(c) and _delta(c) in (3, 4) else None, lambda c, s: [s["fh"]], False),
-    "levels_16320_rows": ("band_levels_P: the same, delta 1 and 2",
+    "levels_16320_rows": ("plan_levels_P: the same, delta 1 and 2",
                           lambda c: LV_MAX_LEVELS * lv_rows(2) if _levels_case(c) and _delta(c) in (1, 2) else None, lambda c, s: [s["fh"]], False),
 }
 CROSSED_IN_SESSION = ("levels_tiles_4096", "sweep_threads_4096", "band_tw_width_4200", "band_mw_waves_4200", "sweep_px_lds_8192", "commit_lds_16384")
@@ -426,7 +427,7 @@ def run_kw(c):
 
 
 def vp_geometry(c):
-    """chunks and LDS stages of the parallel backtrack in the case's first session (seam_step_impl: nchunks; k_backtrack.hip)"""
+    """chunks and LDS stages of the parallel backtrack in the case's first session (plan_seam_step: vp_chunks; k_backtrack.hip)"""
     s, r = sessions(c)[0], vp_chunk_rows(c["kw"].get("delta_x", 1))
     nchunks = (s["fh"] - 1 + r - 1) // r
     return nchunks, (nchunks + VP_STAGE - 1) // VP_STAGE

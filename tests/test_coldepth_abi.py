@@ -161,18 +161,23 @@ def test_mid_manifest_lists_every_vector_with_its_checksum_and_size_limits():
 
 
 def kernel_constants():
-    """EU_ROWS, EU_LOGB, FROZEN_LAG_MAX and the delta_x thresholds of k_emap_update's instantiations (both forms of the working
-    plane go through the one function, eu_samples), from the sources"""
+    """EU_ROWS, EU_LOGB, FROZEN_LAG_MAX from the sources; the delta_x thresholds of k_emap_update's instantiations (both forms of the
+    working plane go through the one function, eu_samples) and the lag rule as the planner itself answers (csrc/lqr_plan.h through
+    tests/c/plan_main.cc, built by tests/test_plan.py)"""
+    import test_plan
     common = open(os.path.join(CSRC, "lqr_common.h")).read()
-    shim = open(os.path.join(CSRC, "lqr_shim.hip")).read()
+    plan = open(os.path.join(CSRC, "lqr_plan.h")).read()
     K = {}
-    for name, src in (("EU_ROWS", common), ("EU_LOGB", common), ("FROZEN_LAG_MAX", shim)):
+    for name, src in (("EU_ROWS", common), ("EU_LOGB", common), ("FROZEN_LAG_MAX", plan)):
         (K[name],) = {int(v) for v in re.findall(r"^#define\s+%s\s+(\d+)" % name, src, re.M)}
-    (m,) = re.findall(r"constexpr int eu_samples\(int delta_x\) \{ return delta_x <= (\d+) \? (\d+) : delta_x <= (\d+) \? (\d+) : (\d+); \}", shim)
-    a, na, b, nb, nc = map(int, m)
-    K["NT"] = [(a, na), (b, nb), (10 ** 9, nc)]
-    # the lag of a group: a quarter up to 4 carvers (the one helper both places of the seam loop call)
-    assert len(re.findall(r"const int lag_max = n <= 4 \? FROZEN_LAG_MAX / 4 : FROZEN_LAG_MAX;", shim)) == 1
+    rules = [ln.split() for ln in test_plan.run_plan("rules\n").splitlines()]
+    nt = [(int(d), int(v)) for kind, d, v in rules if kind == "nt"]          # samples per row for delta_x 0 .. LQRHIP_MAX_DELTA
+    assert [d for d, _ in nt] == list(range(17)) and [v for _, v in nt] == sorted(v for _, v in nt)
+    last = {v: d for d, v in nt}                                             # the largest delta_x of each sample count
+    K["NT"] = [(10 ** 9 if d == 16 else d, v) for v, d in sorted(last.items())]
+    # the lag of a group: a quarter up to 4 carvers -- the seam step's plan says when the frozen planes are caught up
+    lag = {int(n): int(v) for kind, n, v in rules if kind == "lag"}
+    assert lag == {n: K["FROZEN_LAG_MAX"] // 4 if n <= 4 else K["FROZEN_LAG_MAX"] for n in range(1, 9)}, lag
     # the chunk of every rank loop a deep carver runs: k_wk_init_visible and k_frozen_catchup; k_vs_commit, k_inflate, k_compact, k_compact_jobs
     for unit, loops in (("k_energy.hip", 2), ("k_oneoff.hip", 4)):
         src = open(os.path.join(CSRC, unit)).read()

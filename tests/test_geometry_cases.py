@@ -29,7 +29,7 @@ def test_restated_constants_match_the_sources():
     import os
     import re
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gimp-lqr-plugin_amd", "csrc")
-    common = open(os.path.join(root, "lqr_common.h")).read()
+    common = open(os.path.join(root, "lqr_plan.h")).read()          # the geometry constants the choices depend on live with the choices
     hdr = open(os.path.join(os.path.dirname(root), "..", "include", "lqr_hip.h")).read()
     for pat, want in ((r"constexpr int LV_MAX_TILES = (\d+);", G.LV_MAX_TILES), (r"constexpr int LV_MAX_LEVELS = (\d+);", G.LV_MAX_LEVELS),
                       (r"constexpr int DPP_BLK_BITS = (\d+);", G.DPP_BLK_BITS), (r"#define DP_THREADS (\d+)", G.DP_THREADS),
