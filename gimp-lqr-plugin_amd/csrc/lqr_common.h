@@ -14,6 +14,7 @@
 //   k_energy_out.hip energy read-outs (lqr_energy.h) k_energy_range (squash, min / max per workgroup), k_energy_out (normalise, expand to pixels, image orientation)
 //   lqr_shim.hip     the lqrhip_* C ABI of include/lqr_hip.h: allocation cache, batches, the per-seam launch sequence
 //   lqr_plan.h       which form of each stage that sequence runs (plain C++17, no HIP: also compiled alone by tests/test_plan.py)
+//   lqr_own.h        who owns a device block: DevBuf, Scratch (plain C++17, no HIP: also compiled alone by tests/test_own.py)
 // lqr_kernels.h declares every kernel for the shim; each kernel file instantiates the templates the shim launches.
 // lqr_pixel.h (k_energy.hip, k_oneoff.hip): the packed 8-bit and the value / deep form of a pixel as compile-time policies, so that
 // every kernel that touches pixels exists once and serves 8-bit grey / RGB carvers and those of any other depth, type or channel count

@@ -1,10 +1,13 @@
 // lqr_shim.hip -- the host side: the lqrhip_* C ABI of include/lqr_hip.h (plain pointers and sizes) on top of the kernels of
 // k_*.hip: device selection, the allocation cache, host <-> device transfers through a pinned ring, batches and their streams,
 // lqrhip_seam_step's per-seam launch sequence (which form of each stage it runs is lqr_plan.h's choice), read-out, reset from device memory,
-// the copy ceiling and the seam-map colour ramp.  The three kernels that live here (k_poison_random, k_copy16, k_vmap_ramp)
+// the copy ceiling and the seam-map colour ramp.  Every block of the allocation cache has one owner, a DevBuf or a Scratch of lqr_own.h:
+// nothing here gives a block back by hand.  The three kernels that live here (k_poison_random, k_copy16, k_vmap_ramp)
 // are debugging / measuring / one-off aids next to their only callers.
 #include "lqr_common.h"
 #include "lqr_kernels.h"
+#include "lqr_own.h"
+#include <memory>
 
 static thread_local std::string g_err;
 static int g_device = -1;
@@ -31,7 +34,18 @@ static PlanDevice g_dev;
 // ===========================================================================
 // host side of the shim
 // ===========================================================================
-struct LqrHipCarver {
+namespace {
+struct WorkingPlanes {
+    DevBuf<uint32_t> pix;
+    DevBuf<float> en, m, m2, bias, rig;
+    DevBuf<int8_t> least, least2;
+    DevBuf<int32_t> seam_x, seam_log, flags;
+    DevBuf<int8_t> vp_map, vp_path;     // parallel backtrack: chunk displacement maps and paths (allocated on first use)
+};
+}  // namespace
+// (hidden: whatever the compiler emits for the struct's members -- its destructor gives the planes back -- stays out of the exports,
+// which are those of include/lqr_hip.h)
+struct __attribute__((visibility("hidden"))) LqrHipCarver {
     int ch = 0;
     int depth = 0;                   // LqrColDepth: 0 8I, 1 .. 3 16I / 32F / 64F
     int luma = 0;                    // (value plane) the value in `pix` is luma, not brightness
@@ -39,32 +53,90 @@ struct LqrHipCarver {
     int pix_deep = 0;                // `pix` as allocated holds a double per pixel (reads_value() at the time)
     int w0 = 0, h0 = 0;              // base layout dims
     // base planes
-    uint8_t *rgb0 = nullptr;
-    int32_t *vs = nullptr;           // owned by roots only
-    float *bias0 = nullptr, *rig0 = nullptr;
+    DevBuf<uint8_t> rgb0;
+    DevBuf<int32_t> vs;              // a root's; an attached carver has none and reads its root's (vs_of)
+    DevBuf<float> bias0, rig0;
     // working planes
     int active = 0;
     int stride = 0, wk_h = 0;
-    uint32_t *pix = nullptr;
-    float *en = nullptr, *m = nullptr, *m2 = nullptr, *bias = nullptr, *rig = nullptr;
-    int8_t *least = nullptr, *least2 = nullptr;
-    int32_t *seam_x = nullptr, *seam_log = nullptr, *flags = nullptr;
-    int8_t *vp_map = nullptr;       // parallel backtrack: chunk displacement maps and paths (allocated on first use)
-    int8_t *vp_path = nullptr;
-    size_t vp_cap = 0;
-    int log_cap = 0, log_h = 0;
+    WorkingPlanes wk;
+    int log_cap = 0, log_h = 0;      // the seam log's shape: seams x rows
     int frozen_epoch = 0;           // pix / bias are in the frame before seam `frozen_epoch` of the session
     LqrHipCarver *root = nullptr;
     std::vector<LqrHipCarver *> aux;
     LqrHipBatch *batch = nullptr;
 };
 
+// bytes per pixel of the base layout
+static inline size_t px_bytes(const LqrHipCarver *c) { return (size_t) c->ch << (c->depth == 0 ? 0 : c->depth == 1 ? 1 : c->depth == 2 ? 2 : 3); }
+// the visibility map a carver reads: its own, or its root's
+static inline int32_t *vs_of(const LqrHipCarver *c) { return (c->root ? c->root : c)->vs; }
+
+// E14 / E11: every carver of the batch (roots and their attached carvers) goes through ONE launch (a job table in device
+// memory, one grid slice of blocks per job); the new planes replace the old ones after its synchronisation.  Everything
+// staged for the pass is owned by a PlaneJobs object until then: dropping it gives all of it back to the pool.
+namespace {
+struct PlaneJob {
+    LqrHipCarver *c;
+    DevBuf<uint8_t> nrgb;
+    DevBuf<float> nbias, nrig;
+};
+}  // namespace
+struct PlaneJobs {
+    std::vector<PlaneJob> jobs;
+    std::vector<DevBuf<int32_t>> new_vs;    // one per root (none for a transpose)
+    // the job table (ch = bytes per pixel), ordered by the form of the kernel that takes each job (stage()): the first n_narrow go
+    // to the pass's 8-bit kernel, the others to its deep form / k_transpose_px (lqr_pixel.h: 16-byte accesses where they fit)
+    std::vector<InflateDev> dev;
+    DevBuf<InflateDev> d_dev;
+    size_t n_narrow = 0;
+    // stage the output planes of carver c: n1 pixels each
+    int add(LqrHipCarver *c, const int32_t *vs_old, int32_t *nvs, size_t n1)
+    {
+        jobs.push_back(PlaneJob{c, {}, {}, {}});
+        PlaneJob &j = jobs.back();
+        int rc = j.nrgb.alloc(n1 * px_bytes(c), "&j.nrgb");
+        if (!rc && c->bias0) rc = j.nbias.alloc(n1, "&j.nbias");
+        if (!rc && c->rig0) rc = j.nrig.alloc(n1, "&j.nrig");
+        if (rc) return rc;
+        dev.push_back(InflateDev{c->rgb0, vs_old, c->bias0, c->rig0, j.nrgb, nvs, j.nbias, j.nrig, (int) px_bytes(c), c->depth});
+        return 0;
+    }
+    // the table to the device.  Transpose and flatten (by_width) keep pixels of up to 4 bytes on the 8-bit kernels, which move them
+    // as bytes / one dword; inflate averages, so only 8-bit pixels of up to 4 channels stay there
+    int stage(hipStream_t s, bool by_width)
+    {
+        n_narrow = std::stable_partition(dev.begin(), dev.end(), [&](const InflateDev &d) { return d.ch <= 4 && (by_width || d.depth == 0); }) - dev.begin();
+        int rc = d_dev.alloc(dev.size(), "&d_dev");
+        if (rc) return rc;
+        HIPCK(hipMemcpyAsync(d_dev, dev.data(), dev.size() * sizeof(InflateDev), hipMemcpyHostToDevice, s));
+        return 0;
+    }
+    size_t n_wide() const { return dev.size() - n_narrow; }
+    const InflateDev *d_wide() const { return d_dev + n_narrow; }
+};
+// after the pass has completed: the new base planes become the carvers'
+static void commit(PlaneJobs &pj)
+{
+    for (auto &j : pj.jobs) {
+        j.c->rgb0 = std::move(j.nrgb);
+        if (j.nbias) j.c->bias0 = std::move(j.nbias);
+        if (j.nrig) j.c->rig0 = std::move(j.nrig);
+    }
+}
+
+// Two phases (round 6): lqrhip_inflate / lqrhip_flatten / lqrhip_transpose stage the new planes of the batch, run the pass (the inflate
+// pass with its fused self-check) and ADOPT NOTHING; lqrhip_planes_commit adopts what was staged.  The host runs phase one on every
+// sub-batch of a group before it commits any: a failed check or a failed allocation in sub-batch k must not find sub-batches 0 .. k - 1
+// already living in their new layouts (the roll-back / the error return leaves the whole group where it was).
+// lqrhip_session_rollback / lqrhip_batch_abort / lqrhip_batch_destroy discard a staged pass.
+struct PendingInflate { PlaneJobs pj; int kind = 0 /* 0 inflate, 1 flatten, 2 transpose */, w1 = 0, h1 = 0; };
+
 struct LqrHipBatch {
     std::vector<LqrHipCarver *> cs;
     DevCarver *d_desc = nullptr;
     hipStream_t stream = nullptr;
-    unsigned long long *exch = nullptr;     // k_dp_tile_p: halo granules per image and tile + finished-tile counters
-    size_t exch_elems = 0;
+    DevBuf<unsigned long long> exch;        // k_dp_tile_p: halo granules per image and tile + finished-tile counters
     int exch_ntiles = 0, exch_n = 0, exch_px = 0;      // geometry the exchange area was last laid out for
     int tile_epoch = 0;                     // launches of k_dp_tile_p on this batch (part of the granule tags)
     bool dirty = true;
@@ -72,9 +144,8 @@ struct LqrHipBatch {
     bool shared = false;                    // other batches of the same group run concurrently on their own streams:
                                             // no persistent (spin-waiting, co-residency-dependent) kernels
     bool safe = false;                      // a session is being redone after a fault: kernels without spin waits only
-    void *pending_inflate = nullptr;        // the staged planes of lqrhip_inflate / _flatten / _transpose, until lqrhip_planes_commit adopts them (PendingInflate)
+    std::unique_ptr<PendingInflate> pending_inflate;    // the staged planes of lqrhip_inflate / _flatten / _transpose, until lqrhip_planes_commit adopts them
 };
-static void discard_pending(LqrHipBatch *b);
 static bool g_no_spin = false;             // set by a spin time-out (check_dev_error): the process stays on the non-spinning kernels
 
 struct ProfRec {
@@ -248,7 +319,7 @@ __global__ void k_poison_random(unsigned *p, size_t n, int mode, int stride, int
         p[i] = mode == 1 ? __float_as_uint((float) (hsh >> 8) * (100.0f / 16777216.0f)) : mode == 2 ? (hsh >> 21) : hsh;
     }
 }
-static const char *g_alloc_name = "";      // what the allocation is for (LQRHIP_POISON_LOG)
+static const char *g_alloc_name = "";      // what the allocation under way is for (LQRHIP_POISON_LOG)
 static int g_poison = -2;
 static unsigned g_poison32 = 0;
 static int pool_poison(void *p, size_t sz)
@@ -288,30 +359,34 @@ static int pool_poison(void *p, size_t sz)
 // fault injection (tests/test_faults_gpu.py): the nth device allocation from now on fails with "out of memory", once (-1: disarmed)
 static long g_fail_alloc_in = -1;
 extern "C" void lqrhip_debug_fail_alloc(int nth) { g_fail_alloc_in = nth; }
-static int pool_alloc(void **p, size_t bytes)
+static int lqr_pool_alloc(void **p, size_t bytes, const char *name)
 {
+    *p = nullptr;
+    g_alloc_name = name;
     const size_t sz = (bytes + ((size_t) 1 << 20) - 1) & ~(((size_t) 1 << 20) - 1);      // 1 MiB classes
-    if (g_fail_alloc_in >= 0 && g_fail_alloc_in-- == 0) { *p = nullptr; g_err = std::string("injected allocation failure (") + (g_alloc_name ? g_alloc_name : "?") + ")"; return LQRHIP_ENOMEM; }
+    if (g_fail_alloc_in >= 0 && g_fail_alloc_in-- == 0) { g_err = std::string("injected allocation failure (") + (g_alloc_name ? g_alloc_name : "?") + ")"; return LQRHIP_ENOMEM; }
     auto it = g_pool_free.find(sz);
     if (it != g_pool_free.end()) {
         *p = it->second;
         g_pool_free.erase(it);
         g_pool_cached -= sz;
-        return pool_poison(*p, sz);
+    } else {
+        hipError_t e = hipMalloc(p, sz);
+        if (e == hipErrorOutOfMemory && !g_pool_free.empty()) {       // give the cache back and retry once
+            (void) hipGetLastError();
+            for (auto &kv : g_pool_free) { (void) hipFree(kv.second); g_pool_size.erase(kv.second); }
+            g_pool_free.clear();
+            g_pool_cached = 0;
+            e = hipMalloc(p, sz);
+        }
+        HIPCK(e);
+        g_pool_size[*p] = sz;
     }
-    hipError_t e = hipMalloc(p, sz);
-    if (e == hipErrorOutOfMemory && !g_pool_free.empty()) {       // give the cache back and retry once
-        (void) hipGetLastError();
-        for (auto &kv : g_pool_free) { (void) hipFree(kv.second); g_pool_size.erase(kv.second); }
-        g_pool_free.clear();
-        g_pool_cached = 0;
-        e = hipMalloc(p, sz);
-    }
-    HIPCK(e);
-    g_pool_size[*p] = sz;
-    return pool_poison(*p, sz);
+    const int rc = pool_poison(*p, sz);
+    if (rc) { lqr_pool_free(*p); *p = nullptr; }      // a failed allocation hands nothing out
+    return rc;
 }
-static void pool_free(void *p)
+static void lqr_pool_free(void *p)
 {
     auto it = g_pool_size.find(p);
     if (it == g_pool_size.end()) { (void) hipFree(p); return; }
@@ -323,21 +398,9 @@ static void pool_free(void *p)
     g_pool_free.emplace(it->second, p);
     g_pool_cached += it->second;
 }
+extern "C" unsigned long long lqrhip_debug_pool_live(void) { return g_pool_size.size() - g_pool_free.size(); }
 
-template <typename T>
-static int dmalloc_(T **p, size_t n, const char *name)
-{
-    *p = nullptr;
-    g_alloc_name = name;
-    return pool_alloc((void **) p, (n ? n : 1) * sizeof(T));
-}
-#define dmalloc(p, n) dmalloc_((p), (n), #p)
-template <typename T>
-static void dfree(T *&p)
-{
-    if (p) pool_free((void *) p);
-    p = nullptr;
-}
+static void lqr_stream_wait(void *stream) { (void) hipStreamSynchronize((hipStream_t) stream); }
 
 // zero device memory and wait: hipMemset on the null stream is asynchronous for device memory and the
 // engine's streams are non-blocking, so a null-stream memset is not ordered with the kernels after it
@@ -545,8 +608,6 @@ static void default_read(LqrHipCarver *c)
     c->alpha = c->ch == 2 ? 1 : c->ch == 4 ? 3 : c->ch == 5 ? 4 : -1;
     c->black = c->ch == 5 ? 3 : -1;
 }
-// bytes per pixel of the base layout
-static inline size_t px_bytes(const LqrHipCarver *c) { return (size_t) c->ch << (c->depth == 0 ? 0 : c->depth == 1 ? 1 : c->depth == 2 ? 2 : 3); }
 
 static int batch_sync_of(LqrHipCarver *c)
 {
@@ -564,7 +625,7 @@ extern "C" LqrHipCarver *lqrhip_carver_create_ext(const void *rgb, int w, int h,
     c->ch = channels; c->depth = depth; c->w0 = w; c->h0 = h;
     default_read(c);
     const size_t n = (size_t) w * h, bytes = n * px_bytes(c);
-    if (dmalloc(&c->rgb0, bytes) || dmalloc(&c->vs, n)) { lqrhip_carver_destroy(c); return nullptr; }
+    if (c->rgb0.alloc(bytes, "&c->rgb0") || c->vs.alloc(n, "&c->vs")) { lqrhip_carver_destroy(c); return nullptr; }
     // the visibility map is cleared on the same stream, under the upload: one synchronisation for both
     if (hipMemsetAsync(c->vs, 0, n * sizeof(int32_t), g_stream0) != hipSuccess || h2d_staged(c->rgb0, rgb, bytes) != 0) {
         g_err = "upload failed";
@@ -600,10 +661,8 @@ extern "C" int lqrhip_carver_set_read(LqrHipCarver *c, int image_type, int alpha
 
 static void free_working(LqrHipCarver *c)
 {
-    dfree(c->pix); dfree(c->en); dfree(c->m); dfree(c->least); dfree(c->m2); dfree(c->least2); dfree(c->bias); dfree(c->rig);
-    dfree(c->seam_x); dfree(c->seam_log); dfree(c->flags);
-    dfree(c->vp_map); dfree(c->vp_path);
-    c->log_cap = 0; c->vp_cap = 0;
+    c->wk = WorkingPlanes();
+    c->log_cap = 0; c->log_h = 0;
 }
 
 extern "C" void lqrhip_carver_destroy(LqrHipCarver *c)
@@ -618,18 +677,13 @@ extern "C" void lqrhip_carver_destroy(LqrHipCarver *c)
         if (g_stream0) (void) hipStreamSynchronize(g_stream0);
         (void) hipGetLastError();
     }
-    dfree(c->rgb0);
-    if (!c->root) dfree(c->vs);
-    dfree(c->bias0); dfree(c->rig0);
-    free_working(c);
     delete c;
 }
 
 extern "C" int lqrhip_carver_attach(LqrHipCarver *root, LqrHipCarver *aux)
 {
     if (root->w0 != aux->w0 || root->h0 != aux->h0) return LQRHIP_EARG;
-    dfree(aux->vs);
-    aux->vs = root->vs;
+    aux->vs.reset();
     aux->root = root;
     root->aux.push_back(aux);
     if (root->batch) root->batch->dirty = true;
@@ -642,24 +696,25 @@ static int ensure_working(LqrHipCarver *c, int w, int h)
     int stride = ((w + 16) + 63) & ~63;
     bool need_bias = c->bias0 != nullptr, need_rig = c->rig0 != nullptr;
     const int deep = reads_value(c) ? 1 : 0;
-    if (c->pix && c->stride == stride && c->wk_h == h && (!!c->bias == need_bias) && (!!c->rig == need_rig) && c->pix_deep == deep) return 0;
+    WorkingPlanes &k = c->wk;
+    if (k.pix && c->stride == stride && c->wk_h == h && (!!k.bias == need_bias) && (!!k.rig == need_rig) && c->pix_deep == deep) return 0;
     free_working(c);
     c->stride = 0; c->wk_h = 0;
     size_t n = (size_t) stride * (h + 1) + 1024;
     const size_t npix = deep ? 2 * n : n;              // a value plane holds a double per pixel
     int rc;
-    if ((rc = dmalloc(&c->pix, npix)) || (rc = dmalloc(&c->en, n)) || (rc = dmalloc(&c->m, n)) || (rc = dmalloc(&c->least, n)) ||
-        (rc = dmalloc(&c->seam_x, (size_t) h + 8)) || (rc = dmalloc(&c->flags, (size_t) FLAG_WORDS)) ||
-        (need_bias && (rc = dmalloc(&c->bias, n))) || (need_rig && (rc = dmalloc(&c->rig, n)))) {
+    if ((rc = k.pix.alloc(npix, "&c->pix")) || (rc = k.en.alloc(n, "&c->en")) || (rc = k.m.alloc(n, "&c->m")) || (rc = k.least.alloc(n, "&c->least")) ||
+        (rc = k.seam_x.alloc((size_t) h + 8, "&c->seam_x")) || (rc = k.flags.alloc((size_t) FLAG_WORDS, "&c->flags")) ||
+        (need_bias && (rc = k.bias.alloc(n, "&c->bias"))) || (need_rig && (rc = k.rig.alloc(n, "&c->rig")))) {
         free_working(c);            // never leave a half-allocated set behind: a retry must not pass the early-out above
         return rc;
     }
     // all on the shim's stream, one synchronisation
-    hipError_t e = hipMemsetAsync(c->least, 0, n, g_stream0);
-    if (e == hipSuccess) e = hipMemsetAsync(c->m, 0, n * sizeof(float), g_stream0);
-    if (e == hipSuccess) e = hipMemsetAsync(c->en, 0, n * sizeof(float), g_stream0);
-    if (e == hipSuccess) e = hipMemsetAsync(c->pix, 0, npix * sizeof(uint32_t), g_stream0);
-    if (e == hipSuccess) e = hipMemsetAsync(c->flags, 0, (size_t) FLAG_WORDS * sizeof(int32_t), g_stream0);
+    hipError_t e = hipMemsetAsync(k.least, 0, n, g_stream0);
+    if (e == hipSuccess) e = hipMemsetAsync(k.m, 0, n * sizeof(float), g_stream0);
+    if (e == hipSuccess) e = hipMemsetAsync(k.en, 0, n * sizeof(float), g_stream0);
+    if (e == hipSuccess) e = hipMemsetAsync(k.pix, 0, npix * sizeof(uint32_t), g_stream0);
+    if (e == hipSuccess) e = hipMemsetAsync(k.flags, 0, (size_t) FLAG_WORDS * sizeof(int32_t), g_stream0);
     if (e == hipSuccess) e = hipStreamSynchronize(g_stream0);
     if (e != hipSuccess) { free_working(c); HIPCK(e); }
     c->stride = stride; c->wk_h = h; c->pix_deep = deep;
@@ -669,9 +724,8 @@ static int ensure_working(LqrHipCarver *c, int w, int h)
 
 static int ensure_log(LqrHipCarver *c, int n_seams, int h)
 {
-    if (c->seam_log && c->log_cap >= n_seams && c->log_h == h) return 0;
-    dfree(c->seam_log);
-    int rc = dmalloc(&c->seam_log, (size_t) n_seams * h);
+    if (c->wk.seam_log && c->log_cap >= n_seams && c->log_h == h) return 0;
+    int rc = c->wk.seam_log.alloc((size_t) n_seams * h, "&c->seam_log");      // (a log of another shape is replaced, also by a smaller one)
     if (rc) return rc;
     c->log_cap = n_seams; c->log_h = h;
     if (c->batch) c->batch->dirty = true;
@@ -686,55 +740,54 @@ extern "C" int lqrhip_carver_activate(LqrHipCarver *c)
     return ensure_working(c, c->w0, c->h0);
 }
 
+// ---- masks: the 8-bit ones of lqr.h and the computed ones of include/lqr_masks.h (kernels in k_energy.hip, k_masks.hip) ----------------
+extern "C" int lqrhip_mask_plane_ensure(LqrHipCarver *c, int is_rigmask)
+{
+    DevBuf<float> &plane = is_rigmask ? c->rig0 : c->bias0;
+    if (plane) return 0;
+    int rc = batch_sync_of(c);
+    if (rc) return rc;
+    const size_t n = (size_t) c->w0 * c->h0;
+    if ((rc = plane.alloc(n, "plane"))) return rc;
+    hipError_t e = dzero(plane, n * sizeof(float));
+    if (e != hipSuccess) { plane.reset(); HIPCK(e); }
+    if (c->batch) c->batch->dirty = true;
+    return 0;
+}
+
+// Where a width x height mask laid at (x_off, y_off) over the image (transposed: over the carver's transposed frame) falls: (x0, y0) what
+// of the offset is negative, (x1, y1) the first pixel it covers, nx x ny how many.  The far edge is computed in long long, so that a mask
+// near INT_MAX wide cannot wrap; for arguments where plain int arithmetic does not overflow the values are those it gives.
+struct MaskClip { int x0, y0, x1, y1, nx, ny; };
+static MaskClip mask_clip(const LqrHipCarver *c, int width, int height, int x_off, int y_off, int transposed)
+{
+    const int wt = transposed ? c->h0 : c->w0, ht = transposed ? c->w0 : c->h0;
+    const int x0 = x_off < 0 ? x_off : 0, y0 = y_off < 0 ? y_off : 0;
+    const int x1 = x_off > 0 ? x_off : 0, y1 = y_off > 0 ? y_off : 0;
+    const long long xe = (long long) width + x_off, ye = (long long) height + y_off;
+    const int x2 = wt < xe ? wt : (int) xe, y2 = ht < ye ? ht : (int) ye;
+    return MaskClip{x0, y0, x1, y1, x2 - x1, y2 - y1};
+}
+
 extern "C" int lqrhip_mask_add(LqrHipCarver *c, const unsigned char *mask, int channels, int width, int height, int x_off,
                                int y_off, int transposed, int is_rigmask, int bias_factor)
 {
     int rc = batch_sync_of(c);
     if (rc) return rc;
-    size_t n = (size_t) c->w0 * c->h0;
-    float **plane = is_rigmask ? &c->rig0 : &c->bias0;
-    if (!*plane) {
-        if ((rc = dmalloc(plane, n))) return rc;
-        HIPCK(dzero(*plane, n * sizeof(float)));
-        if (c->batch) c->batch->dirty = true;
-    }
-    int wt = transposed ? c->h0 : c->w0, ht = transposed ? c->w0 : c->h0;
-    int x0 = x_off < 0 ? x_off : 0, y0 = y_off < 0 ? y_off : 0;
-    int x1 = x_off > 0 ? x_off : 0, y1 = y_off > 0 ? y_off : 0;
-    int x2 = wt < width + x_off ? wt : width + x_off, y2 = ht < height + y_off ? ht : height + y_off;
-    int nx = x2 - x1, ny = y2 - y1;
-    if (nx <= 0 || ny <= 0) return 0;
-    uint8_t *dmask = nullptr;
-    size_t mbytes = (size_t) width * height * channels;
-    if ((rc = dmalloc(&dmask, mbytes))) return rc;
-    auto run = [&]() -> int {
-        int rcu = h2d_staged(dmask, mask, mbytes);
-        if (rcu) return rcu;
-        dim3 grid((nx + 255) / 256, ny);
-        hipLaunchKernelGGL(k_mask_add, grid, dim3(256), 0, g_stream0, *plane, c->w0, dmask, channels, width, x0, y0, x1, y1, nx, ny,
-                           transposed, is_rigmask, bias_factor);
-        HIPCK(hipGetLastError());
-        HIPCK(hipStreamSynchronize(g_stream0));
-        return 0;
-    };
-    rc = run();
-    if (rc) (void) hipStreamSynchronize(g_stream0);
-    dfree(dmask);
-    return rc;
-}
-
-// ---- computed masks (include/lqr_masks.h; kernels in k_masks.hip) ---------------------------------
-extern "C" int lqrhip_mask_plane_ensure(LqrHipCarver *c, int is_rigmask)
-{
-    float **plane = is_rigmask ? &c->rig0 : &c->bias0;
-    if (*plane) return 0;
-    int rc = batch_sync_of(c);
-    if (rc) return rc;
-    const size_t n = (size_t) c->w0 * c->h0;
-    if ((rc = dmalloc(plane, n))) return rc;
-    hipError_t e = dzero(*plane, n * sizeof(float));
-    if (e != hipSuccess) { dfree(*plane); HIPCK(e); }
-    if (c->batch) c->batch->dirty = true;
+    if ((rc = lqrhip_mask_plane_ensure(c, is_rigmask))) return rc;
+    float *plane = is_rigmask ? c->rig0 : c->bias0;
+    const MaskClip k = mask_clip(c, width, height, x_off, y_off, transposed);
+    if (k.nx <= 0 || k.ny <= 0) return 0;
+    const size_t mbytes = (size_t) width * height * channels;
+    Scratch tmp(g_stream0);
+    uint8_t *dmask = tmp.get<uint8_t>(mbytes, "&dmask", rc);
+    if (rc || (rc = h2d_staged(dmask, mask, mbytes))) return rc;
+    dim3 grid((k.nx + 255) / 256, k.ny);
+    hipLaunchKernelGGL(k_mask_add, grid, dim3(256), 0, g_stream0, plane, c->w0, dmask, channels, width, k.x0, k.y0, k.x1, k.y1, k.nx, k.ny,
+                       transposed, is_rigmask, bias_factor);
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(g_stream0));
+    tmp.done();
     return 0;
 }
 
@@ -746,38 +799,27 @@ extern "C" int lqrhip_mask_add_f(LqrHipCarver *c, const void *mask, int depth, i
     if (rc) return rc;
     if ((rc = lqrhip_mask_plane_ensure(c, is_rigmask))) return rc;
     float *plane = is_rigmask ? c->rig0 : c->bias0;
-    // the clipping of lqrhip_mask_add
-    const int wt = transposed ? c->h0 : c->w0, ht = transposed ? c->w0 : c->h0;
-    const int x0 = x_off < 0 ? x_off : 0, y0 = y_off < 0 ? y_off : 0;
-    const int x1 = x_off > 0 ? x_off : 0, y1 = y_off > 0 ? y_off : 0;
-    const long long xe = (long long) width + x_off, ye = (long long) height + y_off;
-    const int x2 = wt < xe ? wt : (int) xe, y2 = ht < ye ? ht : (int) ye;
-    const int nx = x2 - x1, ny = y2 - y1;
-    if (nx <= 0 || ny <= 0) return 0;
+    const MaskClip k = mask_clip(c, width, height, x_off, y_off, transposed);
+    if (k.nx <= 0 || k.ny <= 0) return 0;
     const size_t mbytes = (size_t) width * height * (depth == 2 ? sizeof(float) : sizeof(double));
-    uint8_t *staged = nullptr;
-    if (!on_device && (rc = dmalloc(&staged, mbytes))) return rc;
-    auto run = [&]() -> int {
-        if (!on_device) {
-            int rcu = h2d_staged(staged, mask, mbytes);
-            if (rcu) return rcu;
-        }
-        const void *src = on_device ? mask : (const void *) staged;
-        dim3 grid((nx + 255) / 256, ny);
-        if (depth == 2)
-            hipLaunchKernelGGL(k_mask_add_f<float>, grid, dim3(256), 0, g_stream0, plane, c->w0, (const float *) src, width, x0, y0, x1, y1, nx, ny,
-                               transposed, is_rigmask, bias_factor);
-        else
-            hipLaunchKernelGGL(k_mask_add_f<double>, grid, dim3(256), 0, g_stream0, plane, c->w0, (const double *) src, width, x0, y0, x1, y1, nx, ny,
-                               transposed, is_rigmask, bias_factor);
-        HIPCK(hipGetLastError());
-        HIPCK(hipStreamSynchronize(g_stream0));        // the caller may reuse its buffer
-        return 0;
-    };
-    rc = run();
-    if (rc) (void) hipStreamSynchronize(g_stream0);
-    dfree(staged);
-    return rc;
+    Scratch tmp(g_stream0);
+    const void *src = mask;
+    if (!on_device) {
+        uint8_t *staged = tmp.get<uint8_t>(mbytes, "&staged", rc);
+        if (rc || (rc = h2d_staged(staged, mask, mbytes))) return rc;
+        src = staged;
+    }
+    dim3 grid((k.nx + 255) / 256, k.ny);
+    if (depth == 2)
+        hipLaunchKernelGGL(k_mask_add_f<float>, grid, dim3(256), 0, g_stream0, plane, c->w0, (const float *) src, width, k.x0, k.y0, k.x1, k.y1, k.nx, k.ny,
+                           transposed, is_rigmask, bias_factor);
+    else
+        hipLaunchKernelGGL(k_mask_add_f<double>, grid, dim3(256), 0, g_stream0, plane, c->w0, (const double *) src, width, k.x0, k.y0, k.x1, k.y1, k.nx, k.ny,
+                           transposed, is_rigmask, bias_factor);
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(g_stream0));        // the caller may reuse its buffer
+    tmp.done();
+    return 0;
 }
 
 static unsigned long long g_mask_flushes = 0;
@@ -791,39 +833,33 @@ extern "C" int lqrhip_mask_scatter(LqrHipCarver *c, int is_rigmask, const int *i
     if ((rc = lqrhip_mask_plane_ensure(c, is_rigmask))) return rc;
     float *plane = is_rigmask ? c->rig0 : c->bias0;
     const size_t n = start[buckets];
-    int *dindex = nullptr;
-    double *dvalue = nullptr;
-    if ((rc = dmalloc(&dindex, n)) || (rc = dmalloc(&dvalue, n))) { dfree(dindex); return rc; }
-    auto run = [&]() -> int {
-        int rcu = h2d_staged(dindex, index, n * sizeof(int));
-        if (!rcu) rcu = h2d_staged(dvalue, value, n * sizeof(double));
-        if (rcu) return rcu;
-        // bucket after bucket on one stream: a pixel that is hit k times receives its values in call order
-        for (int b = 0; b < buckets; b++) {
-            const size_t nb = start[b + 1] - start[b];
-            if (!nb) continue;
-            hipLaunchKernelGGL(k_mask_scatter, dim3((unsigned) ((nb + 255) / 256)), dim3(256), 0, g_stream0, plane, dindex + start[b], dvalue + start[b],
-                               nb, is_rigmask);
-            HIPCK(hipGetLastError());
-            g_mask_flushes++;
-        }
-        HIPCK(hipStreamSynchronize(g_stream0));
-        return 0;
-    };
-    rc = run();
-    if (rc) (void) hipStreamSynchronize(g_stream0);
-    dfree(dindex); dfree(dvalue);
-    return rc;
+    Scratch tmp(g_stream0);
+    int *dindex = tmp.get<int>(n, "&dindex", rc);
+    if (rc) return rc;
+    double *dvalue = tmp.get<double>(n, "&dvalue", rc);
+    if (rc || (rc = h2d_staged(dindex, index, n * sizeof(int))) || (rc = h2d_staged(dvalue, value, n * sizeof(double)))) return rc;
+    // bucket after bucket on one stream: a pixel that is hit k times receives its values in call order
+    for (int b = 0; b < buckets; b++) {
+        const size_t nb = start[b + 1] - start[b];
+        if (!nb) continue;
+        hipLaunchKernelGGL(k_mask_scatter, dim3((unsigned) ((nb + 255) / 256)), dim3(256), 0, g_stream0, plane, dindex + start[b], dvalue + start[b],
+                           nb, is_rigmask);
+        HIPCK(hipGetLastError());
+        g_mask_flushes++;
+    }
+    HIPCK(hipStreamSynchronize(g_stream0));
+    tmp.done();
+    return 0;
 }
 
 extern "C" int lqrhip_mask_clear(LqrHipCarver *c, int is_rigmask)
 {
-    float **plane = is_rigmask ? &c->rig0 : &c->bias0;
-    if (!*plane) return 0;
+    DevBuf<float> &plane = is_rigmask ? c->rig0 : c->bias0;
+    if (!plane) return 0;
     int rc = batch_sync_of(c);
     if (rc) return rc;
     HIPCK(hipStreamSynchronize(g_stream0));
-    dfree(*plane);
+    plane.reset();
     // the working copy goes at the next lqrhip_wk_init (ensure_working lays the planes out for the masks the carver has)
     if (c->batch) c->batch->dirty = true;
     return 0;
@@ -837,15 +873,16 @@ extern "C" int lqrhip_read_mask_plane(LqrHipCarver *c, int is_rigmask, int trans
     const float *plane = is_rigmask ? c->rig0 : c->bias0;
     if (!plane) { memset(out, 0, n * sizeof(float)); return 0; }
     if (!transposed) return d2h_staged(out, plane, n * sizeof(float));
-    float *t = nullptr;
-    if ((rc = dmalloc(&t, n))) return rc;
+    Scratch tmp(g_stream0);
+    float *t = tmp.get<float>(n, "&t", rc);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_plane_transpose, dim3((c->w0 + 15) / 16, (c->h0 + 15) / 16), dim3(256), 0, g_stream0, plane, t, c->w0, c->h0);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) rc = d2h_staged(out, t, n * sizeof(float));
-    else { g_err = std::string("k_plane_transpose: ") + hipGetErrorString(e); rc = LQRHIP_EHIP; }
+    if (e != hipSuccess) { g_err = std::string("k_plane_transpose: ") + hipGetErrorString(e); return LQRHIP_EHIP; }
+    if ((rc = d2h_staged(out, t, n * sizeof(float)))) return rc;
     (void) hipStreamSynchronize(g_stream0);
-    dfree(t);
-    return rc;
+    tmp.done();
+    return 0;
 }
 
 // ---- batch -----------------------------------------------------------------
@@ -900,7 +937,7 @@ extern "C" void lqrhip_batch_abort(LqrHipBatch *b)
     if (!b) return;
     (void) hipStreamSynchronize(b->stream);
     (void) hipGetLastError();
-    discard_pending(b);
+    b->pending_inflate.reset();
     if (g_dev_err_host) *g_dev_err_host = 0;
     invalidate_all_batches();
 }
@@ -910,8 +947,6 @@ extern "C" void lqrhip_batch_destroy(LqrHipBatch *b)
     if (!b) return;
     g_live_batches.erase(std::remove(g_live_batches.begin(), g_live_batches.end(), b), g_live_batches.end());
     if (b->stream) { (void) hipStreamSynchronize(b->stream); (void) hipStreamDestroy(b->stream); }
-    discard_pending(b);
-    dfree(b->exch);
     for (auto *c : b->cs) if (c->batch == b) c->batch = nullptr;
     if (b->d_desc) (void) hipFree(b->d_desc);
     delete b;
@@ -927,10 +962,11 @@ extern "C" void *lqrhip_batch_stream(LqrHipBatch *b) { return (void *) b->stream
 static DevCarver make_desc(const LqrHipCarver *c)
 {
     DevCarver d;
-    d.rgb0 = c->rgb0; d.vs = c->vs; d.bias0 = c->bias0; d.rig0 = c->rig0;
-    d.pix = c->pix; d.en = c->en; d.m = c->m; d.least = c->least; d.m2 = c->m2; d.least2 = c->least2; d.bias = c->bias; d.rig = c->rig;
-    d.seam_x = c->seam_x; d.seam_log = c->seam_log; d.flags = c->flags;
-    d.vp_map = c->vp_map; d.vp_path = c->vp_path;
+    const WorkingPlanes &k = c->wk;
+    d.rgb0 = c->rgb0; d.vs = vs_of(c); d.bias0 = c->bias0; d.rig0 = c->rig0;
+    d.pix = k.pix; d.en = k.en; d.m = k.m; d.least = k.least; d.m2 = k.m2; d.least2 = k.least2; d.bias = k.bias; d.rig = k.rig;
+    d.seam_x = k.seam_x; d.seam_log = k.seam_log; d.flags = k.flags;
+    d.vp_map = k.vp_map; d.vp_path = k.vp_path;
     return d;
 }
 
@@ -1075,16 +1111,17 @@ extern "C" int lqrhip_energy_out(LqrHipBatch *b, int w, int h, int transposed, i
     int rc;
     if ((rc = batch_upload(b))) return rc;
     LqrHipCarver *c0 = b->cs[0];
-    if (!c0->en) return LQRHIP_EARG;
+    if (!c0->wk.en) return LQRHIP_EARG;
     const size_t bytes = (size_t) w * h * channels_of[image_type] << depth;
     const int chunks = (w + EO_CHUNK - 1) / EO_CHUNK;
     const int n_partials = form ? (int) std::min((long long) EO_MAX_PARTIALS, (long long) h * chunks) : 0;
-    float *partials = nullptr;
-    uint8_t *staged = nullptr;
-    if (form && (rc = dmalloc(&partials, (size_t) 2 * n_partials))) return rc;
-    if (!on_device && (rc = dmalloc(&staged, bytes))) { dfree(partials); return rc; }
+    Scratch tmp(b->stream);
+    float *partials = form ? tmp.get<float>((size_t) 2 * n_partials, "&partials", rc) : nullptr;
+    if (rc) return rc;
+    uint8_t *staged = on_device ? nullptr : tmp.get<uint8_t>(bytes, "&staged", rc);
+    if (rc) return rc;
     uint8_t *dst = on_device ? (uint8_t *) out : staged;
-    auto run = [&]() -> int {
+    {
         // ("energy_out" in lqrhip_prof_get: the output stage alone, with the bytes it reads and writes)
         ProfScope prof("energy_out", b->stream, (double) w * h * sizeof(float) * (form ? 2 : 1) + (double) bytes);
         if (form == 1) hipLaunchKernelGGL(k_energy_range<false>, dim3(n_partials), dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, partials);
@@ -1096,19 +1133,14 @@ extern "C" int lqrhip_energy_out(LqrHipBatch *b, int w, int h, int transposed, i
             hipLaunchKernelGGL(k_energy_plane, grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, transposed, form, partials, n_partials, (float *) dst);
         else K_ENERGY_OUT_FORMS(CASE) return no_form("k_energy_out");
 #undef CASE
-        return 0;
-    };
-    rc = run();
-    if (!rc) {
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-        if (e != hipSuccess) { g_err = std::string("energy read-out: ") + hipGetErrorString(e); (void) hipGetLastError(); rc = LQRHIP_EHIP; }
     }
-    if (!rc) rc = check_dev_error();
-    if (!rc && !on_device) rc = d2h_staged(out, staged, bytes);
-    if (rc) (void) hipStreamSynchronize(b->stream);
-    dfree(partials); dfree(staged);
-    return rc;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e != hipSuccess) { g_err = std::string("energy read-out: ") + hipGetErrorString(e); (void) hipGetLastError(); return LQRHIP_EHIP; }
+    if ((rc = check_dev_error())) return rc;
+    if (!on_device && (rc = d2h_staged(out, staged, bytes))) return rc;
+    tmp.done();
+    return 0;
 }
 
 // E5 as H/32 dependent launches of one wave per 192-column tile (any batch size)
@@ -1141,7 +1173,7 @@ static PlanBatch plan_batch(const LqrHipBatch *b)
     PlanBatch pb;
     pb.images = (int) b->cs.size(); pb.shared = b->shared; pb.shared_n = b->shared_n; pb.spin = !(b->safe || g_no_spin);
     pb.wk_h = b->cs[0]->wk_h; pb.value = reads_value(b->cs[0]);
-    for (auto *c : b->cs) pb.rigmask |= c->rig != nullptr;
+    for (auto *c : b->cs) pb.rigmask |= c->wk.rig != nullptr;
     return pb;
 }
 extern "C" int lqrhip_general_batch_limit_delta(int w, int delta)
@@ -1156,14 +1188,10 @@ extern "C" int lqrhip_general_batch_limit(int w) { return lqrhip_general_batch_l
 static int exch_ensure(LqrHipBatch *b, size_t need_elems, int ntiles, int n, int layout)
 {
     int rc;
-    if (b->exch_elems < need_elems) {
-        HIPCK(hipStreamSynchronize(b->stream));
-        dfree(b->exch);
-        b->exch_elems = 0;
-        if ((rc = dmalloc(&b->exch, need_elems))) return rc;
-        b->exch_elems = need_elems;
-        b->exch_ntiles = 0;
-    }
+    bool grew = false;
+    if (b->exch.size() < need_elems) HIPCK(hipStreamSynchronize(b->stream));     // (the area in use goes back to the pool)
+    if ((rc = b->exch.ensure(need_elems, "&b->exch", &grew))) return rc;
+    if (grew) b->exch_ntiles = 0;
     if (b->exch_ntiles != ntiles || b->exch_n != n || b->exch_px != layout) {
         HIPCK(hipMemsetAsync(b->exch, 0, need_elems * sizeof(unsigned long long), b->stream));
         b->exch_ntiles = ntiles; b->exch_n = n; b->exch_px = layout;
@@ -1197,15 +1225,19 @@ static int launch_dp_persistent(LqrHipBatch *b, const DpK &k, const DpPlan &dp, 
         // through a tiled update on their own with fresh ones
         bool grew = false;
         for (auto *c : b->cs) {
-            if (c->m2 && c->least2) continue;
+            if (c->wk.m2 && c->wk.least2) continue;
             if (!grew) { HIPCK(hipStreamSynchronize(b->stream)); grew = true; }
             const size_t pe = (size_t) c->stride * (c->wk_h + 1) + 1024;
-            const bool fresh_m2 = !c->m2, fresh_l2 = !c->least2;
-            if (!c->m2 && (rc = dmalloc(&c->m2, pe))) return rc;
-            if (!c->least2 && (rc = dmalloc(&c->least2, pe))) { if (fresh_m2) dfree(c->m2); return rc; }     // (an m2 that was never zeroed must not pass for an old one)
+            // m2 and least2 are made here and dropped in free_working, both times as a pair; the carver gets the zeroed pair or
+            // nothing, so that a plane that was never zeroed cannot pass for an old one
+            DevBuf<float> m2;
+            DevBuf<int8_t> least2;
+            if ((rc = m2.alloc(pe, "&c->m2")) || (rc = least2.alloc(pe, "&c->least2"))) return rc;
             // like the first planes (ensure_working): nothing in them depends on what the block held before
-            if (fresh_m2) HIPCK(hipMemsetAsync(c->m2, 0, pe * sizeof(float), b->stream));
-            if (fresh_l2) HIPCK(hipMemsetAsync(c->least2, 0, pe, b->stream));
+            hipError_t e = hipMemsetAsync(m2, 0, pe * sizeof(float), b->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(least2, 0, pe, b->stream);
+            if (e != hipSuccess) { lqr_stream_wait(b->stream); HIPCK(e); }
+            c->wk.m2 = std::move(m2); c->wk.least2 = std::move(least2);
         }
         if (grew) {
             b->dirty = true;
@@ -1222,7 +1254,7 @@ static int launch_dp_persistent(LqrHipBatch *b, const DpK &k, const DpPlan &dp, 
 #define CASE(CLASS, PX, LR, RIG, UPD, DELTA, RIGM, HLN)                                                                         \
         if constexpr (UPD == UPDATE)                                                                                            \
             if (px_lane == PX && f.lr == LR && f.rig == RIG && f.delta == DELTA && f.rigm == RIGM && hln == HLN) {              \
-                hipLaunchKernelGGL((k_dp_tile_p<PX, LR, RIG, UPD, DELTA, RIGM, HLN>), grid, dim3(64 * DPP_W), 0, b->stream, b->d_desc + first, k, w, h, c0->stride, b->exch, epoch, g_dev_err); \
+                hipLaunchKernelGGL((k_dp_tile_p<PX, LR, RIG, UPD, DELTA, RIGM, HLN>), grid, dim3(64 * DPP_W), 0, b->stream, b->d_desc + first, k, w, h, c0->stride, b->exch.get(), epoch, g_dev_err); \
                 return true;                                                                                                    \
             }
         K_DP_TILE_P_FORMS(CASE)
@@ -1232,7 +1264,7 @@ static int launch_dp_persistent(LqrHipBatch *b, const DpK &k, const DpPlan &dp, 
     if (!found) return no_form("k_dp_tile_p");
     HIPCK(hipGetLastError());
     if (UPDATE)       // the kernel's last tile swapped the pointers in the device descriptors: mirror it
-        for (auto *c : b->cs) { std::swap(c->m, c->m2); std::swap(c->least, c->least2); }
+        for (auto *c : b->cs) { std::swap(c->wk.m, c->wk.m2); std::swap(c->wk.least, c->wk.least2); }
     return 0;
 }
 
@@ -1310,7 +1342,7 @@ static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr
     CENSUS(LQRHIP_CENSUS_BAND_LEVELS);
     const DpForm f = dp_form(k, lr, rigm);
 #define CASE(LR, RIG, DELTA, RIGM) if (f.lr == LR && f.rig == RIG && f.delta == DELTA && f.rigm == RIGM) \
-        hipLaunchKernelGGL((k_band_levels<LR, RIG, DELTA, RIGM>), grid, dim3(128), 0, b->stream, b->d_desc, k, w, h, c0->stride, b->exch, epoch, g_dev_err, P, (int) n); else
+        hipLaunchKernelGGL((k_band_levels<LR, RIG, DELTA, RIGM>), grid, dim3(128), 0, b->stream, b->d_desc, k, w, h, c0->stride, b->exch.get(), epoch, g_dev_err, P, (int) n); else
     K_BAND_LEVELS_FORMS(CASE) return no_form("k_band_levels");
 #undef CASE
     HIPCK(hipGetLastError());
@@ -1338,10 +1370,10 @@ extern "C" int lqrhip_seam_step(LqrHipBatch *b, const LqrHipDpParams *p, int w, 
         std::vector<int> hdr = {w, h, c->stride, log_index, FLAG_COUNT}, flags(FLAG_COUNT), seam(h);
         std::vector<float> m(np);
         std::vector<int8_t> least(np);
-        HIPCK(hipMemcpy(flags.data(), c->flags, FLAG_COUNT * sizeof(int), hipMemcpyDeviceToHost));
-        HIPCK(hipMemcpy(seam.data(), c->seam_x, (size_t) h * sizeof(int), hipMemcpyDeviceToHost));
-        HIPCK(hipMemcpy(m.data(), c->m, np * sizeof(float), hipMemcpyDeviceToHost));
-        HIPCK(hipMemcpy(least.data(), c->least, np, hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(flags.data(), c->wk.flags, FLAG_COUNT * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(seam.data(), c->wk.seam_x, (size_t) h * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(m.data(), c->wk.m, np * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(least.data(), c->wk.least, np, hipMemcpyDeviceToHost));
         char path[512];
         snprintf(path, sizeof path, "%s_%04d.bin", dump, call++);
         if (FILE *f = fopen(path, "wb")) {
@@ -1375,14 +1407,14 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
     const int moved_unit = 2 * (4 + (move_dp ? 5 : 0) + (pb.rigmask ? 4 : 0));
     if (s.backtrack == LQRHIP_CENSUS_VP_PARALLEL) {
         const int nchunks = s.vp_chunks, R4 = (s.vp_rows + 3) / 4;
-        const size_t need = (size_t) (nchunks + 1) * stride + 64;
+        const size_t need = (size_t) (nchunks + 1) * stride + 64, need_path = need * 4 * R4;      // (R4 depends on delta_x: each answers for its own size)
         bool grew = false;
         for (auto *c : b->cs) {
-            if (c->vp_map && c->vp_path && c->vp_cap >= need) continue;
+            WorkingPlanes &wp = c->wk;
+            if (wp.vp_map.size() >= need && wp.vp_path.size() >= need_path) continue;
             if (!grew) { HIPCK(hipStreamSynchronize(b->stream)); grew = true; }
-            dfree(c->vp_map); dfree(c->vp_path); c->vp_cap = 0;
-            if ((rc = dmalloc(&c->vp_map, need)) || (rc = dmalloc(&c->vp_path, need * 4 * R4))) return rc;
-            c->vp_cap = need;
+            wp.vp_map.reset(); wp.vp_path.reset();
+            if ((rc = wp.vp_map.alloc(need, "&c->vp_map")) || (rc = wp.vp_path.alloc(need_path, "&c->vp_path"))) return rc;
         }
         if (grew) { b->dirty = true; if ((rc = batch_upload(b))) return rc; }
         ProfScope ps("vpath", b->stream, 0);
@@ -1530,7 +1562,7 @@ extern "C" int lqrhip_session_check(LqrHipBatch *b, int h, int wc0, int n_seams,
 extern "C" int lqrhip_session_rollback(LqrHipBatch *b, int w0, int h0, int first_level, int finish)
 {
     (void) hipStreamSynchronize(b->stream);
-    discard_pending(b);
+    b->pending_inflate.reset();
     (void) hipGetLastError();
     if (g_dev_err_host) *g_dev_err_host = 0;
     invalidate_all_batches();
@@ -1567,126 +1599,60 @@ static void inject_after_commit(LqrHipBatch *b, int w0, int h0, int first_level)
     g_inject_times--; g_fault_stats[5]++;
 }
 
-// E14 / E11: every carver of the batch (roots and their attached carvers) goes through ONE launch (a job table in device
-// memory, one grid slice of blocks per job); the new planes replace the old ones after its synchronisation.  Everything
-// staged for the pass is owned by a PlaneJobs object until then: any error return gives all of it back to the pool.
-struct PlaneJob {
-    LqrHipCarver *c;
-    uint8_t *nrgb;
-    float *nbias, *nrig;
+// A pass being staged (phase one).  The batch owns what is staged from the first block on; a return before kept() is an error return:
+// the stream is drained and everything staged goes back to the pool
+namespace {
+struct Staging {
+    LqrHipBatch *b;
+    bool keep = false;
+    Staging(LqrHipBatch *batch, int kind, int w1, int h1) : b(batch)
+    {
+        b->pending_inflate.reset(new PendingInflate());         // (in place of a staged pass nobody committed)
+        b->pending_inflate->kind = kind; b->pending_inflate->w1 = w1; b->pending_inflate->h1 = h1;
+    }
+    ~Staging() { if (!keep) { lqr_stream_wait(b->stream); b->pending_inflate.reset(); } }
+    PlaneJobs &jobs() const { return b->pending_inflate->pj; }
+    int kept() { keep = true; return 0; }
 };
-struct PlaneJobs {
-    std::vector<PlaneJob> jobs;
-    std::vector<int32_t *> new_vs;          // one per root (may be null)
-    // the job table (ch = bytes per pixel), ordered by the form of the kernel that takes each job (stage()): the first n_narrow go
-    // to the pass's 8-bit kernel, the others to its deep form / k_transpose_px (lqr_pixel.h: 16-byte accesses where they fit)
-    std::vector<InflateDev> dev;
-    InflateDev *d_dev = nullptr;
-    size_t n_narrow = 0;
-    bool committed = false;
-    ~PlaneJobs()
-    {
-        dfree(d_dev);
-        if (committed) return;
-        for (auto &j : jobs) { dfree(j.nrgb); dfree(j.nbias); dfree(j.nrig); }
-        for (auto *&v : new_vs) dfree(v);
-    }
-    // stage the output planes of carver c: n1 pixels each
-    int add(LqrHipCarver *c, const int32_t *vs_old, int32_t *nvs, size_t n1)
-    {
-        PlaneJob j{c, nullptr, nullptr, nullptr};
-        int rc = dmalloc(&j.nrgb, n1 * px_bytes(c));
-        if (!rc && c->bias0) rc = dmalloc(&j.nbias, n1);
-        if (!rc && c->rig0) rc = dmalloc(&j.nrig, n1);
-        jobs.push_back(j);                  // owned from here on, also when rc != 0
-        if (rc) return rc;
-        dev.push_back(InflateDev{c->rgb0, vs_old, c->bias0, c->rig0, j.nrgb, nvs, j.nbias, j.nrig, (int) px_bytes(c), c->depth});
-        return 0;
-    }
-    // the table to the device.  Transpose and flatten (by_width) keep pixels of up to 4 bytes on the 8-bit kernels, which move them
-    // as bytes / one dword; inflate averages, so only 8-bit pixels of up to 4 channels stay there
-    int stage(hipStream_t s, bool by_width)
-    {
-        n_narrow = std::stable_partition(dev.begin(), dev.end(), [&](const InflateDev &d) { return d.ch <= 4 && (by_width || d.depth == 0); }) - dev.begin();
-        int rc = dmalloc(&d_dev, dev.size());
-        if (rc) return rc;
-        HIPCK(hipMemcpyAsync(d_dev, dev.data(), dev.size() * sizeof(InflateDev), hipMemcpyHostToDevice, s));
-        return 0;
-    }
-    size_t n_wide() const { return dev.size() - n_narrow; }
-    const InflateDev *d_wide() const { return d_dev + n_narrow; }
-    // after the pass has completed: the new base planes become the carvers'
-    void commit()
-    {
-        for (auto &j : jobs) {
-            dfree(j.c->rgb0); j.c->rgb0 = j.nrgb;
-            if (j.nbias) { dfree(j.c->bias0); j.c->bias0 = j.nbias; }
-            if (j.nrig) { dfree(j.c->rig0); j.c->rig0 = j.nrig; }
-        }
-        committed = true;
-    }
-};
-
-// Two phases (round 6): lqrhip_inflate / lqrhip_flatten / lqrhip_transpose stage the new planes of the batch, run the pass (the inflate
-// pass with its fused self-check) and ADOPT NOTHING; lqrhip_planes_commit adopts what was staged.  The host runs phase one on every
-// sub-batch of a group before it commits any: a failed check or a failed allocation in sub-batch k must not find sub-batches 0 .. k - 1
-// already living in their new layouts (the roll-back / the error return leaves the whole group where it was).
-// lqrhip_session_rollback / lqrhip_batch_abort / lqrhip_batch_destroy discard a staged pass.
-struct PendingInflate { PlaneJobs pj; int kind = 0 /* 0 inflate, 1 flatten, 2 transpose */, w1 = 0, h1 = 0; };
-static void discard_pending(LqrHipBatch *b) { delete (PendingInflate *) b->pending_inflate; b->pending_inflate = nullptr; }
-static PendingInflate *new_pending(LqrHipBatch *b, int kind, int w1, int h1)
-{
-    discard_pending(b);
-    PendingInflate *pi = new PendingInflate();
-    b->pending_inflate = pi;                // owned by the batch from here on, whatever happens below
-    pi->kind = kind; pi->w1 = w1; pi->h1 = h1;
-    return pi;
-}
+}  // namespace
 extern "C" int lqrhip_inflate(LqrHipBatch *b, int w0, int h0, int l, int max_level)
 {
     int rc;
     const int w1 = w0 + l - max_level + 1;
-    PlaneJobs &pj = new_pending(b, 0, w1, h0)->pj;
-    auto run = [&]() -> int {
-        for (auto *c : b->cs) {
-            int32_t *nvs = nullptr;
-            if ((rc = dmalloc(&nvs, (size_t) w1 * h0))) return rc;
-            pj.new_vs.push_back(nvs);
-            for (auto *a : c->aux)
-                if ((rc = pj.add(a, c->vs, nullptr, (size_t) w1 * h0))) return rc;
-            if ((rc = pj.add(c, c->vs, nvs, (size_t) w1 * h0))) return rc;
-        }
-        if ((rc = pj.stage(b->stream, false))) return rc;
-        const size_t lds = (size_t) ((l - max_level + 1 + 31) / 32 + 1) * sizeof(unsigned);      // one bit per level of the session (the fused self-check)
-        if (pj.n_narrow)
-            hipLaunchKernelGGL(k_inflate<false>, dim3(h0, (unsigned) pj.n_narrow), dim3(256), lds, b->stream, pj.d_dev, w0, w1, l, max_level, g_selfcheck ? g_dev_err : (int *) nullptr);
-        if (pj.n_wide())
-            hipLaunchKernelGGL(k_inflate<true>, dim3(h0, (unsigned) pj.n_wide()), dim3(256), lds, b->stream, pj.d_wide(), w0, w1, l, max_level, g_selfcheck ? g_dev_err : (int *) nullptr);
-        HIPCK(hipGetLastError());
-        HIPCK(hipStreamSynchronize(b->stream));
-        return check_dev_error();           // a failed level check: nothing is adopted, the host rolls the session back
-    };
-    rc = run();
-    if (rc) { (void) hipStreamSynchronize(b->stream); discard_pending(b); }
-    return rc;
+    Staging st(b, 0, w1, h0);
+    PlaneJobs &pj = st.jobs();
+    for (auto *c : b->cs) {
+        pj.new_vs.emplace_back();
+        DevBuf<int32_t> &nvs = pj.new_vs.back();
+        if ((rc = nvs.alloc((size_t) w1 * h0, "&nvs"))) return rc;
+        for (auto *a : c->aux)
+            if ((rc = pj.add(a, c->vs, nullptr, (size_t) w1 * h0))) return rc;
+        if ((rc = pj.add(c, c->vs, nvs, (size_t) w1 * h0))) return rc;
+    }
+    if ((rc = pj.stage(b->stream, false))) return rc;
+    const size_t lds = (size_t) ((l - max_level + 1 + 31) / 32 + 1) * sizeof(unsigned);      // one bit per level of the session (the fused self-check)
+    if (pj.n_narrow)
+        hipLaunchKernelGGL(k_inflate<false>, dim3(h0, (unsigned) pj.n_narrow), dim3(256), lds, b->stream, pj.d_dev.get(), w0, w1, l, max_level, g_selfcheck ? g_dev_err : (int *) nullptr);
+    if (pj.n_wide())
+        hipLaunchKernelGGL(k_inflate<true>, dim3(h0, (unsigned) pj.n_wide()), dim3(256), lds, b->stream, pj.d_wide(), w0, w1, l, max_level, g_selfcheck ? g_dev_err : (int *) nullptr);
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(b->stream));
+    if ((rc = check_dev_error())) return rc;            // a failed level check: nothing is adopted, the host rolls the session back
+    return st.kept();
 }
 extern "C" int lqrhip_planes_commit(LqrHipBatch *b)
 {
-    PendingInflate *pi = (PendingInflate *) b->pending_inflate;
+    PendingInflate *pi = b->pending_inflate.get();
     if (!pi) return LQRHIP_EARG;
     PlaneJobs &pj = pi->pj;
-    pj.commit();
+    commit(pj);
     for (auto &j : pj.jobs) { j.c->w0 = pi->w1; j.c->h0 = pi->h1; }
     if (pi->kind != 2) {                    // (a transpose keeps the carvers' -- all zero -- visibility maps)
         size_t i = 0;
-        for (auto *c : b->cs) {
-            dfree(c->vs);
-            c->vs = pj.new_vs[i++];
-            for (auto *a : c->aux) a->vs = c->vs;
-        }
+        for (auto *c : b->cs) c->vs = std::move(pj.new_vs[i++]);
     }
     b->dirty = true;
-    discard_pending(b);                     // (committed: the destructor frees only the job table)
+    b->pending_inflate.reset();             // (what is left of it: the job table)
     return 0;
 }
 extern "C" int lqrhip_inflate_commit(LqrHipBatch *b) { return lqrhip_planes_commit(b); }
@@ -1694,61 +1660,53 @@ extern "C" int lqrhip_inflate_commit(LqrHipBatch *b) { return lqrhip_planes_comm
 extern "C" int lqrhip_flatten(LqrHipBatch *b, int w0, int h0, int w, int level)
 {
     int rc;
-    PlaneJobs &pj = new_pending(b, 1, w, h0)->pj;
-    auto run = [&]() -> int {
-        for (auto *c : b->cs) {
-            int32_t *nvs = nullptr;                 // the flat carver's visibility map: all zero
-            if ((rc = dmalloc(&nvs, (size_t) w * h0))) return rc;
-            pj.new_vs.push_back(nvs);
-            HIPCK(hipMemsetAsync(nvs, 0, (size_t) w * h0 * sizeof(int32_t), b->stream));
-            for (auto *a : c->aux)
-                if ((rc = pj.add(a, c->vs, nullptr, (size_t) w * h0))) return rc;
-            if ((rc = pj.add(c, c->vs, nullptr, (size_t) w * h0))) return rc;
-        }
-        if ((rc = pj.stage(b->stream, true))) return rc;
-        if (pj.n_narrow)
-            hipLaunchKernelGGL(k_compact_jobs<false>, dim3(h0, (unsigned) pj.n_narrow), dim3(256), 0, b->stream, pj.d_dev, w0, w, level);
-        if (pj.n_wide())
-            hipLaunchKernelGGL(k_compact_jobs<true>, dim3(h0, (unsigned) pj.n_wide()), dim3(256), 0, b->stream, pj.d_wide(), w0, w, level);
-        HIPCK(hipGetLastError());
-        HIPCK(hipStreamSynchronize(b->stream));
-        return 0;
-    };
-    rc = run();
-    if (rc) { (void) hipStreamSynchronize(b->stream); discard_pending(b); }
-    return rc;
+    Staging st(b, 1, w, h0);
+    PlaneJobs &pj = st.jobs();
+    for (auto *c : b->cs) {
+        pj.new_vs.emplace_back();
+        DevBuf<int32_t> &nvs = pj.new_vs.back();        // the flat carver's visibility map: all zero
+        if ((rc = nvs.alloc((size_t) w * h0, "&nvs"))) return rc;
+        HIPCK(hipMemsetAsync(nvs, 0, (size_t) w * h0 * sizeof(int32_t), b->stream));
+        for (auto *a : c->aux)
+            if ((rc = pj.add(a, c->vs, nullptr, (size_t) w * h0))) return rc;
+        if ((rc = pj.add(c, c->vs, nullptr, (size_t) w * h0))) return rc;
+    }
+    if ((rc = pj.stage(b->stream, true))) return rc;
+    if (pj.n_narrow)
+        hipLaunchKernelGGL(k_compact_jobs<false>, dim3(h0, (unsigned) pj.n_narrow), dim3(256), 0, b->stream, pj.d_dev.get(), w0, w, level);
+    if (pj.n_wide())
+        hipLaunchKernelGGL(k_compact_jobs<true>, dim3(h0, (unsigned) pj.n_wide()), dim3(256), 0, b->stream, pj.d_wide(), w0, w, level);
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(b->stream));
+    return st.kept();
 }
 
 extern "C" int lqrhip_transpose(LqrHipBatch *b, int w, int h)
 {
     int rc;
-    PlaneJobs &pj = new_pending(b, 2, h, w)->pj;
-    auto run = [&]() -> int {
-        for (auto *c : b->cs) {
-            for (auto *a : c->aux)
-                if ((rc = pj.add(a, nullptr, nullptr, (size_t) w * h))) return rc;
-            if ((rc = pj.add(c, nullptr, nullptr, (size_t) w * h))) return rc;
-            HIPCK(hipMemsetAsync(c->vs, 0, (size_t) w * h * sizeof(int32_t), b->stream));   // flat carver: all zero already
-        }
-        if ((rc = pj.stage(b->stream, true))) return rc;
-        if (pj.n_narrow)
-            hipLaunchKernelGGL(k_transpose, dim3((w + 31) / 32, (h + 31) / 32, (unsigned) pj.n_narrow), dim3(32, 8), 0, b->stream, pj.d_dev, w, h);
-        if (pj.n_wide())
-            hipLaunchKernelGGL(k_transpose_px, dim3((w + 31) / 32, (h + 31) / 32, (unsigned) pj.n_wide()), dim3(32, 8), 0, b->stream, pj.d_wide(), w, h);
-        HIPCK(hipGetLastError());
-        HIPCK(hipStreamSynchronize(b->stream));
-        return 0;
-    };
-    rc = run();
-    if (rc) { (void) hipStreamSynchronize(b->stream); discard_pending(b); }
-    return rc;
+    Staging st(b, 2, h, w);
+    PlaneJobs &pj = st.jobs();
+    for (auto *c : b->cs) {
+        for (auto *a : c->aux)
+            if ((rc = pj.add(a, nullptr, nullptr, (size_t) w * h))) return rc;
+        if ((rc = pj.add(c, nullptr, nullptr, (size_t) w * h))) return rc;
+        HIPCK(hipMemsetAsync(c->vs, 0, (size_t) w * h * sizeof(int32_t), b->stream));   // flat carver: all zero already
+    }
+    if ((rc = pj.stage(b->stream, true))) return rc;
+    if (pj.n_narrow)
+        hipLaunchKernelGGL(k_transpose, dim3((w + 31) / 32, (h + 31) / 32, (unsigned) pj.n_narrow), dim3(32, 8), 0, b->stream, pj.d_dev.get(), w, h);
+    if (pj.n_wide())
+        hipLaunchKernelGGL(k_transpose_px, dim3((w + 31) / 32, (h + 31) / 32, (unsigned) pj.n_wide()), dim3(32, 8), 0, b->stream, pj.d_wide(), w, h);
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(b->stream));
+    return st.kept();
 }
 
 // ---- read-back ---------------------------------------------------------------
 // the pixels of carver c visible at `level`, compacted into device memory (w x h0 pixels); on g_stream0, not synchronised
 static void launch_read_visible(const LqrHipCarver *c, int w0, int h0, int w, int level, uint8_t *d)
 {
-#define LAUNCH_RV(DEEP) hipLaunchKernelGGL(k_compact<DEEP>, dim3(h0), dim3(256), 0, g_stream0, c->rgb0, c->vs, (const float *) nullptr, (const float *) nullptr, \
+#define LAUNCH_RV(DEEP) hipLaunchKernelGGL(k_compact<DEEP>, dim3(h0), dim3(256), 0, g_stream0, c->rgb0.get(), vs_of(c), (const float *) nullptr, (const float *) nullptr, \
                                            d, (float *) nullptr, (float *) nullptr, (int32_t *) nullptr, w0, w, (int) px_bytes(c), level, 0)
     if (px_bytes(c) > 4) LAUNCH_RV(true); else LAUNCH_RV(false);
 #undef LAUNCH_RV
@@ -1757,18 +1715,15 @@ extern "C" int lqrhip_read_visible(LqrHipCarver *c, int w0, int h0, int w, int l
 {
     int rc = batch_sync_of(c);
     if (rc) return rc;
-    uint8_t *d = nullptr;
     size_t n = (size_t) w * h0 * px_bytes(c);
-    if ((rc = dmalloc(&d, n))) return rc;
-    auto run = [&]() -> int {
-        launch_read_visible(c, w0, h0, w, level, d);
-        HIPCK(hipGetLastError());
-        return d2h_staged(out, d, n);
-    };
-    rc = run();
-    if (rc) (void) hipStreamSynchronize(g_stream0);
-    dfree(d);
-    return rc;
+    Scratch tmp(g_stream0);
+    uint8_t *d = tmp.get<uint8_t>(n, "&d", rc);
+    if (rc) return rc;
+    launch_read_visible(c, w0, h0, w, level, d);
+    HIPCK(hipGetLastError());
+    if ((rc = d2h_staged(out, d, n))) return rc;
+    tmp.done();
+    return 0;
 }
 
 extern "C" int lqrhip_read_visible_device(LqrHipCarver *c, int w0, int h0, int w, int level, void *device_out)
@@ -1786,24 +1741,21 @@ extern "C" int lqrhip_mask_line_max(const unsigned char *mask, int channels, int
 {
     if (lqrhip_init() < 0) return LQRHIP_EHIP;
     if (n_lines <= 0 || line_len <= 0) return 0;
-    uint8_t *d = nullptr;
-    int *dout = nullptr;
     int rc, result = 0;
     size_t bytes = (size_t) width * height * channels;
-    if ((rc = dmalloc(&d, bytes)) || (rc = dmalloc(&dout, 1))) { dfree(d); return rc; }
-    auto run = [&]() -> int {
-        HIPCK(hipMemcpyAsync(d, mask, bytes, hipMemcpyHostToDevice, g_stream0));
-        HIPCK(hipMemsetAsync(dout, 0, sizeof(int), g_stream0));
-        hipLaunchKernelGGL(k_mask_line_max, dim3(n_lines), dim3(256), 0, g_stream0, d, channels, width, a0, b0, line_len, direction, dout);
-        HIPCK(hipGetLastError());
-        HIPCK(hipMemcpyAsync(&result, dout, sizeof(int), hipMemcpyDeviceToHost, g_stream0));
-        HIPCK(hipStreamSynchronize(g_stream0));
-        return 0;
-    };
-    rc = run();
-    if (rc) (void) hipStreamSynchronize(g_stream0);
-    dfree(d); dfree(dout);
-    return rc ? rc : result;
+    Scratch tmp(g_stream0);
+    uint8_t *d = tmp.get<uint8_t>(bytes, "&d", rc);
+    if (rc) return rc;
+    int *dout = tmp.get<int>(1, "&dout", rc);
+    if (rc) return rc;
+    HIPCK(hipMemcpyAsync(d, mask, bytes, hipMemcpyHostToDevice, g_stream0));
+    HIPCK(hipMemsetAsync(dout, 0, sizeof(int), g_stream0));
+    hipLaunchKernelGGL(k_mask_line_max, dim3(n_lines), dim3(256), 0, g_stream0, d, channels, width, a0, b0, line_len, direction, dout);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(&result, dout, sizeof(int), hipMemcpyDeviceToHost, g_stream0));
+    HIPCK(hipStreamSynchronize(g_stream0));
+    tmp.done();
+    return result;
 }
 
 extern "C" void lqrhip_pool_trim(void)
@@ -1824,43 +1776,40 @@ extern "C" int lqrhip_read_vmap(LqrHipCarver *c, int w0, int h0, int w, int leve
 {
     int rc = batch_sync_of(c);
     if (rc) return rc;
-    int32_t *d = nullptr;
     size_t n = (size_t) w * h0;
-    if ((rc = dmalloc(&d, n))) return rc;
-    auto run = [&]() -> int {
-        hipLaunchKernelGGL(k_compact<false>, dim3(h0), dim3(256), 0, g_stream0, (const uint8_t *) nullptr, c->vs, (const float *) nullptr,
-                           (const float *) nullptr, (uint8_t *) nullptr, (float *) nullptr, (float *) nullptr, d, w0, w, c->ch, level,
-                           depth);
-        HIPCK(hipGetLastError());
-        return d2h_staged(out, d, n * sizeof(int32_t));
-    };
-    rc = run();
-    if (rc) (void) hipStreamSynchronize(g_stream0);
-    dfree(d);
-    return rc;
+    Scratch tmp(g_stream0);
+    int32_t *d = tmp.get<int32_t>(n, "&d", rc);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_compact<false>, dim3(h0), dim3(256), 0, g_stream0, (const uint8_t *) nullptr, vs_of(c), (const float *) nullptr,
+                       (const float *) nullptr, (uint8_t *) nullptr, (float *) nullptr, (float *) nullptr, d, w0, w, c->ch, level,
+                       depth);
+    HIPCK(hipGetLastError());
+    if ((rc = d2h_staged(out, d, n * sizeof(int32_t)))) return rc;
+    tmp.done();
+    return 0;
 }
 
 extern "C" int lqrhip_read_working(LqrHipCarver *c, int w, int h, float *en, float *m, int *least_dx)
 {
     int rc = batch_sync_of(c);
     if (rc) return rc;
-    if (!c->pix) return LQRHIP_EARG;
+    if (!c->wk.pix) return LQRHIP_EARG;
     int32_t fl[FLAG_COUNT];
-    HIPCK(hipMemcpy(fl, c->flags, sizeof fl, hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(fl, c->wk.flags, sizeof fl, hipMemcpyDeviceToHost));
     const int org = fl[FLAG_ORG];                 // the carved planes start `org` elements into each row
     size_t n = (size_t) c->stride * h;
     std::vector<float> t(n);
     std::vector<int8_t> tl(n);
     if (en) {
-        HIPCK(hipMemcpy(t.data(), c->en, n * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(t.data(), c->wk.en, n * sizeof(float), hipMemcpyDeviceToHost));
         for (int y = 0; y < h; y++) memcpy(en + (size_t) y * w, t.data() + (size_t) y * c->stride + org, (size_t) w * sizeof(float));
     }
     if (m) {
-        HIPCK(hipMemcpy(t.data(), c->m, n * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(t.data(), c->wk.m, n * sizeof(float), hipMemcpyDeviceToHost));
         for (int y = 0; y < h; y++) memcpy(m + (size_t) y * w, t.data() + (size_t) y * c->stride + org, (size_t) w * sizeof(float));
     }
     if (least_dx) {
-        HIPCK(hipMemcpy(tl.data(), c->least, n, hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(tl.data(), c->wk.least, n, hipMemcpyDeviceToHost));
         for (int y = 0; y < h; y++)
             for (int x = 0; x < w; x++) least_dx[(size_t) y * w + x] = y == 0 ? 0 : (int) tl[(size_t) y * c->stride + org + x];
     }
@@ -1871,16 +1820,17 @@ extern "C" int lqrhip_read_working(LqrHipCarver *c, int w, int h, float *en, flo
 __global__ __launch_bounds__(256) void k_copy16(const u32x4 *__restrict__ src, u32x4 *__restrict__ dst, size_t n16);
 extern "C" int lqrhip_carver_reset(LqrHipCarver *c, const void *device_rgb, int w, int h)
 {
+    // roots without attached carvers only: an attached carver holds no visibility map of its own (vs_of)
     if (!c || c->root || !c->aux.empty() || w < 1 || h < 1) return LQRHIP_EARG;
     int rc = batch_sync_of(c);
     if (rc) return rc;
     const size_t n = (size_t) w * h;
-    dfree(c->rgb0); dfree(c->vs); dfree(c->bias0); dfree(c->rig0);
+    c->rgb0.reset(); c->vs.reset(); c->bias0.reset(); c->rig0.reset();
     // a carver that had masks carries bias / rig working planes: the fresh carver has none
-    if (c->bias || c->rig) { free_working(c); c->stride = 0; c->wk_h = 0; }
+    if (c->wk.bias || c->wk.rig) { free_working(c); c->stride = 0; c->wk_h = 0; }
     c->w0 = w; c->h0 = h;
     c->frozen_epoch = 0;
-    if ((rc = dmalloc(&c->rgb0, n * px_bytes(c))) || (rc = dmalloc(&c->vs, n))) return rc;
+    if ((rc = c->rgb0.alloc(n * px_bytes(c), "&c->rgb0")) || (rc = c->vs.alloc(n, "&c->vs"))) return rc;
     // (round 6: these copies on four more streams side by side -- one 33 MB device-to-device copy runs at ~0.5 TB/s, 64 of them are 4 ms of a
     // 190-ms step -- made the 64-image step 45 % LONGER: with g_stream0 and the four sub-batch streams that is nine streams on the
     // process's eight hardware queues, and sub-batch streams that share a queue run one after the other.  One stream.)
@@ -1888,8 +1838,8 @@ extern "C" int lqrhip_carver_reset(LqrHipCarver *c, const void *device_rgb, int 
         // the runtime's device-to-device copy kernel moves a 33 MB image in 66 us (0.5 TB/s; 64 of them: 4.2 ms of a 190-ms step, one after
         // the other); the engine's own streaming copy (k_copy16, the one that measures the HBM ceiling) takes ~10
         const size_t bytes = n * px_bytes(c), n16 = bytes / 16;
-        if (n16 && !(((uintptr_t) device_rgb | (uintptr_t) c->rgb0) & 15)) {
-            hipLaunchKernelGGL(k_copy16, dim3((unsigned) ((n16 + 255) / 256)), dim3(256), 0, g_stream0, (const u32x4 *) device_rgb, (u32x4 *) c->rgb0, n16);
+        if (n16 && !(((uintptr_t) device_rgb | (uintptr_t) c->rgb0.get()) & 15)) {
+            hipLaunchKernelGGL(k_copy16, dim3((unsigned) ((n16 + 255) / 256)), dim3(256), 0, g_stream0, (const u32x4 *) device_rgb, (u32x4 *) c->rgb0.get(), n16);
             HIPCK(hipGetLastError());
             if (bytes & 15) HIPCK(hipMemcpyAsync(c->rgb0 + n16 * 16, (const uint8_t *) device_rgb + n16 * 16, bytes & 15, hipMemcpyDeviceToDevice, g_stream0));
         } else {
@@ -1933,30 +1883,25 @@ extern "C" int lqrhip_copy_bandwidth(unsigned long long bytes, int iters, double
 {
     if (lqrhip_init() < 0) return LQRHIP_EHIP;
     if (iters < 1 || bytes < 4096) return LQRHIP_EARG;
-    uint8_t *a = nullptr, *b = nullptr;
+    struct Event { hipEvent_t e = nullptr; ~Event() { if (e) (void) hipEventDestroy(e); } } e0, e1;      // (destroyed after the Scratch has waited)
     int rc;
-    if ((rc = dmalloc(&a, bytes)) || (rc = dmalloc(&b, bytes))) { dfree(a); return rc; }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    Scratch tmp(g_stream0);
+    uint8_t *a = tmp.get<uint8_t>(bytes, "&a", rc);
+    if (rc) return rc;
+    uint8_t *b = tmp.get<uint8_t>(bytes, "&b", rc);
+    if (rc) return rc;
     float ms = 0;
     const size_t n16 = bytes / 16;
-    auto run = [&]() -> int {
-        HIPCK(hipMemsetAsync(a, 1, bytes, g_stream0));
-        HIPCK(hipEventCreate(&e0)); HIPCK(hipEventCreate(&e1));
-        const dim3 grid((unsigned) ((n16 + 255) / 256));
-        hipLaunchKernelGGL(k_copy16, grid, dim3(256), 0, g_stream0, (const u32x4 *) a, (u32x4 *) b, n16);     // warm-up
-        HIPCK(hipEventRecord(e0, g_stream0));
-        for (int i = 0; i < iters; i++) hipLaunchKernelGGL(k_copy16, grid, dim3(256), 0, g_stream0, (const u32x4 *) a, (u32x4 *) b, n16);
-        HIPCK(hipEventRecord(e1, g_stream0));
-        HIPCK(hipStreamSynchronize(g_stream0));
-        HIPCK(hipEventElapsedTime(&ms, e0, e1));
-        return 0;
-    };
-    rc = run();
-    if (rc) (void) hipStreamSynchronize(g_stream0);
-    if (e0) (void) hipEventDestroy(e0);
-    if (e1) (void) hipEventDestroy(e1);
-    dfree(a); dfree(b);
-    if (rc) return rc;
+    HIPCK(hipMemsetAsync(a, 1, bytes, g_stream0));
+    HIPCK(hipEventCreate(&e0.e)); HIPCK(hipEventCreate(&e1.e));
+    const dim3 grid((unsigned) ((n16 + 255) / 256));
+    hipLaunchKernelGGL(k_copy16, grid, dim3(256), 0, g_stream0, (const u32x4 *) a, (u32x4 *) b, n16);     // warm-up
+    HIPCK(hipEventRecord(e0.e, g_stream0));
+    for (int i = 0; i < iters; i++) hipLaunchKernelGGL(k_copy16, grid, dim3(256), 0, g_stream0, (const u32x4 *) a, (u32x4 *) b, n16);
+    HIPCK(hipEventRecord(e1.e, g_stream0));
+    HIPCK(hipStreamSynchronize(g_stream0));
+    HIPCK(hipEventElapsedTime(&ms, e0.e, e1.e));
+    tmp.done();
     if (gbps) *gbps = 2.0 * (double) (n16 * 16) * iters / (ms * 1e-3) / 1e9;
     return 0;
 }
@@ -1992,21 +1937,18 @@ extern "C" int lqrhip_vmap_to_rgba(const int *vmap, int w, int h, int depth, con
     if (lqrhip_init() < 0) return LQRHIP_EHIP;
     if (!vmap || !out_rgba || w < 1 || h < 1) return LQRHIP_EARG;
     const size_t n = (size_t) w * h;
-    int32_t *dv = nullptr;
-    uint32_t *dout = nullptr;
     int rc;
-    if ((rc = dmalloc(&dv, n)) || (rc = dmalloc(&dout, n))) { dfree(dv); return rc; }
-    auto run = [&]() -> int {
-        HIPCK(hipMemcpyAsync(dv, vmap, n * sizeof(int32_t), hipMemcpyHostToDevice, g_stream0));
-        hipLaunchKernelGGL(k_vmap_ramp, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, g_stream0, dv, dout, n, depth, col_start[0], col_start[1],
-                           col_start[2], col_end[0], col_end[1], col_end[2]);
-        HIPCK(hipGetLastError());
-        HIPCK(hipMemcpyAsync(out_rgba, dout, n * 4, hipMemcpyDeviceToHost, g_stream0));
-        HIPCK(hipStreamSynchronize(g_stream0));
-        return 0;
-    };
-    rc = run();
-    if (rc) (void) hipStreamSynchronize(g_stream0);      // nothing may still use the blocks when they go back to the pool
-    dfree(dv); dfree(dout);
-    return rc;
+    Scratch tmp(g_stream0);
+    int32_t *dv = tmp.get<int32_t>(n, "&dv", rc);
+    if (rc) return rc;
+    uint32_t *dout = tmp.get<uint32_t>(n, "&dout", rc);
+    if (rc) return rc;
+    HIPCK(hipMemcpyAsync(dv, vmap, n * sizeof(int32_t), hipMemcpyHostToDevice, g_stream0));
+    hipLaunchKernelGGL(k_vmap_ramp, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, g_stream0, dv, dout, n, depth, col_start[0], col_start[1],
+                       col_start[2], col_end[0], col_end[1], col_end[2]);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(out_rgba, dout, n * 4, hipMemcpyDeviceToHost, g_stream0));
+    HIPCK(hipStreamSynchronize(g_stream0));
+    tmp.done();
+    return 0;
 }

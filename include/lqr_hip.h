@@ -198,6 +198,9 @@ void lqrhip_debug_inject(int kind, int at_step, int times);
 /* Test hook: the nth device allocation from now on (0 = the next one) fails once with LQRHIP_ENOMEM; -1 disarms.  What the host side
  * owes its caller then: LQR_NOMEM (the one value src/render.c:42-46 tests for) and a carver that is still consistent. */
 void lqrhip_debug_fail_alloc(int nth);
+/* Test hook: device blocks of the allocation cache handed out and not yet given back.  A call that fails, and a carver or batch that
+ * is destroyed, leave the count where it was before. */
+unsigned long long lqrhip_debug_pool_live(void);
 /* The three passes that replace a batch's base planes run in TWO PHASES: the call stages the new planes and runs the pass -- nothing of
  * the carvers changes -- and lqrhip_planes_commit adopts what was staged.  A group commits only after every one of its sub-batches has
  * passed phase one, so that a failed self-check (LQRHIP_EFAULT) or a failed allocation (LQRHIP_ENOMEM) in one sub-batch leaves the

@@ -12,6 +12,7 @@
 * an allocation failure at every allocation point of one read-out; tests/c/energy_replay.c linked to the engine.
 """
 import ctypes
+import gc
 import json
 import os
 import subprocess
@@ -186,6 +187,7 @@ def test_device_forms_equal_the_host_forms_also_one_element_off_an_allocation(en
 def test_an_allocation_failure_at_every_point_of_a_read_out_leaves_a_usable_carver(eng):
     lib = eng.lib
     lib.lqrhip_debug_fail_alloc.argtypes = [ctypes.c_int]
+    lib.lqrhip_debug_pool_live.restype, lib.lqrhip_debug_pool_live.argtypes = ctypes.c_ulonglong, []
     w, h = 70, 66
     img = _image(w, h)
     ref = _carver(eng, img)
@@ -193,9 +195,11 @@ def test_an_allocation_failure_at_every_point_of_a_read_out_leaves_a_usable_carv
     assert ref.resize(w - 5, h) == 1
     want_image = ref.read_image_ext()
     ref.destroy()
+    gc.collect()            # (a carver that an earlier, failed test left to the collector would go while the blocks are counted)
     failures = 0
     try:
         for n in range(64):
+            live = lib.lqrhip_debug_pool_live()     # device blocks handed out and not given back: the iteration leaves none behind
             c = _carver(eng, img)
             lib.lqrhip_debug_fail_alloc(n)
             ret, buf = c.energy_call(1, 1, nbytes=4 * w * h, guard=16)
@@ -203,6 +207,7 @@ def test_an_allocation_failure_at_every_point_of_a_read_out_leaves_a_usable_carv
             if ret == L.LQR_OK:
                 assert np.array_equal(bits(buf[:4 * w * h].view(np.float32).reshape(h, w)), bits(want))
                 c.destroy()
+                assert lib.lqrhip_debug_pool_live() == live, n
                 break
             assert ret == L.LQR_NOMEM, (n, ret)
             failures += 1
@@ -213,10 +218,12 @@ def test_an_allocation_failure_at_every_point_of_a_read_out_leaves_a_usable_carv
             assert np.array_equal(bits(c.get_energy(1)), bits(want)), n    # asked again: the exact result
             assert c.resize(w - 5, h) == 1 and np.array_equal(c.read_image_ext(), want_image), n
             c.destroy()
+            assert lib.lqrhip_debug_pool_live() == live, n
         else:
             raise AssertionError("the read-out never got through")
     finally:
         lib.lqrhip_debug_fail_alloc(-1)
+    print("allocation sweep energy-read-out: %d failure points" % failures)
     assert failures >= 4, failures          # the transposed planes, the working planes, the partials, the staging block
 
 

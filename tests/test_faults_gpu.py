@@ -12,6 +12,7 @@ Checked here: with recovery (the default) every injected fault ends in LQR_OK an
 (lqrhip_set_recovery(0)) in LQR_ERROR with the carver as it was before the failed session -- scan lines serve that image -- and
 the NEXT resize of the same carver and of a fresh one is bit-exact; two faults in a row end in LQR_ERROR likewise."""
 import ctypes
+import gc
 
 import numpy as np
 import pytest
@@ -32,6 +33,7 @@ def lib(engine):
         getattr(lb, f).argtypes = [ctypes.c_int]
     lb.lqrhip_get_no_spin.restype = ctypes.c_int
     lb.lqrhip_debug_fail_alloc.argtypes = [ctypes.c_int]
+    lb.lqrhip_debug_pool_live.restype, lb.lqrhip_debug_pool_live.argtypes = ctypes.c_ulonglong, []
     yield lb
     lb.lqrhip_debug_fail_alloc(-1)
     lb.lqrhip_debug_inject(0, 0, 0); lb.lqrhip_set_recovery(1); lb.lqrhip_set_no_spin(0); lb.lqrhip_set_selfcheck(1)
@@ -252,8 +254,10 @@ def test_an_allocation_failure_anywhere_in_a_resize_leaves_consistent_carvers(or
             co.destroy()
         return states[i][size]
     resize = lambda cs, size=(nw, nh): cs[0].resize(*size) if n_images == 1 else L.resize_batch(engine, cs, *size)
+    gc.collect()            # (a carver that an earlier, failed test left to the collector would go while the blocks are counted)
     failures, seen = 0, set()
     for n in range(0, 6000, stride):
+        live = lib.lqrhip_debug_pool_live()         # device blocks handed out and not given back: the iteration leaves none behind
         cs = [H.init_carver(engine, im, nw, nh, **kw)[0] for im in imgs]
         for ps in pre:
             assert resize(cs, ps) == L.LQR_OK
@@ -264,6 +268,7 @@ def test_an_allocation_failure_anywhere_in_a_resize_leaves_consistent_carvers(or
             for c, (fi, fv) in zip(cs, final):
                 assert np.array_equal(c.read_image(), fi) and np.array_equal(c.vmap_dump()["data"], fv), n
                 c.destroy()
+            assert lib.lqrhip_debug_pool_live() == live, n
             break
         assert ret == L.LQR_NOMEM, (n, ret)
         failures += 1
@@ -278,6 +283,7 @@ def test_an_allocation_failure_anywhere_in_a_resize_leaves_consistent_carvers(or
         for c, (fi, fv) in zip(cs, final):
             assert np.array_equal(c.read_image(), fi) and np.array_equal(c.vmap_dump()["data"], fv), n
             c.destroy()
+        assert lib.lqrhip_debug_pool_live() == live, n
     else:
         pytest.fail("the resize never got through")
     print("allocation sweep %s: %d failure points, states seen %s" % (case, failures, sorted(seen)))
