@@ -2,7 +2,7 @@
 // k_*.hip: device selection, the allocation cache, host <-> device transfers through a pinned ring, batches and their streams,
 // lqrhip_seam_step's per-seam launch sequence (which form of each stage it runs is lqr_plan.h's choice), read-out, reset from device memory,
 // the copy ceiling and the seam-map colour ramp.  Every block of the allocation cache has one owner, a DevBuf or a Scratch of lqr_own.h:
-// nothing here gives a block back by hand.  The three kernels that live here (k_poison_random, k_copy16, k_vmap_ramp)
+// nothing here gives a block back by hand.  The four kernels that live here (k_poison_random, k_copy16, k_reset_jobs, k_vmap_ramp)
 // are debugging / measuring / one-off aids next to their only callers.
 #include "lqr_common.h"
 #include "lqr_kernels.h"
@@ -62,6 +62,9 @@ struct __attribute__((visibility("hidden"))) LqrHipCarver {
     WorkingPlanes wk;
     int log_cap = 0, log_h = 0;      // the seam log's shape: seams x rows
     int frozen_epoch = 0;           // pix / bias are in the frame before seam `frozen_epoch` of the session
+    // What the session that ended owes the frozen planes (lqrhip_vs_commit): seams [frozen_epoch, owed_to) of its log, still alive, are
+    // to be removed from pix / bias, after which the frame is owed_w x owed_h.  Paid by pay_catchup, dropped by drop_catchup; 0: nothing
+    int owed_to = 0, owed_w = 0, owed_h = 0;
     LqrHipCarver *root = nullptr;
     std::vector<LqrHipCarver *> aux;
     LqrHipBatch *batch = nullptr;
@@ -135,6 +138,7 @@ struct PendingInflate { PlaneJobs pj; int kind = 0 /* 0 inflate, 1 flatten, 2 tr
 struct LqrHipBatch {
     std::vector<LqrHipCarver *> cs;
     DevCarver *d_desc = nullptr;
+    size_t desc_cap = 0;                    // descriptors d_desc holds (a parked block may be larger than the batch)
     hipStream_t stream = nullptr;
     DevBuf<unsigned long long> exch;        // k_dp_tile_p: halo granules per image and tile + finished-tile counters
     int exch_ntiles = 0, exch_n = 0, exch_px = 0;      // geometry the exchange area was last laid out for
@@ -659,10 +663,19 @@ extern "C" int lqrhip_carver_set_read(LqrHipCarver *c, int image_type, int alpha
     return (differs && (was || reads_value(c))) ? 1 : 0;
 }
 
+// the frozen planes are about to be laid out afresh, or are garbage: what the last session owed them is owed no more, and the log
+// restarts at 0
+static inline void drop_catchup(LqrHipCarver *c)
+{
+    c->owed_to = 0; c->owed_w = 0; c->owed_h = 0;
+    c->frozen_epoch = 0;
+}
+
 static void free_working(LqrHipCarver *c)
 {
     c->wk = WorkingPlanes();
     c->log_cap = 0; c->log_h = 0;
+    drop_catchup(c);
 }
 
 extern "C" void lqrhip_carver_destroy(LqrHipCarver *c)
@@ -905,6 +918,30 @@ extern "C" int lqrhip_sub_batches(int n)
 extern "C" void lqrhip_batch_set_shared(LqrHipBatch *b, int shared) { b->shared = shared != 0; b->shared_n = shared > 1 ? shared : 1; }
 extern "C" void lqrhip_batch_set_safe(LqrHipBatch *b, int safe) { b->safe = safe != 0; if (safe) g_fault_stats[6]++; }
 
+// A group is opened and closed around every resize (host/lqr_carver.c group_open / group_close), and creating a stream, a raw hipMalloc,
+// destroying the stream and a raw hipFree -- which waits for the device -- per sub-batch were part of every call.  A destroyed batch parks
+// its stream (idle: it has been synchronised) and its descriptor block here instead, and the next batch takes them: a parked stream is
+// reused before a new one is created, so the process holds no more streams than its largest group had.  Descriptor blocks stay outside
+// the counted allocator (they are no failure point of the allocation sweeps and lqrhip_debug_pool_live does not see them).
+// lqrhip_pool_trim gives both back.
+static const size_t MAX_PARKED = 4;                         // the most sub-batch streams a group runs on (plan_streams)
+static std::vector<hipStream_t> g_parked_streams;
+static unsigned long long g_fixed_stats[3];           // test hook (lqrhip_debug_fixedcost): [0] batch streams taken from the parked ones, [1] carvers reset by k_reset_jobs, [2] by the runtime's copy and fill
+static std::multimap<size_t, DevCarver *> g_parked_desc;    // by capacity in descriptors
+extern "C" void lqrhip_debug_fixedcost(unsigned long long out4[4], int reset)
+{
+    out4[0] = g_parked_streams.size();
+    for (int i = 0; i < 3; i++) out4[i + 1] = g_fixed_stats[i];
+    if (reset) memset(g_fixed_stats, 0, sizeof g_fixed_stats);
+}
+static void unpark_all(void)
+{
+    for (hipStream_t s : g_parked_streams) (void) hipStreamDestroy(s);
+    g_parked_streams.clear();
+    for (auto &kv : g_parked_desc) (void) hipFree(kv.second);
+    g_parked_desc.clear();
+}
+
 extern "C" LqrHipBatch *lqrhip_batch_create(LqrHipCarver **carvers, int n)
 {
     if (lqrhip_init() < 0 || n <= 0) return nullptr;
@@ -913,9 +950,17 @@ extern "C" LqrHipBatch *lqrhip_batch_create(LqrHipCarver **carvers, int n)
         b->cs.push_back(carvers[i]);
         carvers[i]->batch = b;
     }
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc((void **) &b->d_desc, sizeof(DevCarver) * n) != hipSuccess) {
+    hipError_t e = hipSuccess;
+    if (!g_parked_streams.empty()) { b->stream = g_parked_streams.back(); g_parked_streams.pop_back(); g_fixed_stats[0]++; }
+    else e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) {
+        auto it = g_parked_desc.lower_bound((size_t) n);        // the smallest parked block that holds n
+        if (it != g_parked_desc.end()) { b->d_desc = it->second; b->desc_cap = it->first; g_parked_desc.erase(it); }
+        else if ((e = hipMalloc((void **) &b->d_desc, sizeof(DevCarver) * n)) == hipSuccess) b->desc_cap = (size_t) n;
+    }
+    if (e != hipSuccess) {
         g_err = "batch_create failed";
+        (void) hipGetLastError();
         if (b->stream) (void) hipStreamDestroy(b->stream);
         for (auto *c : b->cs) if (c->batch == b) c->batch = nullptr;
         delete b;
@@ -946,9 +991,16 @@ extern "C" void lqrhip_batch_destroy(LqrHipBatch *b)
 {
     if (!b) return;
     g_live_batches.erase(std::remove(g_live_batches.begin(), g_live_batches.end(), b), g_live_batches.end());
-    if (b->stream) { (void) hipStreamSynchronize(b->stream); (void) hipStreamDestroy(b->stream); }
+    if (b->stream) (void) hipStreamSynchronize(b->stream);
     for (auto *c : b->cs) if (c->batch == b) c->batch = nullptr;
-    if (b->d_desc) (void) hipFree(b->d_desc);
+    if (b->stream) {
+        if (g_parked_streams.size() < MAX_PARKED) g_parked_streams.push_back(b->stream);
+        else (void) hipStreamDestroy(b->stream);
+    }
+    if (b->d_desc) {
+        if (g_parked_desc.size() < MAX_PARKED) g_parked_desc.emplace(b->desc_cap, b->d_desc);
+        else (void) hipFree(b->d_desc);
+    }
     delete b;
 }
 
@@ -1060,6 +1112,7 @@ extern "C" int lqrhip_prof_get_union(const char *kernel, double *ms_union)
     return 0;
 }
 
+static int pay_catchup(LqrHipBatch *b);
 extern "C" int lqrhip_wk_init(LqrHipBatch *b, int from_visible)
 {
     LqrHipCarver *c0 = b->cs[0];
@@ -1071,7 +1124,7 @@ extern "C" int lqrhip_wk_init(LqrHipBatch *b, int from_visible)
         if ((rc = ensure_working(c, w, h))) return rc;
     }
     if ((rc = batch_upload(b))) return rc;
-    for (auto *c : b->cs) c->frozen_epoch = 0;
+    for (auto *c : b->cs) drop_catchup(c);
     const dim3 grid((c0->stride + 255) / 256, h, (unsigned) b->cs.size()), grid_v(h, (unsigned) b->cs.size());
 #define LAUNCH_WK(FORM, arg) do { if (from_visible) hipLaunchKernelGGL(k_wk_init_visible<FORM>, grid_v, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, arg); \
                                   else hipLaunchKernelGGL(k_wk_init<FORM>, grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, arg); } while (0)
@@ -1088,6 +1141,7 @@ extern "C" int lqrhip_wk_init(LqrHipBatch *b, int from_visible)
 extern "C" int lqrhip_emap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h)
 {
     int rc;
+    if ((rc = pay_catchup(b))) return rc;           // the energy reads pix / bias in the carved frame
     if ((rc = batch_upload(b))) return rc;
     LqrHipCarver *c0 = b->cs[0];
     dim3 grid((w + 255) / 256, h, (unsigned) b->cs.size());
@@ -1329,6 +1383,42 @@ static int frozen_catchup(LqrHipBatch *b, int to, int w_at_to, int h)
     return 0;
 }
 
+// The catch-up a session's end owes (lqrhip_vs_commit) is paid here, by the same launch on the batch's stream, before anything reads
+// pix / bias in the carved frame (lqrhip_emap_build) and before the session's log is replaced (lqrhip_seam_log_reserve).  Whatever lays
+// the planes out afresh instead (a reload, a flatten, a transpose, lqrhip_wk_init) drops the debt: there the pass was 1.1 ms per
+// 16 images of 4K for nothing.
+static int pay_catchup(LqrHipBatch *b)
+{
+    LqrHipCarver *c0 = b->cs[0];
+    bool any = false, alike = true;
+    for (auto *c : b->cs) {
+        any |= c->owed_to > 0;
+        alike &= c->owed_to == c0->owed_to && c->owed_w == c0->owed_w && c->owed_h == c0->owed_h && c->frozen_epoch == c0->frozen_epoch && c->stride == c0->stride;
+    }
+    if (!any) return 0;
+    int rc;
+    if ((rc = batch_upload(b))) return rc;
+    if (alike) {
+        if ((rc = frozen_catchup(b, c0->owed_to, c0->owed_w, c0->owed_h))) return rc;
+    } else {
+        // carvers that ended their last sessions in different batches (alone: a lag of 32; in a group: of 128) owe different ranges, and
+        // the kernel takes one range per launch: one launch per owing carver, each through its own descriptor of the table
+        for (size_t i = 0; i < b->cs.size(); i++) {
+            LqrHipCarver *c = b->cs[i];
+            if (c->owed_to <= c->frozen_epoch) continue;
+            const int from = c->frozen_epoch, w_from = c->owed_w + (c->owed_to - from);
+            const size_t lds = (size_t) (c->owed_to - from) * sizeof(int) + (size_t) w_from + 16;
+            with_form(c, [&](auto value) {
+                hipLaunchKernelGGL(k_frozen_catchup<value>, dim3(c->owed_h, 1), dim3(256), lds, b->stream, b->d_desc + i, from, c->owed_to, w_from, c->owed_h, c->stride);
+            });
+            HIPCK(hipGetLastError());
+            drop_catchup(c);
+        }
+    }
+    for (auto *c : b->cs) drop_catchup(c);              // paid: the planes are in the carved frame, the log restarts at 0
+    return 0;
+}
+
 static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr, int P, bool rigm)
 {
     LqrHipCarver *c0 = b->cs[0];
@@ -1391,7 +1481,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
     int rc;
     LqrHipCarver *c0 = b->cs[0];
     for (auto *c : b->cs)
-        if (log_index >= c->log_cap) return LQRHIP_EARG;
+        if (log_index >= c->log_cap || c->owed_to) return LQRHIP_EARG;     // (a carver that owes a catch-up never meets the new session's log)
     if ((rc = batch_upload(b))) return rc;
     const unsigned n = (unsigned) b->cs.size();
     DpK k = make_dpk(p, c0->ch);
@@ -1512,6 +1602,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
 extern "C" int lqrhip_seam_log_reserve(LqrHipBatch *b, int n_seams, int h)
 {
     int rc;
+    if ((rc = pay_catchup(b))) return rc;           // (reads the log of the session before, which ensure_log may replace)
     for (auto *c : b->cs) if ((rc = ensure_log(c, n_seams, h))) return rc;
     return 0;
 }
@@ -1532,9 +1623,12 @@ extern "C" int lqrhip_vs_commit(LqrHipBatch *b, int w0, int h0, int wc0, int n_s
                        first_level, finish);
     HIPCK(hipGetLastError());
     inject_after_commit(b, w0, h0, first_level);
-    // the session is over: bring the frozen planes to the carved frame, the log restarts at 0
-    if ((rc = frozen_catchup(b, n_seams, wc0 - n_seams, h0))) return rc;
-    for (auto *c : b->cs) c->frozen_epoch = 0;
+    // the session is over: the frozen planes are owed the seams from frozen_epoch on, and the log stays alive and counts on until
+    // pay_catchup has brought them to the carved frame -- or until they are laid out afresh and the debt is dropped
+    for (auto *c : b->cs) {
+        if (c->frozen_epoch < n_seams) { c->owed_to = n_seams; c->owed_w = wc0 - n_seams; c->owed_h = h0; }
+        else drop_catchup(c);
+    }
     return 0;
 }
 
@@ -1572,7 +1666,7 @@ extern "C" int lqrhip_session_rollback(LqrHipBatch *b, int w0, int h0, int first
     hipLaunchKernelGGL(k_vs_rollback, dim3((unsigned) std::min<size_t>((n + 255) / 256, 4096), (unsigned) b->cs.size()), dim3(256), 0, b->stream, b->d_desc, n, first_level, finish ? w0 : 0);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(b->stream));
-    for (auto *c : b->cs) c->frozen_epoch = 0;
+    for (auto *c : b->cs) drop_catchup(c);
     g_fault_stats[4]++;
     return 0;
 }
@@ -1647,6 +1741,8 @@ extern "C" int lqrhip_planes_commit(LqrHipBatch *b)
     PlaneJobs &pj = pi->pj;
     commit(pj);
     for (auto &j : pj.jobs) { j.c->w0 = pi->w1; j.c->h0 = pi->h1; }
+    if (pi->kind != 0)                      // flat, or flat and transposed: the working planes are laid out afresh from here
+        for (auto *c : b->cs) drop_catchup(c);
     if (pi->kind != 2) {                    // (a transpose keeps the carvers' -- all zero -- visibility maps)
         size_t i = 0;
         for (auto *c : b->cs) c->vs = std::move(pj.new_vs[i++]);
@@ -1764,6 +1860,7 @@ extern "C" void lqrhip_pool_trim(void)
     for (auto &kv : g_pool_free) { (void) hipFree(kv.second); g_pool_size.erase(kv.second); }
     g_pool_free.clear();
     g_pool_cached = 0;
+    unpark_all();
 }
 
 extern "C" int lqrhip_device_sync(void)
@@ -1818,10 +1915,9 @@ extern "C" int lqrhip_read_working(LqrHipCarver *c, int w, int h, float *en, flo
 
 // ---- start over from a device-resident image ---------------------------------------------------
 __global__ __launch_bounds__(256) void k_copy16(const u32x4 *__restrict__ src, u32x4 *__restrict__ dst, size_t n16);
-extern "C" int lqrhip_carver_reset(LqrHipCarver *c, const void *device_rgb, int w, int h)
+// the host side of a reset, up to the fresh base planes: what lqrhip_carver_reset and lqrhip_carver_reset_batch do alike per carver
+static int reset_planes(LqrHipCarver *c, int w, int h)
 {
-    // roots without attached carvers only: an attached carver holds no visibility map of its own (vs_of)
-    if (!c || c->root || !c->aux.empty() || w < 1 || h < 1) return LQRHIP_EARG;
     int rc = batch_sync_of(c);
     if (rc) return rc;
     const size_t n = (size_t) w * h;
@@ -1829,8 +1925,17 @@ extern "C" int lqrhip_carver_reset(LqrHipCarver *c, const void *device_rgb, int 
     // a carver that had masks carries bias / rig working planes: the fresh carver has none
     if (c->wk.bias || c->wk.rig) { free_working(c); c->stride = 0; c->wk_h = 0; }
     c->w0 = w; c->h0 = h;
-    c->frozen_epoch = 0;
+    drop_catchup(c);                // (the working planes are laid out afresh from the new image: nothing is owed to them)
     if ((rc = c->rgb0.alloc(n * px_bytes(c), "&c->rgb0")) || (rc = c->vs.alloc(n, "&c->vs"))) return rc;
+    return 0;
+}
+extern "C" int lqrhip_carver_reset(LqrHipCarver *c, const void *device_rgb, int w, int h)
+{
+    // roots without attached carvers only: an attached carver holds no visibility map of its own (vs_of)
+    if (!c || c->root || !c->aux.empty() || w < 1 || h < 1) return LQRHIP_EARG;
+    int rc = reset_planes(c, w, h);
+    if (rc) return rc;
+    const size_t n = (size_t) w * h;
     // (round 6: these copies on four more streams side by side -- one 33 MB device-to-device copy runs at ~0.5 TB/s, 64 of them are 4 ms of a
     // 190-ms step -- made the 64-image step 45 % LONGER: with g_stream0 and the four sub-batch streams that is nine streams on the
     // process's eight hardware queues, and sub-batch streams that share a queue run one after the other.  One stream.)
@@ -1849,6 +1954,62 @@ extern "C" int lqrhip_carver_reset(LqrHipCarver *c, const void *device_rgb, int 
     HIPCK(hipMemsetAsync(c->vs, 0, n * sizeof(int32_t), g_stream0));
     if (c->batch) c->batch->dirty = true;
     if (c->active && (rc = ensure_working(c, w, h))) return rc;        // synchronises g_stream0 when it allocates
+    return 0;
+}
+
+// The same for a whole list, as the batch drivers reload (64 carvers per step): per carver the bookkeeping above, in the same order, and
+// then ONE launch per RESET_JOBS carvers that copies their images and clears their visibility maps -- 64 copy kernels and 64 fills one
+// after the other on the stream were ~4 ms of a 64 x 4K step for 6.4 GB, 1.6 TB/s.  The jobs travel in the kernel's arguments: nothing
+// is allocated for them.  An image that does not start on a 16-byte boundary goes the way lqrhip_carver_reset copies it.
+// On a failure the carvers before the failing one are reset completely (lqrhip_carver_reset_batch_count says how many), the failing
+// one is as lqrhip_carver_reset leaves it, the ones after it are untouched.
+enum { RESET_JOBS = 16 };
+struct ResetJob { const uint8_t *src; uint8_t *dst; uint8_t *vs; size_t bytes; };
+struct ResetJobs { ResetJob j[RESET_JOBS]; };
+__global__ __launch_bounds__(256) void k_reset_jobs(const ResetJobs jobs, const size_t vs_bytes);
+static int g_reset_batch_count = 0;
+extern "C" int lqrhip_carver_reset_batch_count(void) { return g_reset_batch_count; }
+extern "C" int lqrhip_carver_reset_batch(LqrHipCarver **cs, const void *const *device_rgb, int n, int w, int h)
+{
+    g_reset_batch_count = 0;
+    if (!cs || !device_rgb || n < 1 || w < 1 || h < 1) return LQRHIP_EARG;
+    for (int i = 0; i < n; i++)         // every argument before any carver is touched
+        if (!cs[i] || cs[i]->root || !cs[i]->aux.empty() || !device_rgb[i]) return LQRHIP_EARG;
+    const size_t npx = (size_t) w * h, vs_bytes = npx * sizeof(int32_t);
+    ResetJobs jobs = {};
+    int nj = 0;
+    size_t most = vs_bytes;             // the longest plane of the jobs collected
+    auto flush = [&]() -> int {
+        if (!nj) return 0;
+        const unsigned blocks = (unsigned) std::min<size_t>((most / 16 + 255) / 256 + 1, 4096);
+        hipLaunchKernelGGL(k_reset_jobs, dim3(blocks, (unsigned) nj), dim3(256), 0, g_stream0, jobs, vs_bytes);
+        nj = 0; most = vs_bytes;
+        HIPCK(hipGetLastError());
+        return 0;
+    };
+    for (int i = 0; i < n; i++) {
+        LqrHipCarver *c = cs[i];
+        g_reset_batch_count = i;
+        int rc = reset_planes(c, w, h);
+        if (rc) { (void) flush(); return rc; }
+        const size_t bytes = npx * px_bytes(c);
+        if (!(((uintptr_t) device_rgb[i] | (uintptr_t) c->rgb0.get() | (uintptr_t) c->vs.get()) & 15)) {
+            jobs.j[nj++] = ResetJob{(const uint8_t *) device_rgb[i], c->rgb0.get(), (uint8_t *) c->vs.get(), bytes};
+            most = std::max(most, bytes);
+            g_fixed_stats[1]++;
+        } else {
+            g_fixed_stats[2]++;
+            hipError_t e = hipMemcpyAsync(c->rgb0, device_rgb[i], bytes, hipMemcpyDeviceToDevice, g_stream0);
+            if (e == hipSuccess) e = hipMemsetAsync(c->vs, 0, vs_bytes, g_stream0);
+            if (e != hipSuccess) { (void) flush(); HIPCK(e); }
+        }
+        if (c->batch) c->batch->dirty = true;
+        if (c->active && (rc = ensure_working(c, w, h))) { (void) flush(); return rc; }       // synchronises g_stream0 when it allocates
+        if (nj == RESET_JOBS && (rc = flush())) return rc;
+    }
+    int rc = flush();
+    if (rc) return rc;
+    g_reset_batch_count = n;
     return 0;
 }
 
@@ -1877,6 +2038,23 @@ __global__ __launch_bounds__(256) void k_copy16(const u32x4 *__restrict__ src, u
 {
     const size_t i = (size_t) blockIdx.x * 256 + threadIdx.x;
     if (i < n16) __builtin_nontemporal_store(__builtin_nontemporal_load((const GLOBAL_AS u32x4 *) src + i), (GLOBAL_AS u32x4 *) dst + i);
+}
+
+// The reload of a list of carvers (lqrhip_carver_reset_batch): job blockIdx.y copies its image and clears its visibility map, 16 bytes
+// per access, the grid striding over the planes; src, dst and vs are 16-byte aligned.  The bytes past the last multiple of 16 are moved
+// one each by the grid's last threads.
+__global__ __launch_bounds__(256) void k_reset_jobs(const ResetJobs jobs, const size_t vs_bytes)
+{
+    const ResetJob j = jobs.j[blockIdx.y];
+    const size_t tid = (size_t) blockIdx.x * 256 + threadIdx.x, nthreads = (size_t) gridDim.x * 256;
+    const size_t n16 = j.bytes / 16, z16 = vs_bytes / 16;
+    for (size_t i = tid; i < n16; i += nthreads)
+        __builtin_nontemporal_store(__builtin_nontemporal_load((const GLOBAL_AS u32x4 *) j.src + i), (GLOBAL_AS u32x4 *) j.dst + i);
+    const u32x4 zero = {0u, 0u, 0u, 0u};
+    for (size_t i = tid; i < z16; i += nthreads) __builtin_nontemporal_store(zero, (GLOBAL_AS u32x4 *) j.vs + i);
+    const size_t back = nthreads - 1 - tid;         // 0 for the last thread of the grid row
+    if (back < (j.bytes & 15)) j.dst[n16 * 16 + back] = j.src[n16 * 16 + back];
+    if (back < (vs_bytes & 15)) j.vs[z16 * 16 + back] = 0;
 }
 
 extern "C" int lqrhip_copy_bandwidth(unsigned long long bytes, int iters, double *gbps)

@@ -15,6 +15,9 @@
  * and configuration advancing in lock-step (lqrx_carver_resize_batch); the
  * plug-in's single carver is a group of one.
  */
+#ifdef LQRHIP_TIMING
+#define _POSIX_C_SOURCE 199309L
+#endif
 #include <stdlib.h>
 #include <string.h>
 #include <stdio.h>
@@ -30,6 +33,29 @@
 
 #define MAXI(a, b) ((a) > (b) ? (a) : (b))
 #define MINI(a, b) ((a) < (b) ? (a) : (b))
+
+/* Host timers around the fixed part of a batched resize (-DLQRHIP_TIMING in CFLAGS; compiled out by default): wall time the calling
+ * thread spends in the reload, in group_open, in group_close and in a session's tail (self-check .. commit of the inflated planes),
+ * printed per part when the library is unloaded.  profiles/fixedcost/README.md */
+#ifdef LQRHIP_TIMING
+#include <time.h>
+enum { T_RELOAD, T_OPEN, T_CLOSE, T_TAIL, T_PARTS };
+static double g_t_sum[T_PARTS];
+static long g_t_calls[T_PARTS];
+static double t_now(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
+__attribute__((destructor)) static void t_report(void)
+{
+    static const char *const name[T_PARTS] = {"reload", "group_open", "group_close", "session_tail"};
+    int i;
+    for (i = 0; i < T_PARTS; i++)
+        if (g_t_calls[i]) fprintf(stderr, "LQRHIP_TIMING %s calls %ld total_ms %.3f mean_ms %.4f\n", name[i], g_t_calls[i], g_t_sum[i], g_t_sum[i] / g_t_calls[i]);
+}
+#define T_BEGIN(part) const double t_begin_##part = t_now()
+#define T_END(part) do { g_t_sum[part] += t_now() - t_begin_##part; g_t_calls[part]++; } while (0)
+#else
+#define T_BEGIN(part) do { } while (0)
+#define T_END(part) do { } while (0)
+#endif
 
 struct _LqrProgress {
     gfloat update_step;
@@ -776,12 +802,14 @@ static LqrRetVal group_build_vsmap(Group *g, int depth, int *reported)
 
     /* the seam loop is over: nothing of it is committed to the base layout before its kernels have all ended without a device-side
      * failure and the seam log has passed its self-check */
+    T_BEGIN(T_TAIL);
     HIP_ALL(g, lqrhip_session_check(B, r0->h, wc0, n_seams, r0->delta_x));
     HIP_ALL(g, lqrhip_batch_sync(B));
     HIP_ALL(g, lqrhip_vs_commit(B, r0->w0, r0->h0, wc0, n_seams, first_level, finish));
     /* inflate (E14): every seam of this session is doubled in the base layout */
     HIP_ALL(g, lqrhip_inflate(B, r0->w0, r0->h0, depth - 1, r0->max_level));        /* every sub-batch staged and checked ... */
     HIP_ALL(g, lqrhip_planes_commit(B));                                            /* ... before any adopts its inflated layout */
+    T_END(T_TAIL);
     w1 = r0->w0 + (depth - 1) - r0->max_level + 1;
     FOR_TREE(g, i, r, {
         r->level = depth; r->max_level = depth;
@@ -996,7 +1024,11 @@ static LqrRetVal group_resize(LqrCarver **rs, int n, int w1, int h1)
                     LQRHIP_MAX_FRAME_WIDTH);
             return LQR_ERROR;
         }
-    LQR_CATCH(group_open(&g, rs, n));
+    {
+        T_BEGIN(T_OPEN);
+        LQR_CATCH(group_open(&g, rs, n));
+        T_END(T_OPEN);
+    }
     if (rs[0]->resize_order == LQR_RES_ORDER_HOR) {
         if ((ret = group_resize_dir(&g, w1, 0)) == LQR_OK) ret = group_resize_dir(&g, h1, 1);
     } else {
@@ -1008,7 +1040,11 @@ static LqrRetVal group_resize(LqrCarver **rs, int n, int w1, int h1)
     }
     if (ret != LQR_OK) { int k; for (k = 0; k < g.nb; k++) lqrhip_batch_abort(g.b[k]); }      /* nothing of this resize may surface in the next one */
     FOR_TREE(&g, i, r, { r->ro_valid = 0; r->ro_line = 0; r->ro_x = 0; });
-    group_close(&g);
+    {
+        T_BEGIN(T_CLOSE);
+        group_close(&g);
+        T_END(T_CLOSE);
+    }
     return ret;
 }
 
@@ -1153,15 +1189,27 @@ LqrRetVal lqrx_vmap_to_rgba(LqrVMap *v, const gdouble col_start[3], const gdoubl
 /* ======================= reload from device memory ======================= */
 LqrRetVal lqrx_carver_reload_device_batch(LqrCarver **rs, gint n, void *const *device_rgb)
 {
-    int i, x;
+    int i, x, lo, rc = 0, done = 0;
+    LqrHipCarver **ds;
+    T_BEGIN(T_RELOAD);
     if (n < 1) return LQR_ERROR;
     for (i = 0; i < n; i++)
         if (!rs[i] || rs[i]->root || rs[i]->attached || !device_rgb[i]) return LQR_ERROR;
-    for (i = 0; i < n; i++) {
+    ds = (LqrHipCarver **) malloc((size_t) n * sizeof *ds);
+    if (!ds) return LQR_NOMEM;
+    for (i = 0; i < n; i++) ds[i] = rs[i]->dev;
+    /* the device side of the whole list: one call, and one copy launch per 16 images, for every run of carvers of one size */
+    for (lo = 0; lo < n && !rc; lo = i) {
+        for (i = lo + 1; i < n && rs[i]->img_w == rs[lo]->img_w && rs[i]->img_h == rs[lo]->img_h; i++);
+        rc = lqrhip_carver_reset_batch(ds + lo, (const void *const *) device_rgb + lo, i - lo, rs[lo]->img_w, rs[lo]->img_h);
+        done = rc ? lo + lqrhip_carver_reset_batch_count() : i;
+    }
+    free(ds);
+    /* ... and the host side of every carver the device side has reset (all of them, unless it failed) */
+    for (i = 0; i < done; i++) {
         LqrCarver *r = rs[i];
         LqrVMapList *v, *vn;
         lqr_maskq_reset(&r->mq[0]); lqr_maskq_reset(&r->mq[1]);        /* masks are dropped, queued ones too */
-        HIP_CATCH(lqrhip_carver_reset(r->dev, device_rgb[i], r->img_w, r->img_h));
         for (v = r->flushed_vs; v; v = vn) { vn = v->next; lqr_vmap_destroy(v->current); free(v); }
         r->flushed_vs = NULL;
         r->level = r->max_level = 1;
@@ -1176,7 +1224,9 @@ LqrRetVal lqrx_carver_reload_device_batch(LqrCarver **rs, gint n, void *const *d
             for (x = -r->delta_x; x <= r->delta_x; x++)
                 r->rigidity_map[x + r->delta_x] = r->rigidity * powf(fabsf((float) x), 1.5f) / r->h;
     }
+    HIP_CATCH(rc);
     HIP_CATCH(lqrhip_reset_sync());
+    T_END(T_RELOAD);
     return LQR_OK;
 }
 

@@ -85,7 +85,14 @@ void lqrhip_carver_destroy(LqrHipCarver *c);
  * the visibility map is cleared, masks are dropped; working planes are kept when the geometry is the
  * same.  For batch drivers that keep their inputs device-resident (bench.py). */
 int lqrhip_carver_reset(LqrHipCarver *c, const void *device_rgb, int w, int h);
-/* wait for the copies lqrhip_carver_reset enqueued */
+/* The same for n carvers of w x h at once: per carver what lqrhip_carver_reset does on the host, then one kernel launch per 16 carvers
+ * that copies their images and clears their visibility maps (an image that is not 16-byte aligned is copied as lqrhip_carver_reset
+ * copies it).  Every argument is checked before any carver is touched.  On a failure the carvers before the failing one are reset
+ * completely, the failing one is as lqrhip_carver_reset leaves it and those after it are untouched;
+ * lqrhip_carver_reset_batch_count() says how many the last call reset completely. */
+int lqrhip_carver_reset_batch(LqrHipCarver **cs, const void *const *device_rgb, int n, int w, int h);
+int lqrhip_carver_reset_batch_count(void);
+/* wait for the copies lqrhip_carver_reset / lqrhip_carver_reset_batch enqueued */
 int lqrhip_reset_sync(void);
 /* attached carver (render.c:897): shares the root's visibility map */
 int lqrhip_carver_attach(LqrHipCarver *root, LqrHipCarver *aux);
@@ -134,6 +141,8 @@ LqrHipBatch *lqrhip_batch_create(LqrHipCarver **carvers, int n);
  * must be co-resident are then never chosen (k_dp_tile_p spins on neighbour tiles) or sized so that ALL the siblings' grids
  * fit together (k_band_levels) */
 void lqrhip_batch_set_shared(LqrHipBatch *b, int shared);
+/* waits for the batch's stream; the stream (idle now) and the descriptor block are parked for the next lqrhip_batch_create, up to
+ * four of each; lqrhip_pool_trim gives the parked ones back */
 void lqrhip_batch_destroy(LqrHipBatch *b);
 int lqrhip_batch_sync(LqrHipBatch *b);
 /* after a failed call on the batch: drain its stream, discard the device-side error record of the failed call, and have
@@ -169,7 +178,10 @@ int lqrhip_seam_log_reserve(LqrHipBatch *b, int n_seams, int h);
 /* E8 update_vsmap for a whole session at once: turn the session's seam log
  * (n_seams seams, carved frame wc0 wide at session start) into visibility
  * levels first_level, first_level+1, ... in the base layout; `finish` applies
- * liblqr's finish_vsmap (last column gets level w0). */
+ * liblqr's finish_vsmap (last column gets level w0).  The working planes pix / bias stay behind the carved frame by the seams the
+ * session has not compacted yet: that catch-up is owed per carver (the session's log is kept for it) and is paid on the batch's
+ * stream at the top of the next lqrhip_emap_build or lqrhip_seam_log_reserve, or dropped where the planes are laid out afresh
+ * (lqrhip_wk_init, lqrhip_carver_reset, lqrhip_session_rollback, lqrhip_planes_commit of a flatten or a transpose). */
 int lqrhip_vs_commit(LqrHipBatch *b, int w0, int h0, int wc0, int n_seams, int first_level, int finish);
 /* Session self-check, enqueued behind the last seam step and in front of lqrhip_vs_commit: the seam log of the session (n_seams
  * seams of h rows, carved frame wc0 wide at its start) must hold delta_x-connected seams inside their frames; a violation is
@@ -201,6 +213,9 @@ void lqrhip_debug_fail_alloc(int nth);
 /* Test hook: device blocks of the allocation cache handed out and not yet given back.  A call that fails, and a carver or batch that
  * is destroyed, leave the count where it was before. */
 unsigned long long lqrhip_debug_pool_live(void);
+/* Test hook: [0] batch streams parked now, and since the last reset [1] batch streams taken from the parked ones instead of created,
+ * [2] carvers lqrhip_carver_reset_batch reset through k_reset_jobs, [3] through the runtime's copy and fill (unaligned images). */
+void lqrhip_debug_fixedcost(unsigned long long out4[4], int reset);
 /* The three passes that replace a batch's base planes run in TWO PHASES: the call stages the new planes and runs the pass -- nothing of
  * the carvers changes -- and lqrhip_planes_commit adopts what was staged.  A group commits only after every one of its sub-batches has
  * passed phase one, so that a failed self-check (LQRHIP_EFAULT) or a failed allocation (LQRHIP_ENOMEM) in one sub-batch leaves the
