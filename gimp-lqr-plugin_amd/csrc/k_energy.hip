@@ -78,6 +78,95 @@ __global__ void k_emap_full(const DevCarver *cs, DpK p, int w, int h, int stride
     c.en[(size_t) y * stride + x] = e;
 }
 
+// E1 + E3/E4 in one pass, for the start of a session on a FLAT carver of packed pixels (lqrhip_wk_init_emap): k_wk_init<PixPacked>
+// and k_emap_full<NRG, false> back to back wrote the packed plane and read it straight back (4 bytes per pixel each way), and
+// k_emap_full formed the brightness of every pixel once per neighbour that asks for it (2 to 4 times).  Here a thread lays out 4
+// columns of row y and computes their energies from the base layout's pixels, which are the packed plane's values: px_bright on
+// the same u32 through the same table, grad_energy_f on the same samples -- the energies are k_emap_full's bit for bit.  The
+// brightnesses a thread needs (row y: its 4 columns and one either side; rows y - 1, y + 1: its 4 columns, not for the XABS
+// energies) are formed once each and held in registers; the sample reader handed to grad_energy_f picks among them by
+// compile-time-unrolled selects, not by indexing (no scratch).
+// The planes are laid out afresh: the origin is 0, the view the physical one.
+template <int NRG>
+__global__ __launch_bounds__(256) void k_wk_init_emap(const DevCarver *cs, DpK p, int w, int h, int stride)
+{
+    PixRead<false> rd;
+    rd.setup(threadIdx.x, 256);                     // (a barrier inside: before any thread leaves)
+    const GCarver c = gview_phys(cs[blockIdx.z]);
+    const int x = (blockIdx.x * 256 + threadIdx.x) * 4, y = blockIdx.y, ch = p.ch;
+    if (x == 0 && y == 0) { c.flags[FLAG_ORG] = 0; c.flags[FLAG_ORG_PREV] = 0; c.flags[FLAG_SIDE] = 0; }
+    if (x >= stride) return;
+    constexpr bool luma = (NRG >= 3), rows3 = (NRG % 3 != 2) && NRG != 6;
+    const size_t o = (size_t) y * stride + x, i0 = (size_t) y * w + x;
+    // whole 16-byte vectors where RGBA rows start on 16-byte boundaries in the base layout (width a multiple of 4) and in the working
+    // planes (the stride is a multiple of 64): a vector is then wholly inside the row or wholly past it; else column by column
+    const bool vst = (stride & 3) == 0 && (((size_t) c.pix | (size_t) c.en) & 15) == 0;        // 16-byte stores of the working planes
+    const bool vec = ch == 4 && (w & 3) == 0 && ((size_t) c.rgb0 & 15) == 0;                   // 16-byte loads of the base layout
+    auto load4 = [&](int yy, uint32_t *q) {         // pixels x .. x + 3 of row yy (0 past the frame)
+        if (vec) {
+            u32x4 v = {0u, 0u, 0u, 0u};
+            if (x < w) v = *(const GLOBAL_AS u32x4 *) (c.rgb0 + ((size_t) yy * w + x) * 4);
+            q[0] = v.x; q[1] = v.y; q[2] = v.z; q[3] = v.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) q[k] = x + k < w ? PixPacked::form(c.rgb0, (size_t) yy * w + x + k, ch) : 0u;
+        }
+    };
+    uint32_t own[4];
+    load4(y, own);
+    float bv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (vst) *(GLOBAL_AS u32x4 *) (c.pix + o) = u32x4{own[0], own[1], own[2], own[3]};     // (columns past the frame: 0, as k_wk_init leaves them)
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (x + k >= stride) break;
+        if (!vst) c.pix[o + k] = own[k];
+        if (c.bias0 && x + k < w) bv[k] = c.bias0[i0 + k];
+        if (c.bias) c.bias[o + k] = bv[k];
+        if (c.rig) c.rig[o + k] = (c.rig0 && x + k < w) ? c.rig0[i0 + k] : 0.0f;
+    }
+    if (x >= w) return;                             // the energies: inside the frame only, as k_emap_full
+    auto bright = [&](uint32_t q) { return px_bright(q, ch, luma, Norm255Lut{rd.n255}); };
+    double bm[6], bu[4] = {0.0, 0.0, 0.0, 0.0}, bd[4] = {0.0, 0.0, 0.0, 0.0};      // row y: columns x - 1 .. x + 4; rows y - 1, y + 1: x .. x + 3
+    bm[0] = (NRG != 6 && x > 0) ? bright(PixPacked::form(c.rgb0, i0 - 1, ch)) : 0.0;
+    bm[5] = (NRG != 6 && x + 4 < w) ? bright(PixPacked::form(c.rgb0, i0 + 4, ch)) : 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) bm[k + 1] = NRG != 6 ? bright(own[k]) : 0.0;
+    if (rows3) {
+        uint32_t q[4];
+        if (y > 0) {
+            load4(y - 1, q);
+#pragma unroll
+            for (int k = 0; k < 4; k++) bu[k] = bright(q[k]);
+        }
+        if (y < h - 1) {
+            load4(y + 1, q);
+#pragma unroll
+            for (int k = 0; k < 4; k++) bd[k] = bright(q[k]);
+        }
+    }
+    const bool ven = vst && x + 3 < w;             // the energies of a quad that ends past the frame go one by one: nothing is written past it
+    float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (x + k >= w) break;
+        e[k] = grad_energy_f<NRG>([&](int xx, int yy) {
+            const int dx = xx - x, dy = yy - y;
+            double r = 0.0;
+            if (dy == 0) {
+#pragma unroll
+                for (int j = 0; j < 6; j++) r = (dx + 1 == j) ? bm[j] : r;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; j++) r = (dx == j) ? (dy < 0 ? bu[j] : bd[j]) : r;
+            }
+            return r;
+        }, x + k, y, w, h);
+        if (c.bias) e[k] = __fadd_rn(e[k], __fdiv_rn(bv[k], (float) p.w_start));
+        if (!ven) c.en[o + k] = e[k];
+    }
+    if (ven) *(GLOBAL_AS f32x4 *) (c.en + o) = f32x4{e[0], e[1], e[2], e[3]};
+}
+
 // E2: mask value = mean(colour)/255 * alpha/255 (help/en/index.wiki:48)
 __global__ void k_mask_add(float *plane, int w0, const uint8_t *mask, int channels, int mw, int x0, int y0, int x1, int y1,
                            int nx, int ny, int transposed, int is_rig, int bias_factor)
@@ -218,5 +307,8 @@ INST_WK(PixPacked) INST_WK(PixValue<0>) INST_WK(PixValue<1>) INST_WK(PixValue<2>
 K_EMAP_FORMS(INST)
 #undef INST
 #undef INST_U
+#define INST_WE(N) template __global__ void k_wk_init_emap<N>(const DevCarver *, DpK, int, int, int);
+K_WK_INIT_EMAP_FORMS(INST_WE)
+#undef INST_WE
 template __global__ void k_frozen_catchup<false>(const DevCarver *, int, int, int, int, int);
 template __global__ void k_frozen_catchup<true>(const DevCarver *, int, int, int, int, int);

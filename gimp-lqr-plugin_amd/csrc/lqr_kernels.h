@@ -18,6 +18,8 @@ template <class FORM> __global__ __launch_bounds__(256) void k_wk_init_visible(c
 #define K_EMAP_FORMS(X) X(0, false) X(1, false) X(2, false) X(3, false) X(4, false) X(5, false) X(6, false) X(0, true) X(1, true) X(2, true) X(6, true)
 #define K_EMAP_UPDATE_NT_FORMS(X, ...) X(12, __VA_ARGS__) X(36, __VA_ARGS__) X(68, __VA_ARGS__)      // brightness samples per row (eu_samples in lqr_plan.h)
 template <int NRG, bool VALUE> __global__ void k_emap_full(const DevCarver *cs, DpK p, int w, int h, int stride);
+#define K_WK_INIT_EMAP_FORMS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6)     // LqrEnergyFuncBuiltinType; packed pixels only
+template <int NRG> __global__ __launch_bounds__(256) void k_wk_init_emap(const DevCarver *cs, DpK p, int w, int h, int stride);
 __global__ void k_mask_add(float *plane, int w0, const uint8_t *mask, int channels, int mw, int x0, int y0, int x1, int y1,
                            int nx, int ny, int transposed, int is_rig, int bias_factor);
 template <int NRG, int EU_NT, bool VALUE> __global__ __launch_bounds__(64) void k_emap_update(const DevCarver *cs, DpK p, int w, int h, int stride, int k, int epoch);

@@ -195,14 +195,27 @@ static inline bool levels_auto(const PlanKnobs &k, int delta, size_t group, bool
     return k.update_mode < 0 && delta <= 4 && group >= 8 && (group <= 64 || !plain);
 }
 // Slots (workgroups) per image for k_band_levels on a frame w x h (0: not usable here): as many as the group's images leave room for
-// within the residency bound, at most LV_PMAX; lqrhip_set_band_levels pins it.  Automatic: 12 slots while the group's workgroups stay
-// below ~384 (beyond that the sibling kernels are starved of registers, NOTES/rounds-1-5.md 4.15 / 4.16: 48 images with 10 slots 452 k,
-// with 8 slots 479 k), never fewer than LV_AUTO_MIN
+// within the residency bound, at most LV_PMAX; lqrhip_set_band_levels pins it.  Automatic, never fewer than LV_AUTO_MIN and never
+// more than 12:
+//   * a batch whose group is spread over sibling streams (b.shared): while the group's workgroups stay below ~384 (beyond that the
+//     sibling kernels are starved of registers, NOTES/rounds-1-5.md 4.15 / 4.16: 48 images with 10 slots 452 k, with 8 slots 479 k);
+//   * a batch that has its stream to itself -- what a process with fewer than 8 hardware queues runs, plan_streams -- has no
+//     sibling: the carve runs after the levels, not beside them.  Its bound is two workgroups per compute unit (2 * n_cu, 512 on an
+//     MI355X).  That figure is read off the measurements below; the explanation that goes with it -- a workgroup is two waves, so
+//     up to there every wave can have a SIMD to itself -- is a supposition about where the dispatcher puts them, not something
+//     observed.  Measured on one stream (profiles/onestream/README.md; ms per step of 64 / 48 x 4K, 200 seams, two rounds,
+//     slots per image 7 / 8 / 9 / 10 / 12):
+//         64 images (448 .. 768 workgroups)  214.9 214.6 / 210.9 211.0 / 216.2 216.2 / 217.1 216.8 / 217.8 217.9
+//         48 images (336 .. 576 workgroups)  179.4 179.6 / 175.5 175.7 / 173.0 173.2 / 173.2 173.2 / 182.2 181.9
+//     512 and 480 workgroups are the best or equal to it, 576 loses 3 % both times.  So 64 images get 8 slots (they had 7: -3.7 ms,
+//     1.7 %) and 48 get 10 (they had 8: -2.4 ms, 1.4 %).  Only 48 and 64 images were run: every other group size of 33 .. 63 gets
+//     its slots by extrapolation over the workgroup count (33 .. 42 images: 12 slots, they had 11 .. 9; 43 .. 46: 11; 47 .. 51: 10;
+//     52 .. 56: 9; 57 .. 63: 8).  Groups up to 32 get 12 slots under either bound, as before
 static inline int plan_levels_P(const PlanKnobs &k, const PlanDevice &d, const PlanBatch &b, int w, int h, int delta)
 {
     if (!b.spin || k.band_levels == 0 || delta < 1 || delta > LQR_FAST_MAX_DELTA || tiles_of(h, lv_rows(delta, true)) > LV_MAX_LEVELS || tiles_of(w, 64) > LV_MAX_TILES) return 0;
     const int per_batch = plan_limit(k, d.wgs_levels) / std::max(b.shared_n, 1);
-    const int want = k.band_levels > 0 ? k.band_levels : std::max(LV_AUTO_MIN, std::min(12, (int) (384 / std::max<size_t>(b.group(), 1))));
+    const int want = k.band_levels > 0 ? k.band_levels : std::max(LV_AUTO_MIN, std::min(12, (int) ((b.shared ? 384 : 2 * d.n_cu) / std::max<size_t>(b.group(), 1))));
     const int P = std::min({LV_PMAX, per_batch / std::max(b.images, 1), want});
     return P >= (k.band_levels > 0 ? 1 : LV_AUTO_MIN) ? P : 0;
 }

@@ -1113,7 +1113,9 @@ extern "C" int lqrhip_prof_get_union(const char *kernel, double *ms_union)
 }
 
 static int pay_catchup(LqrHipBatch *b);
-extern "C" int lqrhip_wk_init(LqrHipBatch *b, int from_visible)
+// what comes before the launch that lays the working planes of a batch out: carvers of one shape and pixel kind, their planes
+// allocated, the descriptors on the device, no catch-up owed to planes that are about to be overwritten
+static int wk_init_prepare(LqrHipBatch *b)
 {
     LqrHipCarver *c0 = b->cs[0];
     int w = c0->w0, h = c0->h0, rc;
@@ -1125,6 +1127,13 @@ extern "C" int lqrhip_wk_init(LqrHipBatch *b, int from_visible)
     }
     if ((rc = batch_upload(b))) return rc;
     for (auto *c : b->cs) drop_catchup(c);
+    return 0;
+}
+extern "C" int lqrhip_wk_init(LqrHipBatch *b, int from_visible)
+{
+    LqrHipCarver *c0 = b->cs[0];
+    int w = c0->w0, h = c0->h0, rc;
+    if ((rc = wk_init_prepare(b))) return rc;
     const dim3 grid((c0->stride + 255) / 256, h, (unsigned) b->cs.size()), grid_v(h, (unsigned) b->cs.size());
 #define LAUNCH_WK(FORM, arg) do { if (from_visible) hipLaunchKernelGGL(k_wk_init_visible<FORM>, grid_v, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, arg); \
                                   else hipLaunchKernelGGL(k_wk_init<FORM>, grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, arg); } while (0)
@@ -1150,6 +1159,25 @@ extern "C" int lqrhip_emap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w,
     const int nrg = plane_nrg(value, nrg_index(p->nrg_func));
 #define CASE(N, V) if (nrg == N && value == V) hipLaunchKernelGGL((k_emap_full<N, V>), grid, dim3(256), 0, b->stream, b->d_desc, k, w, h, c0->stride); else
     K_EMAP_FORMS(CASE) return no_form("k_emap_full");
+#undef CASE
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+// lqrhip_wk_init(b, 0) and lqrhip_emap_build(b, p, w, h) of a session that starts on flat carvers.  Packed pixels in the frame the
+// planes are laid out in: ONE pass (k_wk_init_emap) -- the packed plane is written and not read back, a pixel's brightness is
+// formed once (64 x 4K: 1.36 + 2.29 ms -> 1.58 ms, profiles/onestream/README.md).  Value planes, another frame: the two launches.
+extern "C" int lqrhip_wk_init_emap(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h)
+{
+    LqrHipCarver *c0 = b->cs[0];
+    int rc;
+    if (reads_value(c0) || w != c0->w0 || h != c0->h0) return (rc = lqrhip_wk_init(b, 0)) ? rc : lqrhip_emap_build(b, p, w, h);
+    if ((rc = wk_init_prepare(b))) return rc;
+    const dim3 grid((tiles_of(c0->stride, 4) + 255) / 256, h, (unsigned) b->cs.size());
+    DpK k = make_dpk(p, c0->ch);
+    const int nrg = nrg_index(p->nrg_func);
+#define CASE(N) if (nrg == N) hipLaunchKernelGGL(k_wk_init_emap<N>, grid, dim3(256), 0, b->stream, b->d_desc, k, w, h, c0->stride); else
+    K_WK_INIT_EMAP_FORMS(CASE) return no_form("k_wk_init_emap");
 #undef CASE
     HIPCK(hipGetLastError());
     return 0;

@@ -826,15 +826,17 @@ static LqrRetVal session_run(Group *g, int depth, int redo, int *reported)
     LqrHipDpParams p;
     int i;
     for (i = 0; i < g->n; i++) set_width_one(g->r[i], g->r[i]->w_start - g->r[i]->max_level + 1);    /* the carved frame */
-    if (!r0->wk_valid || redo) {
-        /* a flat carver: identity; a multi-size image (a redone deeper session, working planes lost in a failed one): the
-         * pixels of the base layout without a level, in order */
-        const int from_visible = (r0->max_level != 1 || r0->w0 != r0->w_start);
-        HIP_ALL(g, lqrhip_wk_init(B, from_visible));
-        for (i = 0; i < g->n; i++) g->r[i]->wk_valid = 1;
-    }
     dp_params(r0, &p);
-    HIP_ALL(g, lqrhip_emap_build(B, &p, r0->w, r0->h));
+    if (!r0->wk_valid || redo) {
+        /* a flat carver: identity, and the energy in the same pass over the planes; a multi-size image (a redone deeper session,
+         * working planes lost in a failed one): the pixels of the base layout without a level, in order */
+        const int from_visible = (r0->max_level != 1 || r0->w0 != r0->w_start);
+        if (from_visible) HIP_ALL(g, lqrhip_wk_init(B, 1));
+        else HIP_ALL(g, lqrhip_wk_init_emap(B, &p, r0->w, r0->h));
+        for (i = 0; i < g->n; i++) g->r[i]->wk_valid = 1;
+        if (from_visible) HIP_ALL(g, lqrhip_emap_build(B, &p, r0->w, r0->h));
+    } else
+        HIP_ALL(g, lqrhip_emap_build(B, &p, r0->w, r0->h));
     HIP_ALL(g, lqrhip_mmap_build(B, &p, r0->w, r0->h, r0->leftright));
     return group_build_vsmap(g, depth, reported);
 }

@@ -156,6 +156,10 @@ void *lqrhip_batch_stream(LqrHipBatch *b);      /* hipStream_t, for event timing
 int lqrhip_wk_init(LqrHipBatch *b, int from_visible);
 /* E3+E4 lqr_carver_build_emap: full energy map of the w x h carved frame */
 int lqrhip_emap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h);
+/* lqrhip_wk_init(b, 0) followed by lqrhip_emap_build(b, p, w, h), as a session starts on flat carvers: one pass over the planes
+ * where the pixels are packed 8-bit ones and w x h is the frame they are laid out in, the two passes otherwise.  Same planes,
+ * same energies, the same allocations in the same order */
+int lqrhip_wk_init_emap(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h);
 /* The output stage of the energy read-outs (lqr_energy.h), enqueued behind lqrhip_emap_build on the stream of a batch of ONE carver: the
  * w x h energy plane of the carver's frame goes out in IMAGE orientation (`transposed`: the frame is the transpose of it), as
  * form 0 the values as they are (floats), form 1 squashed and normalised to [0, 1] (floats), form 2 the normalised values as pixels of
