@@ -15,6 +15,8 @@
 //   lqr_shim.hip     the lqrhip_* C ABI of include/lqr_hip.h: allocation cache, batches, the per-seam launch sequence
 //   lqr_plan.h       which form of each stage that sequence runs (plain C++17, no HIP: also compiled alone by tests/test_plan.py)
 //   lqr_own.h        who owns a device block: DevBuf, Scratch (plain C++17, no HIP: also compiled alone by tests/test_own.py)
+//   lqr_pool.h       the allocation cache those blocks come from: BlockCache (plain C++17, no HIP: also compiled alone by tests/test_pool.py)
+//   lqr_stage.h      the ring of pinned buffers and helper threads every image is copied through: StageRing (likewise, tests/test_stage.py)
 // lqr_kernels.h declares every kernel for the shim; each kernel file instantiates the templates the shim launches.
 // lqr_pixel.h (k_energy.hip, k_oneoff.hip): the packed 8-bit and the value / deep form of a pixel as compile-time policies, so that
 // every kernel that touches pixels exists once and serves 8-bit grey / RGB carvers and those of any other depth, type or channel count
@@ -50,11 +52,6 @@
 #include <vector>
 #include <algorithm>
 #include <map>
-#include <deque>
-#include <thread>
-#include <mutex>
-#include <condition_variable>
-#include <dirent.h>
 #include <unistd.h>
 
 #include "../../include/lqr_hip.h"

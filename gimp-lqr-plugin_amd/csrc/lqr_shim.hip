@@ -1,5 +1,6 @@
 // lqr_shim.hip -- the host side: the lqrhip_* C ABI of include/lqr_hip.h (plain pointers and sizes) on top of the kernels of
-// k_*.hip: device selection, the allocation cache, host <-> device transfers through a pinned ring, batches and their streams,
+// k_*.hip: device selection, the allocation cache (its rules are lqr_pool.h's, over hipMalloc / hipFree), host <-> device transfers
+// through a pinned ring (lqr_stage.h, over this file's stream), batches and their streams,
 // lqrhip_seam_step's per-seam launch sequence (which form of each stage it runs is lqr_plan.h's choice), read-out, reset from device memory,
 // the copy ceiling and the seam-map colour ramp.  Every block of the allocation cache has one owner, a DevBuf or a Scratch of lqr_own.h:
 // nothing here gives a block back by hand.  The four kernels that live here (k_poison_random, k_copy16, k_reset_jobs, k_vmap_ramp)
@@ -7,7 +8,10 @@
 #include "lqr_common.h"
 #include "lqr_kernels.h"
 #include "lqr_own.h"
+#include "lqr_pool.h"
+#include "lqr_stage.h"
 #include <memory>
+#include <dirent.h>
 
 static thread_local std::string g_err;
 static int g_device = -1;
@@ -297,15 +301,10 @@ extern "C" int lqrhip_fault_stats(unsigned long long *out8, int reset)
     return 0;
 }
 
-// Device allocations go through a small size-class cache: the carve path allocates and frees
-// image-sized planes for every inflate / flatten / read-out, and hipMalloc / hipFree (which
-// synchronises the device) would otherwise cost more than the kernels between them.  A block is
-// only returned to the cache after the stream that used it has been synchronised.
-static std::multimap<size_t, void *> g_pool_free;
-static std::map<void *, size_t> g_pool_size;
-static size_t g_pool_cached = 0;
-static const size_t POOL_MAX_CACHED = (size_t) 24 << 30;
-
+// Device allocations go through a small size-class cache, the BlockCache of lqr_pool.h (g_cache below): the shim supplies hipMalloc,
+// hipFree and the hook that prepares a block handed out, pool_poison.  A block is only returned to the cache after the stream that
+// used it has been synchronised.
+//
 // LQRHIP_POISON=<byte> in the environment (debugging aid, scripts/fuzz_parity.py): every block handed out is first filled
 // with that byte and the device synchronised, so that a kernel that reads memory nothing wrote yet fails the same way every
 // time instead of depending on what the block held before
@@ -323,10 +322,9 @@ __global__ void k_poison_random(unsigned *p, size_t n, int mode, int stride, int
         p[i] = mode == 1 ? __float_as_uint((float) (hsh >> 8) * (100.0f / 16777216.0f)) : mode == 2 ? (hsh >> 21) : hsh;
     }
 }
-static const char *g_alloc_name = "";      // what the allocation under way is for (LQRHIP_POISON_LOG)
 static int g_poison = -2;
 static unsigned g_poison32 = 0;
-static int pool_poison(void *p, size_t sz)
+static int pool_poison(void *p, size_t sz, const char *name)     // name: what the allocation is for (LQRHIP_POISON_LOG)
 {
     if (g_poison == -2) {
         const char *e = getenv("LQRHIP_POISON");
@@ -345,7 +343,7 @@ static int pool_poison(void *p, size_t sz)
             if (r) sscanf(r, "%ld:%ld", &lo, &hi);
         }
         const long me = seq++;
-        if (logit) fprintf(stderr, "alloc %ld %zu %s\n", me, sz, g_alloc_name);
+        if (logit) fprintf(stderr, "alloc %ld %zu %s\n", me, sz, name);
         if (hi >= 0 && (me < lo || me >= hi)) { HIPCK(hipMemset(p, 0, sz)); HIPCK(hipDeviceSynchronize()); return 0; }
     }
     if (g_poison > 256) {
@@ -360,49 +358,21 @@ static int pool_poison(void *p, size_t sz)
     return 0;
 }
 
+static int raw_alloc(void **p, size_t bytes, std::string &why)
+{
+    hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) return 0;
+    why = std::string("e: ") + hipGetErrorString(e);
+    (void) hipGetLastError();
+    return e == hipErrorOutOfMemory ? LQRHIP_ENOMEM : LQRHIP_EHIP;
+}
+static void raw_free(void *p) { (void) hipFree(p); }
+static BlockCache g_cache((size_t) 24 << 30, LQRHIP_ENOMEM, raw_alloc, raw_free, pool_poison);
 // fault injection (tests/test_faults_gpu.py): the nth device allocation from now on fails with "out of memory", once (-1: disarmed)
-static long g_fail_alloc_in = -1;
-extern "C" void lqrhip_debug_fail_alloc(int nth) { g_fail_alloc_in = nth; }
-static int lqr_pool_alloc(void **p, size_t bytes, const char *name)
-{
-    *p = nullptr;
-    g_alloc_name = name;
-    const size_t sz = (bytes + ((size_t) 1 << 20) - 1) & ~(((size_t) 1 << 20) - 1);      // 1 MiB classes
-    if (g_fail_alloc_in >= 0 && g_fail_alloc_in-- == 0) { g_err = std::string("injected allocation failure (") + (g_alloc_name ? g_alloc_name : "?") + ")"; return LQRHIP_ENOMEM; }
-    auto it = g_pool_free.find(sz);
-    if (it != g_pool_free.end()) {
-        *p = it->second;
-        g_pool_free.erase(it);
-        g_pool_cached -= sz;
-    } else {
-        hipError_t e = hipMalloc(p, sz);
-        if (e == hipErrorOutOfMemory && !g_pool_free.empty()) {       // give the cache back and retry once
-            (void) hipGetLastError();
-            for (auto &kv : g_pool_free) { (void) hipFree(kv.second); g_pool_size.erase(kv.second); }
-            g_pool_free.clear();
-            g_pool_cached = 0;
-            e = hipMalloc(p, sz);
-        }
-        HIPCK(e);
-        g_pool_size[*p] = sz;
-    }
-    const int rc = pool_poison(*p, sz);
-    if (rc) { lqr_pool_free(*p); *p = nullptr; }      // a failed allocation hands nothing out
-    return rc;
-}
-static void lqr_pool_free(void *p)
-{
-    auto it = g_pool_size.find(p);
-    if (it == g_pool_size.end()) { (void) hipFree(p); return; }
-    if (g_pool_cached + it->second > POOL_MAX_CACHED) {
-        (void) hipFree(p);
-        g_pool_size.erase(it);
-        return;
-    }
-    g_pool_free.emplace(it->second, p);
-    g_pool_cached += it->second;
-}
-extern "C" unsigned long long lqrhip_debug_pool_live(void) { return g_pool_size.size() - g_pool_free.size(); }
+extern "C" void lqrhip_debug_fail_alloc(int nth) { g_cache.fail_in(nth); }
+static int lqr_pool_alloc(void **p, size_t bytes, const char *name) { return g_cache.alloc(p, bytes, name, g_err); }
+static void lqr_pool_free(void *p) { g_cache.free(p); }
+extern "C" unsigned long long lqrhip_debug_pool_live(void) { return g_cache.live(); }
 
 static void lqr_stream_wait(void *stream) { (void) hipStreamSynchronize((hipStream_t) stream); }
 
@@ -414,169 +384,48 @@ static hipError_t dzero(void *p, size_t bytes)
     return e != hipSuccess ? e : hipStreamSynchronize(g_stream0);
 }
 
-// Host <-> device copies of whole images.  The plug-in hands over and takes back PAGEABLE memory (a g_malloc'ed buffer at
-// lqr_carver_new, render.c:222; the scan-line buffer at read-out, io_functions.c:155-164); hipMemcpy on pageable memory
-// runs at ~1-2 GB/s here (it pins and unpins as it goes).  These go through a ring of pinned bounce buffers instead, and
-// the CPU side of the bounce -- memcpy between the caller's pageable buffer and the ring, page faults of a freshly
-// allocated destination included -- is done by a few helper threads in parallel while the DMA engine moves other chunks
-// (round 3: one thread, two 8 MB buffers: 8.6 GB/s up, 4.2 GB/s down; a single core's memcpy and its page faults were
-// the limit, not PCIe).  The helpers touch host memory only; every HIP call stays on the caller's thread.
-// Both functions return with the transfer complete, also on error (the stream is drained before they return).
-static const size_t STAGE_BYTES = (size_t) 4 << 20;
+// Host <-> device copies of whole images go through a ring of pinned bounce buffers that helper threads fill and empty, the StageRing of
+// lqr_stage.h; its device operations are these, on g_stream0.  Both functions return with the transfer complete, also on error.
 static const int STAGE_SLOTS = 16;
-static uint8_t *g_stage[STAGE_SLOTS];
-static hipEvent_t g_stage_ev[STAGE_SLOTS];
-static bool g_stage_ready = false;
-
-struct CopyPool {
-    struct Job { void *dst; const void *src; size_t n; };
-    std::vector<std::thread> th;
-    std::mutex mu;
-    std::condition_variable cv_job, cv_done;
-    std::deque<std::pair<int, Job>> q;      // (ticket, job)
-    std::vector<char> done;                 // per ticket of the current transfer
-    size_t pending = 0;                     // submitted and not finished
-    bool stop = false;
-    void start(int n)
+namespace {
+struct Stream0Stage final : StageDevice {
+    hipEvent_t ev[STAGE_SLOTS] = {};
+    int slot_create(int slot, size_t bytes, void **host) override
     {
-        for (int i = 0; i < n; i++) th.emplace_back([this] { run(); });
-    }
-    void run()
-    {
-        for (;;) {
-            std::pair<int, Job> j;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv_job.wait(lk, [this] { return stop || !q.empty(); });
-                if (stop && q.empty()) return;
-                j = q.front(); q.pop_front();
-            }
-            memcpy(j.second.dst, j.second.src, j.second.n);
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                done[j.first] = 1;
-                pending--;
-            }
-            cv_done.notify_all();
-        }
-    }
-    void begin(size_t tickets) { std::lock_guard<std::mutex> lk(mu); done.assign(tickets, 0); }
-    void submit(int ticket, void *dst, const void *src, size_t n)
-    {
-        { std::lock_guard<std::mutex> lk(mu); q.emplace_back(ticket, Job{dst, src, n}); pending++; }
-        cv_job.notify_one();
-    }
-    void drain()
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        cv_done.wait(lk, [this] { return pending == 0; });
-    }
-    void wait(int ticket)
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        cv_done.wait(lk, [&] { return done[ticket] != 0; });
-    }
-    ~CopyPool()
-    {
-        { std::lock_guard<std::mutex> lk(mu); stop = true; }
-        cv_job.notify_all();
-        for (auto &t : th) t.join();
-    }
-};
-static CopyPool *g_copy_pool = nullptr;
-
-static int stage_init(void)
-{
-    if (g_stage_ready) return 0;
-    // all or nothing: a partial set of buffers / events is released again, so a later call starts over
-    int made = 0;
-    hipError_t e = hipSuccess;
-    for (; made < STAGE_SLOTS; made++) {
-        g_stage[made] = nullptr; g_stage_ev[made] = nullptr;
-        if ((e = hipHostMalloc((void **) &g_stage[made], STAGE_BYTES, hipHostMallocDefault)) != hipSuccess) break;
-        if ((e = hipEventCreateWithFlags(&g_stage_ev[made], hipEventDisableTiming)) != hipSuccess) { (void) hipHostFree(g_stage[made]); break; }
-    }
-    if (made < STAGE_SLOTS) {
-        for (int i = 0; i < made; i++) { (void) hipHostFree(g_stage[i]); (void) hipEventDestroy(g_stage_ev[i]); g_stage[i] = nullptr; }
+        hipError_t e = hipHostMalloc(host, bytes, hipHostMallocDefault);
+        if (e == hipSuccess && (e = hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming)) != hipSuccess) (void) hipHostFree(*host);
+        if (e == hipSuccess) return 0;
         g_err = std::string("staging buffers: ") + hipGetErrorString(e);
         (void) hipGetLastError();
         return e == hipErrorOutOfMemory ? LQRHIP_ENOMEM : LQRHIP_EHIP;
     }
-    if (!g_copy_pool) {
-        unsigned hw = std::thread::hardware_concurrency();
-        g_copy_pool = new CopyPool();
-        g_copy_pool->start(hw >= 16 ? 8 : hw >= 4 ? (int) hw / 2 : 1);
+    void slot_destroy(int slot, void *host) override { (void) hipHostFree(host); (void) hipEventDestroy(ev[slot]); }
+    int copy_up(void *dst, const void *src, size_t n) override { HIPCK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, g_stream0)); return 0; }
+    int copy_down(void *dst, const void *src, size_t n) override { HIPCK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, g_stream0)); return 0; }
+    int record(int slot) override { HIPCK(hipEventRecord(ev[slot], g_stream0)); return 0; }
+    int wait(int slot) override { HIPCK(hipEventSynchronize(ev[slot])); return 0; }
+    bool landed(int slot) override { return hipEventQuery(ev[slot]) == hipSuccess; }
+    int wait_stream(bool quiet) override
+    {
+        hipError_t e = hipStreamSynchronize(g_stream0);
+        if (e == hipSuccess) return 0;
+        if (!quiet) g_err = std::string("upload: ") + hipGetErrorString(e);
+        return LQRHIP_EHIP;
     }
-    g_stage_ready = true;
-    return 0;
-}
-static int h2d_staged(void *dst, const void *src, size_t bytes)
+};
+}  // namespace
+// created at the first transfer; it lives to the end of the process
+static StageRing &stage_ring(void)
 {
-    int rc = stage_init();
-    if (rc) return rc;
-    const size_t nchunk = (bytes + STAGE_BYTES - 1) / STAGE_BYTES;
-    CopyPool &cp = *g_copy_pool;
-    cp.begin(nchunk);
-    auto body = [&]() -> int {
-        size_t submitted = 0;
-        for (size_t i = 0; i < nchunk; i++) {
-            // keep the helpers a ring ahead: chunk j goes into slot j % STAGE_SLOTS once the DMA that last read it is done
-            for (; submitted < nchunk && submitted < i + STAGE_SLOTS; submitted++) {
-                const int slot = (int) (submitted % STAGE_SLOTS);
-                HIPCK(hipEventSynchronize(g_stage_ev[slot]));
-                const size_t off = submitted * STAGE_BYTES;
-                cp.submit((int) submitted, g_stage[slot], (const uint8_t *) src + off, std::min(STAGE_BYTES, bytes - off));
-            }
-            const int slot = (int) (i % STAGE_SLOTS);
-            const size_t off = i * STAGE_BYTES;
-            cp.wait((int) i);
-            HIPCK(hipMemcpyAsync((uint8_t *) dst + off, g_stage[slot], std::min(STAGE_BYTES, bytes - off), hipMemcpyHostToDevice, g_stream0));
-            HIPCK(hipEventRecord(g_stage_ev[slot], g_stream0));
-        }
-        return 0;
-    };
-    rc = body();
-    cp.drain();         // whatever happened, nobody touches the caller's buffer or the ring after we return
-    hipError_t e = hipStreamSynchronize(g_stream0);
-    if (!rc && e != hipSuccess) { g_err = std::string("upload: ") + hipGetErrorString(e); rc = LQRHIP_EHIP; }
-    return rc;
+    static Stream0Stage dev;
+    static StageRing *ring = [] {
+        const unsigned hw = std::thread::hardware_concurrency();
+        return new StageRing(dev, STAGE_SLOTS, (size_t) 4 << 20, hw >= 16 ? 8 : hw >= 4 ? (int) hw / 2 : 1);
+    }();
+    return *ring;
 }
-static int d2h_staged(void *dst, const void *src, size_t bytes)
-{
-    int rc = stage_init();
-    if (rc) return rc;
-    const size_t nchunk = (bytes + STAGE_BYTES - 1) / STAGE_BYTES;
-    CopyPool &cp = *g_copy_pool;
-    cp.begin(nchunk);
-    size_t copied_out = 0;      // chunks handed to the helpers
-    auto hand_over = [&](size_t j) -> int {
-        const int slot = (int) (j % STAGE_SLOTS);
-        const size_t off = j * STAGE_BYTES;
-        HIPCK(hipEventSynchronize(g_stage_ev[slot]));
-        cp.submit((int) j, (uint8_t *) dst + off, g_stage[slot], std::min(STAGE_BYTES, bytes - off));
-        return 0;
-    };
-    auto body = [&]() -> int {
-        for (size_t i = 0; i < nchunk; i++) {
-            if (i >= (size_t) STAGE_SLOTS) {              // slot reuse: the helper must have emptied it
-                for (; copied_out <= i - STAGE_SLOTS; copied_out++) { int r = hand_over(copied_out); if (r) return r; }
-                cp.wait((int) (i - STAGE_SLOTS));
-            }
-            const int slot = (int) (i % STAGE_SLOTS);
-            const size_t off = i * STAGE_BYTES;
-            HIPCK(hipMemcpyAsync(g_stage[slot], (const uint8_t *) src + off, std::min(STAGE_BYTES, bytes - off), hipMemcpyDeviceToHost, g_stream0));
-            HIPCK(hipEventRecord(g_stage_ev[slot], g_stream0));
-            // hand over whatever has landed already, without waiting for it
-            while (copied_out < i && hipEventQuery(g_stage_ev[copied_out % STAGE_SLOTS]) == hipSuccess) { int r = hand_over(copied_out); if (r) return r; copied_out++; }
-        }
-        for (; copied_out < nchunk; copied_out++) { int r = hand_over(copied_out); if (r) return r; }
-        return 0;
-    };
-    rc = body();
-    cp.drain();         // the helpers are done with the caller's buffer
-    if (rc) (void) hipStreamSynchronize(g_stream0);
-    return rc;
-}
+static int h2d_staged(void *dst, const void *src, size_t bytes) { return stage_ring().upload(dst, src, bytes); }
+static int d2h_staged(void *dst, const void *src, size_t bytes) { return stage_ring().download(dst, src, bytes); }
 
 // A carver reads through the value plane (`pix` holds one double per pixel, the value the energy reads; lqr_pixel.h) unless it is
 // 8-bit grey / RGB with or without alpha in liblqr's default layout: those keep their pixels packed in `pix` and every kernel they had.
@@ -1885,9 +1734,7 @@ extern "C" int lqrhip_mask_line_max(const unsigned char *mask, int channels, int
 extern "C" void lqrhip_pool_trim(void)
 {
     (void) hipDeviceSynchronize();
-    for (auto &kv : g_pool_free) { (void) hipFree(kv.second); g_pool_size.erase(kv.second); }
-    g_pool_free.clear();
-    g_pool_cached = 0;
+    g_cache.trim();
     unpark_all();
 }
 
@@ -2055,7 +1902,7 @@ extern "C" int lqrhip_mem_info(unsigned long long *free_bytes, unsigned long lon
     HIPCK(hipMemGetInfo(&f, &t));
     if (free_bytes) *free_bytes = f;
     if (total_bytes) *total_bytes = t;
-    if (cached_bytes) *cached_bytes = g_pool_cached;
+    if (cached_bytes) *cached_bytes = g_cache.cached_bytes();
     return 0;
 }
 
