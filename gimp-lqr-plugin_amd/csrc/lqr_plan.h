@@ -249,7 +249,7 @@ static inline StepPlan plan_seam_step(const PlanKnobs &k, const PlanDevice &d, c
         s.backtrack = LQRHIP_CENSUS_VP_PARALLEL;
         s.vp_rows = vp_chunk_rows(delta);
         s.vp_chunks = tiles_of(h - 1, s.vp_rows);
-    } else s.backtrack = delta <= 7 ? LQRHIP_CENSUS_VPATH1 : LQRHIP_CENSUS_VPATH;      // (the one-wave walk is unrolled for delta_x 1 .. 7)
+    } else s.backtrack = delta >= 1 && delta <= 7 ? LQRHIP_CENSUS_VPATH1 : LQRHIP_CENSUS_VPATH;      // (the one-wave walk is unrolled for delta_x 1 .. 7; delta_x 0 walks with k_vpath's loop)
     // Single images and small groups: the carve and the energy update in one launch (k_carve_e, k_carve.hip) -- the wave that has moved
     // a row refreshes that row's energies; one dependent launch less per seam.  delta_x <= 2 (12 brightness samples per row);
     // value-plane carvers: the two kernels

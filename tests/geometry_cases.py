@@ -186,7 +186,7 @@ def census(case):
         full_dp(s["fw"], h)
         for wb, wnew, full in seam_steps(case, s):
             use_vp = 1 <= delta <= LQR_FAST_MAX_DELTA and h >= 2 and vmode != 0 and (vmode == 1 or delta >= 5 or (n <= VPATH_PAR_MAX and h >= VPATH_MIN_ROWS))
-            c[VP_PARALLEL if use_vp else VPATH1 if delta <= 7 else VPATH] += 1          # plan_seam_step: backtrack
+            c[VP_PARALLEL if use_vp else VPATH1 if 1 <= delta <= 7 else VPATH] += 1     # plan_seam_step: backtrack
             c[CARVE_E if (delta <= 2 and n <= FROZEN_CARVE_FUSED and wnew > 1) else CARVE] += 1      # the carve
             if wnew <= 1:
                 continue
