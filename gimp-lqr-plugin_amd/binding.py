@@ -221,6 +221,40 @@ def bind_energy(api):
     return api
 
 
+# include/lqr_vmap.h: liblqr's way to take a seam map back (lqr_vmap_new, lqr_vmap_load, lqr_vmap_internal_dump) and the engine's forms
+# for a map in device memory and for one map shared by a batch
+VMAP_SYMBOLS = {
+    "lqr_vmap_new": (_P, [_P, _I, _I, _I, _I]),
+    "lqr_vmap_load": (_I, [_P, _P]),
+    "lqr_vmap_internal_dump": (_I, [_P]),
+    "lqrx_vmap_load_device": (_I, [_P, _P, _I, _I, _I, _I]),
+    "lqrx_vmap_load_batch": (_I, [C.POINTER(_P), _I, _P]),
+}
+
+
+def bind_vmap(api):
+    """add VMAP_SYMBOLS to a bound Api; a genuine liblqr-1 has none of the lqrx_ ones"""
+    if not getattr(api, "has_vmap", False):
+        for name, (res, args) in VMAP_SYMBOLS.items():
+            if name.startswith("lqrx_") and not api.has_ext:
+                continue
+            fn = getattr(api.lib, api.prefix + name)      # AttributeError = missing export
+            fn.restype, fn.argtypes = res, args
+            setattr(api, name, fn)
+        api.has_vmap = True
+    return api
+
+
+def _vmap_new(api, m):
+    """a LqrVMap around a malloc'd copy of m["data"] (h x w int32, image orientation), which the map owns"""
+    data = np.ascontiguousarray(m["data"], dtype=np.int32)
+    assert data.ndim == 2
+    v = bind_vmap(api).lqr_vmap_new(_malloc_copy(data.view(np.uint8)), data.shape[1], data.shape[0], int(m["depth"]), int(m["orientation"]))
+    if not v:
+        raise MemoryError("lqr_vmap_new returned NULL")
+    return v
+
+
 class Api:
     """Resolved function table of one library exporting the ABI."""
 
@@ -259,6 +293,11 @@ def engine_masks_api():
 def engine_energy_api():
     """the engine with the colour-depth and energy read-out surfaces bound"""
     return bind_energy(engine_api())
+
+
+def engine_vmap_api():
+    """the engine with the colour-depth and seam-map loading surfaces bound"""
+    return bind_vmap(bind_coldepth(engine_api()))
 
 
 def engine_coldepth_api():
@@ -682,6 +721,24 @@ class Carver:
         self.api.lqr_vmap_destroy(v)
         return d
 
+    # -- loading a seam map (include/lqr_vmap.h); each returns the call's LqrRetVal
+    def vmap_load(self, m):
+        """lqr_vmap_load of the dict vmap_dump returns (data: h x w int32 in image orientation, depth, orientation)"""
+        a = bind_vmap(self.api)
+        v = _vmap_new(a, m)
+        ret = a.lqr_vmap_load(self.p, v)
+        a.lqr_vmap_destroy(v)
+        return ret
+
+    def vmap_load_device(self, tensor, depth, orientation):
+        """lqrx_vmap_load_device: a contiguous h x w int32 torch tensor on the device, read where it lies"""
+        assert tensor.is_cuda and tensor.is_contiguous() and tensor.dim() == 2 and tensor.dtype == torch.int32
+        torch.cuda.current_stream().synchronize()          # the engine reads the buffer on a stream of its own
+        return bind_vmap(self.api).lqrx_vmap_load_device(self.p, tensor.data_ptr(), tensor.shape[1], tensor.shape[0], int(depth), int(orientation))
+
+    def vmap_internal_dump(self):
+        return bind_vmap(self.api).lqr_vmap_internal_dump(self.p)
+
     def dumped_vmaps(self):
         """write_all_vmaps, io_functions.c:292-314: foreach over the carver's list"""
         out = []
@@ -745,6 +802,16 @@ def reload_device_batch(api, carvers, device_ptrs):
     arr = (C.c_void_p * len(carvers))(*[c.p for c in carvers])
     ptrs = (C.c_void_p * len(carvers))(*[int(p) for p in device_ptrs])
     return api.lqrx_carver_reload_device_batch(arr, len(carvers), ptrs)
+
+
+def vmap_load_batch(carvers, m):
+    """lqrx_vmap_load_batch: one map (the dict vmap_dump returns) into every carver of the list; the LqrRetVal"""
+    a = bind_vmap(carvers[0].api)
+    arr = (C.c_void_p * len(carvers))(*[c.p for c in carvers])
+    v = _vmap_new(a, m)
+    ret = a.lqrx_vmap_load_batch(arr, len(carvers), v)
+    a.lqr_vmap_destroy(v)
+    return ret
 
 
 def resize_batch(api, carvers, w1, h1):

@@ -99,6 +99,72 @@ __global__ __launch_bounds__(256) void k_inflate(const InflateDev *jobs, int w0,
     if (dev_err && (twice || (tid == 0 && carry != n_levels))) dev_fail(dev_err, DEVERR_LEVELS);
 }
 
+// lqr_vmap_load (include/lqr_vmap.h): a caller's seam map is checked before a carver adopts it.  Every value must lie in [0, depth] and
+// every level 1 .. depth occur exactly once in every line of the carver's frame -- what k_inflate's level arithmetic and the compaction
+// of every later read-out rest on.  The census is k_inflate's: a bit per level in LDS (at most 16383 levels, 2 KB) and a count per line.
+// A map that fails goes to the error word as DEVERR_VMAP, a code the host reads as "bad argument", not as a device fault.
+// Orientation 0: one workgroup per row of the map, which is a line of the frame; nothing is written (the map is read where it lies).
+__global__ __launch_bounds__(256) void k_vmap_check(const int32_t *map, int len, int depth, int *dev_err)
+{
+    extern __shared__ unsigned s_seen[];          // [(depth + 31) / 32]
+    __shared__ int s_cnt;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < (depth + 31) / 32; i += 256) s_seen[i] = 0u;
+    if (tid == 0) s_cnt = 0;
+    __syncthreads();
+    const int32_t *row = map + (size_t) blockIdx.x * len;
+    bool bad = false;
+    int cnt = 0;
+    for (int x = tid; x < len; x += 256) {
+        const int v = row[x];
+        if (v < 0 || v > depth) bad = true;
+        else if (v) { bad |= (atomicOr(&s_seen[(v - 1) >> 5], 1u << ((v - 1) & 31)) >> ((v - 1) & 31)) & 1u; cnt++; }
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+    if ((tid & 63) == 0) atomicAdd(&s_cnt, cnt);
+    __syncthreads();
+    if (bad || (tid == 0 && s_cnt != depth)) dev_fail(dev_err, DEVERR_VMAP);
+}
+
+// Orientation 1: the map lies height x width in image orientation and a line of the frame is a COLUMN of it.  Columns are not
+// gathered: one workgroup takes VT_LINES neighbouring columns (= lines of the frame) and walks down the rows in tiles of VT_LINES x 32
+// values through a padded LDS tile, as k_transpose does for pixels -- the reads run along the map's rows, the writes along the lines of
+// the transposed plane `out` (width x height, the carver's frame), both coalesced -- with the census of its lines taken on the way.
+__global__ __launch_bounds__(256) void k_vmap_check_t(const int32_t *map, int32_t *out, int width, int height, int depth, int *dev_err)
+{
+    extern __shared__ unsigned s_seen[];          // [VT_LINES][words]
+    __shared__ int32_t tile[VT_LINES][33];
+    __shared__ int s_cnt[VT_LINES];
+    const int tid = threadIdx.x, words = (depth + 31) / 32;
+    const int col0 = blockIdx.x * VT_LINES;
+    for (int i = tid; i < VT_LINES * words; i += 256) s_seen[i] = 0u;
+    if (tid < VT_LINES) s_cnt[tid] = 0;
+    bool bad = false;
+    for (int row0 = 0; row0 < height; row0 += 32) {
+        __syncthreads();
+        for (int i = tid; i < VT_LINES * 32; i += 256) {
+            const int r = i / VT_LINES, c = i % VT_LINES;          // consecutive lanes: consecutive columns of one row of the map
+            if (row0 + r < height && col0 + c < width) tile[c][r] = map[(size_t) (row0 + r) * width + col0 + c];
+        }
+        __syncthreads();
+        for (int i = tid; i < VT_LINES * 32; i += 256) {
+            const int c = i / 32, r = i % 32;                      // consecutive lanes: consecutive values of one line of the frame
+            if (row0 + r < height && col0 + c < width) {
+                const int v = tile[c][r];
+                out[(size_t) (col0 + c) * height + row0 + r] = v;
+                if (v < 0 || v > depth) bad = true;
+                else if (v) {
+                    bad |= (atomicOr(&s_seen[c * words + ((v - 1) >> 5)], 1u << ((v - 1) & 31)) >> ((v - 1) & 31)) & 1u;
+                    atomicAdd(&s_cnt[c], 1);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < VT_LINES && col0 + tid < width && s_cnt[tid] != depth) bad = true;
+    if (bad) dev_fail(dev_err, DEVERR_VMAP);
+}
+
 // Session self-check before the levels are committed (round 6): the session's seam log must describe seams -- entry k of
 // every row inside the frame that seam was found in (0 <= x < wc0 - k), and delta_x-connected from row to row.  Anything
 // else means a kernel of the seam loop misbehaved; the host rolls the session back and redoes it on the non-spinning kernels.

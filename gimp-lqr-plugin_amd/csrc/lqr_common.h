@@ -9,7 +9,7 @@
 //   k_band.hip       E5/E9           k_dp_sweep, k_band_update, k_band_update_mw, k_band_update_tw (one workgroup per image)
 //   k_tiles.hip      E5/E9           k_dp_tile, k_dp_tile_p (an image spread over several compute units)
 //   k_levels.hip     E9              k_band_levels (the band on several compute units, tiles assigned level by level)
-//   k_oneoff.hip     E8(vs)/E11/E12/E14, auto-size  k_vs_commit, k_inflate, k_compact(_jobs), k_transpose(_px), k_mask_line_max
+//   k_oneoff.hip     E8(vs)/E11/E12/E14, auto-size  k_vs_commit, k_inflate, k_vmap_check(_t), k_compact(_jobs), k_transpose(_px), k_mask_line_max
 //   k_masks.hip      E2 (lqr_masks.h) k_mask_add_f (float / double masks, host or device), k_mask_scatter (queued _xy calls), k_plane_transpose
 //   k_energy_out.hip energy read-outs (lqr_energy.h) k_energy_range (squash, min / max per workgroup), k_energy_out (normalise, expand to pixels, image orientation)
 //   lqr_shim.hip     the lqrhip_* C ABI of include/lqr_hip.h: allocation cache, batches, the per-seam launch sequence
@@ -190,6 +190,7 @@ struct DpK {
 #define DEVERR_BAND_PREDICTION 2
 #define DEVERR_SEAMLOG 3            // k_seam_check: the session's seam log does not describe seams
 #define DEVERR_LEVELS 4             // k_inflate: a level of the session missing or twice in a row of the base layout
+#define DEVERR_VMAP 5               // k_vmap_check(_t): a caller's seam map is not one (lqr_vmap_load).  NOT a fault: the shim reads it as a bad argument
 __device__ __forceinline__ void dev_fail(int *flag, int code)
 {
     __hip_atomic_store(flag, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

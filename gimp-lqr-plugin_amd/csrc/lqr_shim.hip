@@ -1586,7 +1586,8 @@ struct Staging {
     int kept() { keep = true; return 0; }
 };
 }  // namespace
-extern "C" int lqrhip_inflate(LqrHipBatch *b, int w0, int h0, int l, int max_level)
+// phase one of the inflate pass; `levels`: the plane every job reads its levels from (lqrhip_vmap_load), null: each root's own
+static int inflate_stage(LqrHipBatch *b, int w0, int h0, int l, int max_level, const int32_t *levels)
 {
     int rc;
     const int w1 = w0 + l - max_level + 1;
@@ -1596,9 +1597,10 @@ extern "C" int lqrhip_inflate(LqrHipBatch *b, int w0, int h0, int l, int max_lev
         pj.new_vs.emplace_back();
         DevBuf<int32_t> &nvs = pj.new_vs.back();
         if ((rc = nvs.alloc((size_t) w1 * h0, "&nvs"))) return rc;
+        const int32_t *vs = levels ? levels : c->vs.get();
         for (auto *a : c->aux)
-            if ((rc = pj.add(a, c->vs, nullptr, (size_t) w1 * h0))) return rc;
-        if ((rc = pj.add(c, c->vs, nvs, (size_t) w1 * h0))) return rc;
+            if ((rc = pj.add(a, vs, nullptr, (size_t) w1 * h0))) return rc;
+        if ((rc = pj.add(c, vs, nvs, (size_t) w1 * h0))) return rc;
     }
     if ((rc = pj.stage(b->stream, false))) return rc;
     const size_t lds = (size_t) ((l - max_level + 1 + 31) / 32 + 1) * sizeof(unsigned);      // one bit per level of the session (the fused self-check)
@@ -1610,6 +1612,71 @@ extern "C" int lqrhip_inflate(LqrHipBatch *b, int w0, int h0, int l, int max_lev
     HIPCK(hipStreamSynchronize(b->stream));
     if ((rc = check_dev_error())) return rc;            // a failed level check: nothing is adopted, the host rolls the session back
     return st.kept();
+}
+extern "C" int lqrhip_inflate(LqrHipBatch *b, int w0, int h0, int l, int max_level) { return inflate_stage(b, w0, h0, l, max_level, nullptr); }
+
+// ---- lqr_vmap_load (include/lqr_vmap.h): a caller's seam map becomes the visibility map of flat carvers ------------------------------
+// The map is brought to the device once (a host map through the pinned ring; a device map is read where it lies), checked by ONE pass
+// of k_vmap_check / k_vmap_check_t -- which for an orientation-1 map also writes the plane in the carver's frame -- and only then do
+// batches stage their inflate pass on it: every job of every batch reads its levels from that ONE plane (InflateDev.vs), nothing is
+// copied per carver.  A map that fails the check is LQRHIP_EMAP: the error word is cleared here, no batch is invalidated, nothing is
+// counted in lqrhip_fault_stats and nothing sticks (the non-spinning mode, the recovery).
+struct __attribute__((visibility("hidden"))) LqrHipVMap {
+    DevBuf<int32_t> own;            // the checked plane where it is the shim's (a host map; an orientation-1 map, transposed)
+    const int32_t *plane = nullptr; // lines x len in the carver's frame: `own`, or the caller's device memory (orientation 0)
+    int len = 0, lines = 0, depth = 0;
+};
+extern "C" int lqrhip_vmap_stage(const int *map, int on_device, int width, int height, int depth, int orientation, LqrHipVMap **out)
+{
+    *out = nullptr;
+    if (lqrhip_init() < 0) return LQRHIP_EHIP;
+    const int len = orientation ? height : width, lines = orientation ? width : height;
+    if (!map || width < 1 || height < 1 || (orientation != 0 && orientation != 1) || depth < 1 || depth >= len || depth >= LQRHIP_MAX_FRAME_WIDTH) {
+        g_err = "vmap: depth, size or orientation out of range";
+        return LQRHIP_EARG;
+    }
+    int rc;
+    const size_t n = (size_t) width * height;
+    std::unique_ptr<LqrHipVMap> m(new LqrHipVMap());
+    m->len = len; m->lines = lines; m->depth = depth;
+    Scratch tmp(g_stream0);
+    const int32_t *src = (const int32_t *) map;
+    if (!on_device) {
+        int32_t *d = orientation ? tmp.get<int32_t>(n, "&vmap_raw", rc) : ((rc = m->own.alloc(n, "&vmap")) ? nullptr : m->own.get());
+        if (rc) return rc;
+        if ((rc = h2d_staged(d, map, n * sizeof(int32_t)))) return rc;
+        src = d;
+    }
+    const size_t words = (size_t) (depth + 31) / 32;
+    if (orientation) {
+        if ((rc = m->own.alloc(n, "&vmap_t"))) return rc;
+        const size_t lds = VT_LINES * words * sizeof(unsigned);
+        if (lds > 56 * 1024) HIPCK(hipFuncSetAttribute((const void *) k_vmap_check_t, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+        hipLaunchKernelGGL(k_vmap_check_t, dim3((width + VT_LINES - 1) / VT_LINES), dim3(256), lds, g_stream0, src, m->own.get(), width, height, depth, g_dev_err);
+        m->plane = m->own;
+    } else {
+        hipLaunchKernelGGL(k_vmap_check, dim3(height), dim3(256), words * sizeof(unsigned), g_stream0, src, width, depth, g_dev_err);
+        m->plane = src;
+    }
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(g_stream0));
+    tmp.done();
+    if (g_dev_err_host && *g_dev_err_host == DEVERR_VMAP) {
+        *g_dev_err_host = 0;
+        g_err = "vmap: a value outside [0, depth], or a level that is missing or occurs twice in a line";
+        return LQRHIP_EMAP;
+    }
+    if ((rc = check_dev_error())) return rc;
+    *out = m.release();
+    return 0;
+}
+extern "C" void lqrhip_vmap_release(LqrHipVMap *m) { delete m; }
+extern "C" int lqrhip_vmap_load(LqrHipBatch *b, const LqrHipVMap *m)
+{
+    if (!m || !m->plane) return LQRHIP_EARG;
+    for (auto *c : b->cs)
+        if (c->w0 != m->len || c->h0 != m->lines) { g_err = "vmap: the carver's frame is not the map's"; return LQRHIP_EARG; }
+    return inflate_stage(b, m->len, m->lines, m->depth, 1, m->plane);
 }
 extern "C" int lqrhip_planes_commit(LqrHipBatch *b)
 {

@@ -28,6 +28,7 @@
 #include "../../include/lqr_imagetype.h"
 #include "../../include/lqr_masks.h"
 #include "../../include/lqr_energy.h"
+#include "../../include/lqr_vmap.h"
 #include "../../include/lqr_hip.h"
 #include "lqr_mask_queue.h"
 
@@ -208,6 +209,16 @@ gint lqr_vmap_get_height(LqrVMap *v) { return v->height; }
 gint lqr_vmap_get_depth(LqrVMap *v) { return v->depth; }
 gint lqr_vmap_get_orientation(LqrVMap *v) { return v->orientation; }
 void lqr_vmap_destroy(LqrVMap *v) { if (v) { free(v->buffer); free(v); } }
+/* lqr_vmap.h: a map object around the caller's malloc'd buffer, which it owns from here on.  Nothing is checked, as in liblqr:
+ * lqr_vmap_load is where a map meets a carver */
+LqrVMap *lqr_vmap_new(gint *buffer, gint width, gint height, gint depth, gint orientation)
+{
+    LqrVMap *v = (LqrVMap *) calloc(1, sizeof *v);
+    if (!v) return NULL;
+    v->buffer = buffer;
+    v->width = width; v->height = height; v->depth = depth; v->orientation = orientation;
+    return v;
+}
 
 /* ======================= lifecycle ======================================= */
 /* the carver of lqr_carver_new / lqr_carver_new_ext, arguments checked: pixels of `depth` (LqrColDepth) uploaded as the base
@@ -909,7 +920,8 @@ LqrVMap *lqr_vmap_dump(LqrCarver *r)
     return v;
 }
 
-static LqrRetVal vmap_internal_dump(LqrCarver *r)
+/* lqr_vmap.h: the carver's map as it stands, appended to the carver's own list (what lqr_carver_set_dump_vmaps makes every resize do) */
+LqrRetVal lqr_vmap_internal_dump(LqrCarver *r)
 {
     LqrVMap *v = lqr_vmap_dump(r);
     LqrVMapList *n = (LqrVMapList *) calloc(1, sizeof *n), *p;
@@ -918,6 +930,81 @@ static LqrRetVal vmap_internal_dump(LqrCarver *r)
     if (!r->flushed_vs) r->flushed_vs = n;
     else { for (p = r->flushed_vs; p->next; p = p->next); p->next = n; }
     return LQR_OK;
+}
+
+/* ======================= vmap load (lqr_vmap.h) ========================== */
+static int same_config(const LqrCarver *a, const LqrCarver *b);
+/* One map onto n root carvers of its size that lqr_carver_init has not seen.  Everything that can refuse the call is decided before a
+ * carver changes: the arguments and sizes here, the map's contents on the device (lqrhip_vmap_stage).  Then: flatten if the carvers
+ * were resized since their last load, transpose if the map lies the other way, and the inflate pass of the whole tree with the map as
+ * every carver's levels, staged on every sub-batch before any commits.  The bookkeeping is group_build_vsmap's after its inflate. */
+static LqrRetVal group_vmap_load(LqrCarver **rs, int n, const gint *map, int on_device, int width, int height, int depth, int orientation)
+{
+    Group g;
+    LqrHipVMap *staged = NULL;
+    LqrRetVal ret = LQR_OK;
+    int i, rc;
+    if (n < 1 || !rs || !map || (orientation != 0 && orientation != 1)) return LQR_ERROR;
+    for (i = 0; i < n; i++)
+        if (!rs[i] || rs[i]->root || rs[i]->active) return LQR_ERROR;
+    for (i = 1; i < n; i++)
+        if (!same_config(rs[0], rs[i])) return LQR_ERROR;
+    for (i = 0; i < n; i++) LQR_CATCH(mask_queue_flush(rs[i]));
+    if (lqr_carver_get_width(rs[0]) != width || lqr_carver_get_height(rs[0]) != height) {
+        fprintf(stderr, "liblqr-hip: lqr_vmap_load refused: a %d x %d map on a carver that is %d x %d now\n", width, height,
+                lqr_carver_get_width(rs[0]), lqr_carver_get_height(rs[0]));
+        return LQR_ERROR;
+    }
+    if (depth < 1 || depth >= (orientation ? height : width) || (orientation ? height : width) > LQRHIP_MAX_FRAME_WIDTH) {
+        fprintf(stderr, "liblqr-hip: lqr_vmap_load refused: depth %d on lines of %d (0 < depth < line length <= %d)\n", depth,
+                orientation ? height : width, LQRHIP_MAX_FRAME_WIDTH);
+        return LQR_ERROR;
+    }
+    LQR_CATCH(group_open(&g, rs, n));
+    rc = lqrhip_vmap_stage(map, on_device, width, height, depth, orientation, &staged);
+    if (rc == LQRHIP_EMAP) {        /* a bad argument, not a device error: said once, nothing has changed */
+        fprintf(stderr, "liblqr-hip: lqr_vmap_load refused: %s\n", lqrhip_last_error());
+        ret = LQR_ERROR;
+    } else
+        ret = hip_ret(rc);
+    if (ret == LQR_OK) ret = group_flatten(&g);
+    if (ret == LQR_OK && rs[0]->transposed != orientation) ret = group_transpose(&g);
+    if (ret == LQR_OK) {
+        int k;
+        for (k = 0; k < g.nb && ret == LQR_OK; k++) ret = hip_ret(lqrhip_vmap_load(g.b[k], staged));     /* every sub-batch staged ... */
+        for (k = 0; k < g.nb && ret == LQR_OK; k++) ret = hip_ret(lqrhip_planes_commit(g.b[k]));         /* ... before any adopts */
+    }
+    if (ret == LQR_OK) {
+        FOR_TREE(&g, i, r, {
+            r->max_level = r->level = depth + 1;
+            r->w0 = r->w_start + depth;
+            set_width_one(r, r->w_start);
+            r->enl_step = 2.0f;
+            r->wk_valid = 0;
+        });
+    } else if (rc != LQRHIP_EMAP) {
+        int k;
+        for (k = 0; k < g.nb; k++) lqrhip_batch_abort(g.b[k]);          /* nothing staged may surface later */
+    }
+    lqrhip_vmap_release(staged);
+    group_close(&g);
+    return ret;
+}
+
+LqrRetVal lqr_vmap_load(LqrCarver *r, LqrVMap *vmap)
+{
+    if (!r || !vmap) return LQR_ERROR;
+    return group_vmap_load(&r, 1, vmap->buffer, 0, vmap->width, vmap->height, vmap->depth, vmap->orientation);
+}
+LqrRetVal lqrx_vmap_load_device(LqrCarver *r, const gint *device_map, gint width, gint height, gint depth, gint orientation)
+{
+    if (!r) return LQR_ERROR;
+    return group_vmap_load(&r, 1, device_map, 1, width, height, depth, orientation);
+}
+LqrRetVal lqrx_vmap_load_batch(LqrCarver **carvers, gint n, LqrVMap *vmap)
+{
+    if (!vmap) return LQR_ERROR;
+    return group_vmap_load(carvers, n, vmap->buffer, 0, vmap->width, vmap->height, vmap->depth, vmap->orientation);
 }
 
 /* ======================= resize (E10) ==================================== */
@@ -956,7 +1043,7 @@ static LqrRetVal group_resize_dir(Group *g, int w1, int want_transposed)
         for (i = 0; i < g->n; i++) {
             set_width_tree(g->r[i], new_w);
             g->r[i]->session_rescale_current = g->r[i]->session_rescale_total - (gamma > 0 ? gamma : -gamma);
-            if (g->r[i]->dump_vmaps) LQR_CATCH(vmap_internal_dump(g->r[i]));
+            if (g->r[i]->dump_vmaps) LQR_CATCH(lqr_vmap_internal_dump(g->r[i]));
         }
         if (new_w < w1) {
             LQR_CATCH(group_flatten(g));
@@ -1011,6 +1098,23 @@ static int frame_refused(const LqrCarver *r, int w1, int want_transposed)
     }
 }
 
+/* A carver lqr_carver_init has not seen cannot build maps: it serves the sizes the map it was given covers (lqr_vmap_load), in that
+ * map's direction, and nothing else.  The walk is group_resize_dir's: what is asked of group_build_maps must lie within max_level,
+ * without a transposition and without a second step.  Decided from the sizes alone, before the resize touches anything (lqr_vmap.h 3) */
+static int inactive_refused(const LqrCarver *r, int w1, int want_transposed)
+{
+    const int same = (r->transposed == want_transposed);
+    int delta, delta_max;
+    if (r->active) return 0;
+    if (w1 == (same ? r->w : r->h)) return 0;           /* nothing to do in this direction */
+    if (!same) return 1;
+    delta = w1 - r->w_start;
+    if (delta < 0) return -delta + 1 > r->max_level;
+    delta_max = (int) ((r->enl_step - 1) * r->w_start) - 1;
+    if (delta_max < 1) delta_max = 1;
+    return delta > delta_max || delta + 1 > r->max_level;
+}
+
 static LqrRetVal group_resize(LqrCarver **rs, int n, int w1, int h1)
 {
     Group g;
@@ -1026,6 +1130,8 @@ static LqrRetVal group_resize(LqrCarver **rs, int n, int w1, int h1)
                     LQRHIP_MAX_FRAME_WIDTH);
             return LQR_ERROR;
         }
+    for (i = 0; i < n; i++)
+        if (inactive_refused(rs[i], w1, 0) || inactive_refused(rs[i], h1, 1)) return LQR_ERROR;
     {
         T_BEGIN(T_OPEN);
         LQR_CATCH(group_open(&g, rs, n));

@@ -39,6 +39,7 @@ extern "C" {
 #define LQRHIP_EHIP (-1)
 #define LQRHIP_EARG (-3)
 #define LQRHIP_EFAULT (-4)   /* a kernel of the session gave up or a self-check failed: roll back, redo (lqrhip_session_rollback) */
+#define LQRHIP_EMAP (-5)     /* lqrhip_vmap_stage: the caller's seam map is not one.  A bad argument, not a device fault: nothing to roll back */
 #define LQRHIP_MAX_DELTA 16
 #define LQRHIP_MAX_CHANNELS 64      /* channels per pixel at most (lqrx_set_max_channels) */
 /* The widest frame, in the direction being carved, that a session may start from: k_dp_sweep holds two rows of it in LDS (128 KB)
@@ -226,6 +227,19 @@ void lqrhip_debug_fixedcost(unsigned long long out4[4], int reset);
  * whole group where it was.  A staged pass is discarded by the next staging call, lqrhip_session_rollback, _batch_abort, _batch_destroy.
  * E14 lqr_carver_inflate(l) on roots and their attached carvers; carries the session's second self-check */
 int lqrhip_inflate(LqrHipBatch *b, int w0, int h0, int l, int max_level);
+/* lqr_vmap_load (lqr_vmap.h), in two steps.  lqrhip_vmap_stage brings a width x height seam map of `depth` seams (row-major in IMAGE
+ * orientation; on_device = 0: host memory, uploaded once through the pinned ring; 1: device memory, read where it lies, which must stay
+ * as it is until the loads that use it have been committed) to the device and checks it in one pass: 0 < depth < line length, every
+ * value in [0, depth], every level 1 .. depth exactly once in every line of the carving direction (a row for orientation 0, a column
+ * for 1); an orientation-1 map is laid out in the carver's frame by the same pass.  A map that fails returns LQRHIP_EMAP and changes
+ * nothing: no batch is invalidated, lqrhip_fault_stats and the non-spinning mode stay as they are.  lqrhip_vmap_load is then phase one
+ * of a pass like lqrhip_inflate: the batch's carvers -- flat, and in the map's frame -- stage the layout in which every seam of the map
+ * is doubled, all reading their levels from the ONE checked plane; lqrhip_planes_commit adopts it.  lqrhip_vmap_release gives the
+ * staged map back (after the commits, or instead of them). */
+typedef struct LqrHipVMap LqrHipVMap;
+int lqrhip_vmap_stage(const int *map, int on_device, int width, int height, int depth, int orientation, LqrHipVMap **out);
+int lqrhip_vmap_load(LqrHipBatch *b, const LqrHipVMap *m);
+void lqrhip_vmap_release(LqrHipVMap *m);
 /* E11 lqr_carver_flatten (render.c:325,636): keep pixels visible at `level` */
 int lqrhip_flatten(LqrHipBatch *b, int w0, int h0, int w, int level);
 /* E11 lqr_carver_transpose: base planes of a flat carver, w x h -> h x w */

@@ -699,6 +699,23 @@ class RefCarver:
         self.r.call("lqr_vmap_destroy", v)
         return d
 
+    # -- loading a seam map (include/lqr_vmap.h), as binding.Carver's
+    def vmap_load(self, m):
+        """lqr_vmap_new on a runner-side copy of m["data"] (the map object owns it), lqr_vmap_load, lqr_vmap_destroy; the LqrRetVal"""
+        r = self.r
+        data = np.ascontiguousarray(m["data"], dtype=np.int32)
+        h, w = data.shape
+        buf = r.alloc(max(data.nbytes, 1))
+        r.write(buf, data.tobytes())
+        v = r.call("lqr_vmap_new", buf, w, h, int(m["depth"]), int(m["orientation"]))
+        assert v
+        ret = r.call("lqr_vmap_load", self.p, v)
+        r.call("lqr_vmap_destroy", v)
+        return ret
+
+    def vmap_internal_dump(self):
+        return self.r.call("lqr_vmap_internal_dump", self.p)
+
     def dumped_vmaps(self):
         r = self.r
         out = []
