@@ -4,10 +4,11 @@
  * include/lqr_hip.h.  It is what gimp-lqr-plugin's src/render.c and
  * src/io_functions.c bind instead of liblqr-1.
  *
- * This file holds NO pixel arithmetic: it keeps the carver's geometry / level
- * bookkeeping (what liblqr keeps in LqrCarver), decides per seam whether the DP
- * map is rebuilt or band-updated (the side-switch schedule), fires the progress
- * callbacks, and serves scan lines from a packed read-back.  All planes live in
+ * This file holds NO pixel arithmetic: it keeps what liblqr keeps in LqrCarver,
+ * does on the device what the resize schedule of lqr_sched.h says comes next
+ * (the geometry's transitions, the steps of a direction, per seam whether the DP
+ * map is rebuilt or band-updated), fires the progress callbacks, and serves
+ * scan lines from a packed read-back.  All planes live in
  * HBM; every stage is a kernel launched through lqrhip_*.  There is no CPU
  * fallback: without a gfx950 device lqr_carver_new() returns NULL and says why.
  *
@@ -31,6 +32,7 @@
 #include "../../include/lqr_vmap.h"
 #include "../../include/lqr_hip.h"
 #include "lqr_mask_queue.h"
+#include "lqr_sched.h"
 
 #define MAXI(a, b) ((a) > (b) ? (a) : (b))
 #define MINI(a, b) ((a) < (b) ? (a) : (b))
@@ -83,16 +85,13 @@ struct _LqrCarverList {
 };
 
 struct _LqrCarver {
-    /* geometry, in the carver frame (transposed => frame x runs along image y) */
-    int w_start, h_start, w, h, w0, h0;
-    int level, max_level;
+    LqrGeom geo;                /* the geometry and its transitions: lqr_sched.h */
     int channels;
     int col_depth;              /* LqrColDepth: 0 (8I, what lqr_carver_new makes) .. 3 (64F) */
     int image_type;             /* LqrImageType, with the channel indices of its roles (-1: none): what the energy reads (lqr_imagetype.h) */
     int alpha_channel, black_channel;
     int preserve_input;         /* lqr_carver_set_preserve_input_image: the caller's buffer is never written nor freed */
     int img_w, img_h;           /* the image handed to lqr_carver_new */
-    int transposed;
     int active;
     LqrCarver *root;
     LqrCarverList *attached;
@@ -192,6 +191,13 @@ LqrRetVal lqr_progress_set_end_width_message(LqrProgress *p, const gchar *m) { r
 LqrRetVal lqr_progress_set_end_height_message(LqrProgress *p, const gchar *m) { return copy_message(p->end_height_message, m); }
 
 /* ======================= lists, vmaps ==================================== */
+/* node n at the end of a list of T (the attached carvers, the dumped maps) */
+#define LIST_APPEND(T, head, n)                      \
+    do {                                             \
+        T **pp__ = &(head);                          \
+        while (*pp__) pp__ = &(*pp__)->next;         \
+        *pp__ = (n);                                 \
+    } while (0)
 LqrCarverList *lqr_carver_list_start(LqrCarver *r) { return r->attached; }
 LqrCarver *lqr_carver_list_current(LqrCarverList *l) { return l->current; }
 LqrCarverList *lqr_carver_list_next(LqrCarverList *l) { return l->next; }
@@ -259,10 +265,8 @@ static LqrCarver *carver_new(void *buffer, int width, int height, int channels, 
     (void) lqrhip_carver_set_read(r->dev, r->image_type, r->alpha_channel, r->black_channel);
     r->in_buffer = (guchar *) buffer;
     r->in_buffer_len = (size_t) width * height * channels * k_depth_bytes[depth];
-    r->level = r->max_level = 1;
+    lqr_geom_reset(&r->geo, width, height);
     r->delta_x = 1;
-    r->w = r->w0 = r->w_start = width;
-    r->h = r->h0 = r->h_start = height;
     r->img_w = width; r->img_h = height;
     r->nrg_func = LQR_EF_GRAD_XABS;
     r->nrg_radius = 1;
@@ -334,16 +338,21 @@ static LqrRetVal set_role(LqrCarver *r, int *role, int *other, int index)
 LqrRetVal lqr_carver_set_alpha_channel(LqrCarver *r, gint i) { return set_role(r, &r->alpha_channel, &r->black_channel, i); }
 LqrRetVal lqr_carver_set_black_channel(LqrCarver *r, gint i) { return set_role(r, &r->black_channel, &r->alpha_channel, i); }
 
-LqrRetVal lqr_carver_init(LqrCarver *r, gint delta_x, gfloat rigidity)
+/* rigidity bias ~ |dx|^1.5 summed along the seam (help/en/index.wiki:83); the
+ * table is tiny and is computed on the host so that it is bit-identical to C */
+static void rigidity_table(LqrCarver *r)
 {
     int x;
+    for (x = -r->delta_x; x <= r->delta_x; x++)
+        r->rigidity_map[x + r->delta_x] = r->rigidity * powf(fabsf((float) x), 1.5f) / r->geo.h;
+}
+
+LqrRetVal lqr_carver_init(LqrCarver *r, gint delta_x, gfloat rigidity)
+{
     if (r->active || delta_x < 0 || delta_x > LQRHIP_MAX_DELTA) return LQR_ERROR;
     r->delta_x = delta_x;
     r->rigidity = rigidity;
-    /* rigidity bias ~ |dx|^1.5 summed along the seam (help/en/index.wiki:83); the
-     * table is tiny and is computed on the host so that it is bit-identical to C */
-    for (x = -delta_x; x <= delta_x; x++)
-        r->rigidity_map[x + delta_x] = r->rigidity * powf(fabsf((float) x), 1.5f) / r->h;
+    rigidity_table(r);
     HIP_CATCH(lqrhip_carver_activate(r->dev));
     r->active = 1;
     return LQR_OK;
@@ -377,13 +386,12 @@ void lqr_carver_destroy(LqrCarver *r)
 
 LqrRetVal lqr_carver_attach(LqrCarver *r, LqrCarver *aux)
 {
-    LqrCarverList *n, *p;
-    if (r->w0 != aux->w0 || r->h0 != aux->h0) return LQR_ERROR;
+    LqrCarverList *n;
+    if (r->geo.w0 != aux->geo.w0 || r->geo.h0 != aux->geo.h0) return LQR_ERROR;
     n = (LqrCarverList *) calloc(1, sizeof *n);
     if (!n) return LQR_NOMEM;
     n->current = aux;
-    if (!r->attached) r->attached = n;
-    else { for (p = r->attached; p->next; p = p->next); p->next = n; }
+    LIST_APPEND(LqrCarverList, r->attached, n);
     aux->root = r;
     HIP_CATCH(lqrhip_carver_attach(r->dev, aux->dev));
     return LQR_OK;
@@ -415,23 +423,27 @@ gfloat lqr_carver_get_enl_step(LqrCarver *r) { return r->enl_step; }
 void lqr_carver_set_dump_vmaps(LqrCarver *r) { r->dump_vmaps = 1; }
 
 /* ======================= getters ========================================= */
-gint lqr_carver_get_width(LqrCarver *r) { return r->transposed ? r->h : r->w; }
-gint lqr_carver_get_height(LqrCarver *r) { return r->transposed ? r->w : r->h; }
+gint lqr_carver_get_width(LqrCarver *r) { return r->geo.transposed ? r->geo.h : r->geo.w; }
+gint lqr_carver_get_height(LqrCarver *r) { return r->geo.transposed ? r->geo.w : r->geo.h; }
 gint lqr_carver_get_channels(LqrCarver *r) { return r->channels; }
-gint lqr_carver_get_ref_width(LqrCarver *r) { return r->transposed ? r->h_start : r->w_start; }
-gint lqr_carver_get_ref_height(LqrCarver *r) { return r->transposed ? r->w_start : r->h_start; }
-gint lqr_carver_get_orientation(LqrCarver *r) { return r->transposed ? 1 : 0; }
-gint lqr_carver_get_depth(LqrCarver *r) { return r->w0 - r->w_start; }
-gint lqrx_carver_frame_width(LqrCarver *r) { return r->w; }
-gint lqrx_carver_frame_height(LqrCarver *r) { return r->h; }
+gint lqr_carver_get_ref_width(LqrCarver *r) { return r->geo.transposed ? r->geo.h_start : r->geo.w_start; }
+gint lqr_carver_get_ref_height(LqrCarver *r) { return r->geo.transposed ? r->geo.w_start : r->geo.h_start; }
+gint lqr_carver_get_orientation(LqrCarver *r) { return r->geo.transposed ? 1 : 0; }
+gint lqr_carver_get_depth(LqrCarver *r) { return r->geo.w0 - r->geo.w_start; }
+gint lqrx_carver_frame_width(LqrCarver *r) { return r->geo.w; }
+gint lqrx_carver_frame_height(LqrCarver *r) { return r->geo.h; }
 
 /* ======================= group helpers =================================== */
-static void set_width_one(LqrCarver *r, int w1)
+/* what is visible changed: the read-out cache is stale and the scan starts over */
+static void ro_invalidate(LqrCarver *r)
 {
-    r->w = w1;
-    r->level = r->w0 - w1 + 1;
     r->ro_valid = 0;
     r->ro_line = 0; r->ro_x = 0;
+}
+static void set_width_one(LqrCarver *r, int w1)
+{
+    lqr_geom_set_width(&r->geo, w1);
+    ro_invalidate(r);
 }
 static void set_width_tree(LqrCarver *r, int w1)
 {
@@ -441,7 +453,7 @@ static void set_width_tree(LqrCarver *r, int w1)
 }
 
 /* delta_x = 2 .. 10 (the whole range of the plug-in's dialog, src/interface.c:47), or a rigidity mask that matters: the carver runs
- * on the tiled kernels' general instantiations, which need the whole group co-resident on ONE stream (DESIGN.md 4.13) */
+ * on the tiled kernels' general instantiations, which need the whole group co-resident on ONE stream (DESIGN.md 4.1) */
 static int is_general(const LqrCarver *c)
 {
     return (c->delta_x >= 2 && c->delta_x <= 10) || (c->delta_x == 1 && c->has_rigmask && c->rigidity != 0);
@@ -527,7 +539,7 @@ static void dp_params(const LqrCarver *r, LqrHipDpParams *p)
     memcpy(p->rigidity_map, r->rigidity_map, sizeof p->rigidity_map);
     p->nrg_func = r->nrg_func;
     p->nrg_radius = r->nrg_radius;
-    p->w_start = r->w_start;
+    p->w_start = r->geo.w_start;
 }
 
 /* ======================= queued _xy mask calls (lqr_masks.h) ============= */
@@ -562,18 +574,15 @@ static LqrRetVal group_flatten(Group *g)
 {
     LqrCarver *r0 = g->r[0];
     int i;
-    /* a carver that is already flat (nothing hidden, nothing inserted) is its own flattening */
-    if (!(r0->w == r0->w0 && r0->level == 1 && r0->max_level == 1 && r0->w_start == r0->w0))
-    {
-        HIP_ALL(g, lqrhip_flatten(B, r0->w0, r0->h0, r0->w, r0->level));     /* every sub-batch staged ... */
-        HIP_ALL(g, lqrhip_planes_commit(B));                                 /* ... before any adopts its flat layout */
-    } else if (r0->wk_valid)
+    if (!lqr_geom_is_flat(&r0->geo)) {
+        HIP_ALL(g, lqrhip_flatten(B, r0->geo.w0, r0->geo.h0, r0->geo.w, r0->geo.level));     /* every sub-batch staged ... */
+        HIP_ALL(g, lqrhip_planes_commit(B));                                                 /* ... before any adopts its flat layout */
+    } else if (r0->wk_valid)       /* a flat carver is its own flattening */
         return LQR_OK;
     FOR_TREE(g, i, r, {
-        r->w0 = r->w; r->h0 = r->h;
-        r->w_start = r->w; r->h_start = r->h;
-        r->level = 1; r->max_level = 1;
-        r->wk_valid = 0; r->ro_valid = 0; r->ro_line = 0; r->ro_x = 0;
+        lqr_geom_flattened(&r->geo);
+        r->wk_valid = 0;
+        ro_invalidate(r);
     });
     return LQR_OK;
 }
@@ -581,20 +590,17 @@ static LqrRetVal group_flatten(Group *g)
 static LqrRetVal group_transpose(Group *g)
 {
     LqrCarver *r0 = g->r[0];
-    int i, x, d;
-    if (r0->level > 1 || r0->max_level > 1 || r0->w0 != r0->w) LQR_CATCH(group_flatten(g));
-    HIP_ALL(g, lqrhip_transpose(B, r0->w0, r0->h0));
+    int i, x;
+    if (lqr_geom_flatten_before_transpose(&r0->geo)) LQR_CATCH(group_flatten(g));
+    HIP_ALL(g, lqrhip_transpose(B, r0->geo.w0, r0->geo.h0));
     HIP_ALL(g, lqrhip_planes_commit(B));
     FOR_TREE(g, i, r, {
-        d = r->w0; r->w0 = r->h0; r->h0 = d;
-        r->w = r->w0; r->h = r->h0;
-        r->w_start = r->w0; r->h_start = r->h0;
-        r->level = 1; r->max_level = 1;
+        lqr_geom_transposed(&r->geo);
         if (r->active)      /* the rigidity table is rescaled, not recomputed */
             for (x = -r->delta_x; x <= r->delta_x; x++)
-                r->rigidity_map[x + r->delta_x] = r->rigidity_map[x + r->delta_x] * r->w0 / r->h0;
-        r->transposed = r->transposed ? 0 : 1;
-        r->wk_valid = 0; r->ro_valid = 0; r->ro_line = 0; r->ro_x = 0;
+                r->rigidity_map[x + r->delta_x] = r->rigidity_map[x + r->delta_x] * r->geo.w0 / r->geo.h0;
+        r->wk_valid = 0;
+        ro_invalidate(r);
     });
     return LQR_OK;
 }
@@ -615,7 +621,7 @@ LqrRetVal lqr_carver_flatten(LqrCarver *r)
 static LqrRetVal mask_prepare(LqrCarver *r)
 {
     if (!r->active || r->root) return LQR_ERROR;
-    if (r->w != r->w0 || r->w_start != r->w0 || r->h != r->h0 || r->h_start != r->h0) LQR_CATCH(lqr_carver_flatten(r));
+    if (lqr_geom_needs_flatten(&r->geo)) LQR_CATCH(lqr_carver_flatten(r));
     return LQR_OK;
 }
 
@@ -625,7 +631,7 @@ LqrRetVal lqr_carver_bias_add_rgb_area(LqrCarver *r, guchar *rgb, gint bias_fact
     LQR_CATCH(mask_prepare(r));
     if (bias_factor == 0) return LQR_OK;
     LQR_CATCH(mask_queue_flush(r));
-    HIP_CATCH(lqrhip_mask_add(r->dev, rgb, channels, width, height, x_off, y_off, r->transposed, 0, bias_factor));
+    HIP_CATCH(lqrhip_mask_add(r->dev, rgb, channels, width, height, x_off, y_off, r->geo.transposed, 0, bias_factor));
     r->has_bias = 1;
     r->wk_valid = 0;
     return LQR_OK;
@@ -636,7 +642,7 @@ LqrRetVal lqr_carver_rigmask_add_rgb_area(LqrCarver *r, guchar *rgb, gint channe
 {
     LQR_CATCH(mask_prepare(r));
     LQR_CATCH(mask_queue_flush(r));
-    HIP_CATCH(lqrhip_mask_add(r->dev, rgb, channels, width, height, x_off, y_off, r->transposed, 1, 0));
+    HIP_CATCH(lqrhip_mask_add(r->dev, rgb, channels, width, height, x_off, y_off, r->geo.transposed, 1, 0));
     r->has_rigmask = 1;
     r->wk_valid = 0;
     return LQR_OK;
@@ -648,7 +654,7 @@ LqrRetVal lqr_carver_rigmask_add_rgb_area(LqrCarver *r, guchar *rgb, gint channe
 static LqrRetVal bias_prepare(LqrCarver *r)
 {
     if (r->root) return LQR_ERROR;
-    if (r->w != r->w0 || r->w_start != r->w0 || r->h != r->h0 || r->h_start != r->h0) LQR_CATCH(lqr_carver_flatten(r));
+    if (lqr_geom_needs_flatten(&r->geo)) LQR_CATCH(lqr_carver_flatten(r));
     return LQR_OK;
 }
 static LqrRetVal mask_add_f(LqrCarver *r, const void *buffer, int depth, int on_device, int is_rig, int bias_factor, int width, int height,
@@ -657,7 +663,7 @@ static LqrRetVal mask_add_f(LqrCarver *r, const void *buffer, int depth, int on_
     if (!is_rig && bias_factor == 0) return LQR_OK;     /* liblqr: before anything else */
     LQR_CATCH(is_rig ? mask_prepare(r) : bias_prepare(r));
     LQR_CATCH(mask_queue_flush(r));
-    HIP_CATCH(lqrhip_mask_add_f(r->dev, buffer, depth, on_device, width, height, x_off, y_off, r->transposed, is_rig, bias_factor));
+    HIP_CATCH(lqrhip_mask_add_f(r->dev, buffer, depth, on_device, width, height, x_off, y_off, r->geo.transposed, is_rig, bias_factor));
     if (is_rig) r->has_rigmask = 1; else r->has_bias = 1;
     r->wk_valid = 0;
     return LQR_OK;
@@ -675,7 +681,7 @@ LqrRetVal lqr_carver_bias_add_rgb(LqrCarver *r, guchar *rgb, gint bias_factor, g
     if (bias_factor == 0) return LQR_OK;
     LQR_CATCH(bias_prepare(r));
     LQR_CATCH(mask_queue_flush(r));
-    HIP_CATCH(lqrhip_mask_add(r->dev, rgb, channels, lqr_carver_get_width(r), lqr_carver_get_height(r), 0, 0, r->transposed, 0, bias_factor));
+    HIP_CATCH(lqrhip_mask_add(r->dev, rgb, channels, lqr_carver_get_width(r), lqr_carver_get_height(r), 0, 0, r->geo.transposed, 0, bias_factor));
     r->has_bias = 1;
     r->wk_valid = 0;
     return LQR_OK;
@@ -720,11 +726,11 @@ static LqrRetVal mask_add_xy(LqrCarver *r, int is_rig, double v, int x, int y)
         r->wk_valid = 0;
     } else if (x < 0 || y < 0 || x >= lqr_carver_get_width(r) || y >= lqr_carver_get_height(r))
         return LQR_ERROR;
-    index = r->transposed ? x * r->w0 + y : y * r->w0 + x;
-    rc = lqr_maskq_append(q, (size_t) r->w0 * r->h0, index, v);
+    index = r->geo.transposed ? x * r->geo.w0 + y : y * r->geo.w0 + x;
+    rc = lqr_maskq_append(q, (size_t) r->geo.w0 * r->geo.h0, index, v);
     if (rc == LQR_MASKQ_FULL) {         /* the bound: an early flush */
         LQR_CATCH(mask_queue_flush_one(r, is_rig));
-        rc = lqr_maskq_append(q, (size_t) r->w0 * r->h0, index, v);
+        rc = lqr_maskq_append(q, (size_t) r->geo.w0 * r->geo.h0, index, v);
     }
     return rc == LQR_MASKQ_OK ? LQR_OK : rc == LQR_MASKQ_NOMEM ? LQR_NOMEM : LQR_ERROR;
 }
@@ -749,8 +755,8 @@ void lqr_carver_rigmask_clear(LqrCarver *r) { mask_clear(r, 1); }
 static LqrRetVal mask_read(LqrCarver *r, int is_rig, gfloat *out)
 {
     LQR_CATCH(mask_queue_flush(r));
-    if (r->w != r->w0 || r->w_start != r->w0 || r->h != r->h0 || r->h_start != r->h0) return LQR_ERROR;     /* flat carvers only */
-    HIP_CATCH(lqrhip_read_mask_plane(r->dev, is_rig, r->transposed, out));
+    if (lqr_geom_needs_flatten(&r->geo)) return LQR_ERROR;     /* flat carvers only */
+    HIP_CATCH(lqrhip_read_mask_plane(r->dev, is_rig, r->geo.transposed, out));
     return LQR_OK;
 }
 LqrRetVal lqrx_carver_get_bias(LqrCarver *r, gfloat *out) { return mask_read(r, 0, out); }
@@ -759,53 +765,42 @@ LqrRetVal lqrx_carver_get_rigmask(LqrCarver *r, gfloat *out) { return mask_read(
 /* ======================= per-seam loop (E10) ============================= */
 static LqrRetVal take_debug_snapshot(LqrCarver *r)
 {
-    size_t n = (size_t) r->w * r->h;
+    size_t n = (size_t) r->geo.w * r->geo.h;
     free(r->dbg_en); free(r->dbg_m); free(r->dbg_least);
-    r->dbg_w = r->w; r->dbg_h = r->h;
+    r->dbg_w = r->geo.w; r->dbg_h = r->geo.h;
     r->dbg_en = (float *) malloc(n * sizeof(float));
     r->dbg_m = (float *) malloc(n * sizeof(float));
     r->dbg_least = (int *) malloc(n * sizeof(int));
     if (!r->dbg_en || !r->dbg_m || !r->dbg_least) return LQR_NOMEM;
-    HIP_CATCH(lqrhip_read_working(r->dev, r->w, r->h, r->dbg_en, r->dbg_m, r->dbg_least));
+    HIP_CATCH(lqrhip_read_working(r->dev, r->geo.w, r->geo.h, r->dbg_en, r->dbg_m, r->dbg_least));
     return LQR_OK;
 }
 
-static LqrRetVal group_build_vsmap(Group *g, int depth, int *reported)
+/* the seam loop of one session and its commit; what happens at which seam is the session's schedule (lqr_sched.h) */
+static LqrRetVal group_build_vsmap(Group *g, const LqrSession *s, int *reported)
 {
     LqrCarver *r0 = g->r[0];
     LqrHipDpParams p;
-    int l, i, lr_switch_interval = 0, n_seams, wc0, first_level, finish = 0, w1;
-    if (depth == 0) depth = r0->w_start + 1;
-    n_seams = depth - r0->max_level;
-    wc0 = r0->w;                         /* = w_start - max_level + 1, the carved frame */
-    first_level = 2 * r0->max_level - 1; /* seam l is stored as level l + max_level - 1 */
-    /* "frequency" = number of side switches per rescale operation */
-    if (r0->lr_switch_frequency) lr_switch_interval = (depth - r0->max_level - 1) / r0->lr_switch_frequency + 1;
+    int l, i;
     dp_params(r0, &p);
-    HIP_ALL(g, lqrhip_seam_log_reserve(B, n_seams, r0->h));
+    HIP_ALL(g, lqrhip_seam_log_reserve(B, s->n_seams, r0->geo.h));
 
-    for (l = r0->max_level; l < depth; l++) {
-        int full = 0, lr_pick = r0->leftright, w_before = r0->w;
-        if ((l - r0->max_level + r0->session_rescale_current) % r0->session_update_step == 0 && r0->progress &&
-            r0->progress->update) {
+    for (l = s->max_level; l < s->depth; l++) {
+        const int lr_pick = r0->leftright;
+        LqrSeam seam;
+        lqr_session_seam(s, l, &seam);
+        if (seam.report && r0->progress && r0->progress->update) {
             /* report completed work, not enqueued work (a session that is being redone does not report twice) */
             HIP_ALL(g, lqrhip_batch_sync(B));
             if (l > *reported) {
-                r0->progress->update((gdouble) (l - r0->max_level + r0->session_rescale_current) /
-                                     (gdouble) r0->session_rescale_total);
+                r0->progress->update(seam.fraction);
                 *reported = l;
             }
         }
-        if (w_before - 1 > 1) {
-            if (r0->lr_switch_frequency && ((l - r0->max_level + lr_switch_interval / 2) % lr_switch_interval) == 0) {
-                for (i = 0; i < g->n; i++) g->r[i]->leftright ^= 1;
-                full = 1;
-            }
-        } else {
-            finish = 1;
-        }
-        HIP_ALL(g, lqrhip_seam_step(B, &p, w_before, r0->h, l - r0->max_level, lr_pick, full, r0->leftright));
-        for (i = 0; i < g->n; i++) { g->r[i]->level++; g->r[i]->w--; }
+        if (seam.full)
+            for (i = 0; i < g->n; i++) g->r[i]->leftright ^= 1;
+        HIP_ALL(g, lqrhip_seam_step(B, &p, seam.w_before, r0->geo.h, l - s->max_level, lr_pick, seam.full, r0->leftright));
+        for (i = 0; i < g->n; i++) { g->r[i]->geo.level++; g->r[i]->geo.w--; }
     }
 
     if (g_debug_snapshot)
@@ -814,75 +809,76 @@ static LqrRetVal group_build_vsmap(Group *g, int depth, int *reported)
     /* the seam loop is over: nothing of it is committed to the base layout before its kernels have all ended without a device-side
      * failure and the seam log has passed its self-check */
     T_BEGIN(T_TAIL);
-    HIP_ALL(g, lqrhip_session_check(B, r0->h, wc0, n_seams, r0->delta_x));
+    HIP_ALL(g, lqrhip_session_check(B, r0->geo.h, s->wc0, s->n_seams, r0->delta_x));
     HIP_ALL(g, lqrhip_batch_sync(B));
-    HIP_ALL(g, lqrhip_vs_commit(B, r0->w0, r0->h0, wc0, n_seams, first_level, finish));
+    HIP_ALL(g, lqrhip_vs_commit(B, r0->geo.w0, r0->geo.h0, s->wc0, s->n_seams, s->first_level, s->finish));
     /* inflate (E14): every seam of this session is doubled in the base layout */
-    HIP_ALL(g, lqrhip_inflate(B, r0->w0, r0->h0, depth - 1, r0->max_level));        /* every sub-batch staged and checked ... */
-    HIP_ALL(g, lqrhip_planes_commit(B));                                            /* ... before any adopts its inflated layout */
+    HIP_ALL(g, lqrhip_inflate(B, r0->geo.w0, r0->geo.h0, s->depth - 1, s->max_level));      /* every sub-batch staged and checked ... */
+    HIP_ALL(g, lqrhip_planes_commit(B));                                                    /* ... before any adopts its inflated layout */
     T_END(T_TAIL);
-    w1 = r0->w0 + (depth - 1) - r0->max_level + 1;
     FOR_TREE(g, i, r, {
-        r->level = depth; r->max_level = depth;
-        r->w0 = w1;
-        set_width_one(r, r->w_start);
+        lqr_geom_session_done(&r->geo, s->depth, s->n_seams);
+        ro_invalidate(r);
     });
     return LQR_OK;
 }
 
 /* one session: (re)lay the working planes out if needed, energy, DP, the seam loop, commit, inflate */
-static LqrRetVal session_run(Group *g, int depth, int redo, int *reported)
+static LqrRetVal session_run(Group *g, const LqrSession *s, int redo, int *reported)
 {
     LqrCarver *r0 = g->r[0];
     LqrHipDpParams p;
     int i;
-    for (i = 0; i < g->n; i++) set_width_one(g->r[i], g->r[i]->w_start - g->r[i]->max_level + 1);    /* the carved frame */
+    for (i = 0; i < g->n; i++) set_width_one(g->r[i], s->wc0);    /* the carved frame */
     dp_params(r0, &p);
     if (!r0->wk_valid || redo) {
         /* a flat carver: identity, and the energy in the same pass over the planes; a multi-size image (a redone deeper session,
          * working planes lost in a failed one): the pixels of the base layout without a level, in order */
-        const int from_visible = (r0->max_level != 1 || r0->w0 != r0->w_start);
+        const int from_visible = (r0->geo.max_level != 1 || r0->geo.w0 != r0->geo.w_start);
         if (from_visible) HIP_ALL(g, lqrhip_wk_init(B, 1));
-        else HIP_ALL(g, lqrhip_wk_init_emap(B, &p, r0->w, r0->h));
+        else HIP_ALL(g, lqrhip_wk_init_emap(B, &p, r0->geo.w, r0->geo.h));
         for (i = 0; i < g->n; i++) g->r[i]->wk_valid = 1;
-        if (from_visible) HIP_ALL(g, lqrhip_emap_build(B, &p, r0->w, r0->h));
+        if (from_visible) HIP_ALL(g, lqrhip_emap_build(B, &p, r0->geo.w, r0->geo.h));
     } else
-        HIP_ALL(g, lqrhip_emap_build(B, &p, r0->w, r0->h));
-    HIP_ALL(g, lqrhip_mmap_build(B, &p, r0->w, r0->h, r0->leftright));
-    return group_build_vsmap(g, depth, reported);
+        HIP_ALL(g, lqrhip_emap_build(B, &p, r0->geo.w, r0->geo.h));
+    HIP_ALL(g, lqrhip_mmap_build(B, &p, r0->geo.w, r0->geo.h, r0->leftright));
+    return group_build_vsmap(g, s, reported);
 }
 
 static LqrRetVal group_build_maps(Group *g, int depth)
 {
     LqrCarver *r0 = g->r[0];
+    LqrSession s;
     LqrRetVal ret;
     int i, k, reported = -1, *snap;
-    if (depth <= r0->max_level) return LQR_OK;
+    if (depth <= r0->geo.max_level) return LQR_OK;
     if (!r0->active || r0->root) return LQR_ERROR;
+    lqr_session_begin(&s, r0->geo.max_level, depth, r0->geo.w_start - r0->geo.max_level + 1, r0->lr_switch_frequency, r0->session_rescale_current,
+                      r0->session_rescale_total, r0->session_update_step);
     /* what a session changes on the host before it succeeds: the roots' width, level and side */
     snap = (int *) malloc((size_t) g->n * 3 * sizeof *snap);
     if (!snap) return LQR_NOMEM;
-    for (i = 0; i < g->n; i++) { snap[3 * i] = g->r[i]->w; snap[3 * i + 1] = g->r[i]->level; snap[3 * i + 2] = g->r[i]->leftright; }
+    for (i = 0; i < g->n; i++) { snap[3 * i] = g->r[i]->geo.w; snap[3 * i + 1] = g->r[i]->geo.level; snap[3 * i + 2] = g->r[i]->leftright; }
     g_last_rc = 0;
-    ret = session_run(g, depth, 0, &reported);
+    ret = session_run(g, &s, 0, &reported);
     for (k = 0; k < 2 && ret != LQR_OK; k++) {
         const int fault = (ret == LQR_ERROR && g_last_rc == LQRHIP_EFAULT);
-        const int wc0 = r0->w_start - r0->max_level + 1, n_seams = (depth ? depth : r0->w_start + 1) - r0->max_level;
         /* the carver as it was before the session: the base layout (levels of this session removed if they were committed),
          * the bookkeeping; the working planes are gone */
         /* (also after an allocation failure: the staging of the inflate pass comes after the commit of the session's levels) */
         if (fault || g_last_rc == LQRHIP_ENOMEM)
-            for (i = 0; i < g->nb; i++) (void) lqrhip_session_rollback(g->b[i], r0->w0, r0->h0, 2 * r0->max_level - 1, wc0 - n_seams <= 1);
+            for (i = 0; i < g->nb; i++) (void) lqrhip_session_rollback(g->b[i], r0->geo.w0, r0->geo.h0, s.first_level, s.finish);
         for (i = 0; i < g->n; i++) {
             LqrCarver *c = g->r[i];
-            c->w = snap[3 * i]; c->level = snap[3 * i + 1]; c->leftright = snap[3 * i + 2];
-            c->wk_valid = 0; c->ro_valid = 0; c->ro_line = 0; c->ro_x = 0;
+            c->geo.w = snap[3 * i]; c->geo.level = snap[3 * i + 1]; c->leftright = snap[3 * i + 2];
+            c->wk_valid = 0;
+            ro_invalidate(c);
         }
         if (!fault || !lqrhip_get_recovery() || k == 1) break;
         fprintf(stderr, "liblqr-hip: the session is carved again on the kernels without spin waits\n");
         for (i = 0; i < g->nb; i++) lqrhip_batch_set_safe(g->b[i], 1);
         g_last_rc = 0;
-        ret = session_run(g, depth, 1, &reported);
+        ret = session_run(g, &s, 1, &reported);
         for (i = 0; i < g->nb; i++) lqrhip_batch_set_safe(g->b[i], 0);
     }
     free(snap);
@@ -893,17 +889,17 @@ static LqrRetVal group_build_maps(Group *g, int depth)
 LqrVMap *lqr_vmap_dump(LqrCarver *r)
 {
     LqrVMap *v;
-    int w = r->w_start, h = r->h, depth = r->w0 - r->w_start, x, y;
+    int w = r->geo.w_start, h = r->geo.h, depth = r->geo.w0 - r->geo.w_start, x, y;
     int *frame, *buffer;
     frame = (int *) malloc((size_t) w * h * sizeof(int));
     v = (LqrVMap *) calloc(1, sizeof *v);
     if (!frame || !v) { free(frame); free(v); return NULL; }
-    if (lqrhip_read_vmap(r->dev, r->w0, r->h0, w, r->w0 - w + 1, depth, frame) != 0) {
+    if (lqrhip_read_vmap(r->dev, r->geo.w0, r->geo.h0, w, r->geo.w0 - w + 1, depth, frame) != 0) {
         fprintf(stderr, "liblqr-hip: vmap read-back failed: %s\n", lqrhip_last_error());
         free(frame); free(v);
         return NULL;
     }
-    if (r->transposed) {    /* hand the map back in image orientation */
+    if (r->geo.transposed) {    /* hand the map back in image orientation */
         buffer = (int *) malloc((size_t) w * h * sizeof(int));
         if (!buffer) { free(frame); free(v); return NULL; }
         for (y = 0; y < h; y++)
@@ -916,7 +912,7 @@ LqrVMap *lqr_vmap_dump(LqrCarver *r)
     v->width = lqr_carver_get_ref_width(r);
     v->height = lqr_carver_get_ref_height(r);
     v->depth = depth;
-    v->orientation = r->transposed;
+    v->orientation = r->geo.transposed;
     return v;
 }
 
@@ -924,11 +920,10 @@ LqrVMap *lqr_vmap_dump(LqrCarver *r)
 LqrRetVal lqr_vmap_internal_dump(LqrCarver *r)
 {
     LqrVMap *v = lqr_vmap_dump(r);
-    LqrVMapList *n = (LqrVMapList *) calloc(1, sizeof *n), *p;
+    LqrVMapList *n = (LqrVMapList *) calloc(1, sizeof *n);
     if (!v || !n) return LQR_NOMEM;
     n->current = v;
-    if (!r->flushed_vs) r->flushed_vs = n;
-    else { for (p = r->flushed_vs; p->next; p = p->next); p->next = n; }
+    LIST_APPEND(LqrVMapList, r->flushed_vs, n);
     return LQR_OK;
 }
 
@@ -968,7 +963,7 @@ static LqrRetVal group_vmap_load(LqrCarver **rs, int n, const gint *map, int on_
     } else
         ret = hip_ret(rc);
     if (ret == LQR_OK) ret = group_flatten(&g);
-    if (ret == LQR_OK && rs[0]->transposed != orientation) ret = group_transpose(&g);
+    if (ret == LQR_OK && rs[0]->geo.transposed != orientation) ret = group_transpose(&g);
     if (ret == LQR_OK) {
         int k;
         for (k = 0; k < g.nb && ret == LQR_OK; k++) ret = hip_ret(lqrhip_vmap_load(g.b[k], staged));     /* every sub-batch staged ... */
@@ -976,9 +971,8 @@ static LqrRetVal group_vmap_load(LqrCarver **rs, int n, const gint *map, int on_
     }
     if (ret == LQR_OK) {
         FOR_TREE(&g, i, r, {
-            r->max_level = r->level = depth + 1;
-            r->w0 = r->w_start + depth;
-            set_width_one(r, r->w_start);
+            lqr_geom_map_loaded(&r->geo, depth);
+            ro_invalidate(r);
             r->enl_step = 2.0f;
             r->wk_valid = 0;
         });
@@ -1008,50 +1002,36 @@ LqrRetVal lqrx_vmap_load_batch(LqrCarver **carvers, gint n, LqrVMap *vmap)
 }
 
 /* ======================= resize (E10) ==================================== */
+/* one direction: the walk says what comes next (lqr_sched.h), here it is done on the device */
 static LqrRetVal group_resize_dir(Group *g, int w1, int want_transposed)
 {
     LqrCarver *r = g->r[0];
-    int delta, gamma, delta_max, i;
+    LqrWalk walk;
+    LqrWalkStep s;
+    int i;
     const gchar *init_msg = want_transposed ? r->progress->init_height_message : r->progress->init_width_message;
     const gchar *end_msg = want_transposed ? r->progress->end_height_message : r->progress->end_width_message;
 
-    if (r->transposed == want_transposed) {
-        delta = w1 - r->w_start; gamma = w1 - r->w;
-        delta_max = (int) ((r->enl_step - 1) * r->w_start) - 1;
-    } else {
-        delta = w1 - r->h_start; gamma = w1 - r->h;
-        delta_max = (int) ((r->enl_step - 1) * r->h_start) - 1;
-    }
-    if (delta_max < 1) delta_max = 1;
-    if (delta < 0) { delta = -delta; delta_max = delta; }
-
+    lqr_walk_begin(&walk, &r->geo, r->enl_step, w1, want_transposed);
     for (i = 0; i < g->n; i++) {
         LqrCarver *c = g->r[i];
-        c->session_rescale_total = gamma > 0 ? gamma : -gamma;
+        c->session_rescale_total = walk.total;
         c->session_rescale_current = 0;
-        c->session_update_step = (int) MAXI(c->session_rescale_total * c->progress->update_step, 1);
+        c->session_update_step = lqr_sched_update_step(walk.total, c->progress->update_step);
     }
-    if (r->session_rescale_total && r->progress->init) r->progress->init(init_msg);
+    if (walk.total && r->progress->init) r->progress->init(init_msg);
 
-    while (gamma) {
-        int delta0 = MINI(delta, delta_max), new_w;
-        delta -= delta0;
-        if (r->transposed != want_transposed) LQR_CATCH(group_transpose(g));
-        new_w = MINI(w1, r->w_start + delta_max);
-        gamma = w1 - new_w;
-        LQR_CATCH(group_build_maps(g, delta0 + 1));
+    while (lqr_walk_next(&walk, &s)) {
+        if (s.transpose) LQR_CATCH(group_transpose(g));
+        LQR_CATCH(group_build_maps(g, s.depth));
         for (i = 0; i < g->n; i++) {
-            set_width_tree(g->r[i], new_w);
-            g->r[i]->session_rescale_current = g->r[i]->session_rescale_total - (gamma > 0 ? gamma : -gamma);
+            set_width_tree(g->r[i], s.new_w);
+            g->r[i]->session_rescale_current = walk.total - (s.gamma > 0 ? s.gamma : -s.gamma);
             if (g->r[i]->dump_vmaps) LQR_CATCH(lqr_vmap_internal_dump(g->r[i]));
         }
-        if (new_w < w1) {
-            LQR_CATCH(group_flatten(g));
-            delta_max = (int) ((r->enl_step - 1) * r->w_start) - 1;
-            if (delta_max < 1) delta_max = 1;
-        }
+        if (s.flatten) LQR_CATCH(group_flatten(g));
     }
-    if (r->session_rescale_total && r->progress->end) {
+    if (walk.total && r->progress->end) {
         HIP_ALL(g, lqrhip_batch_sync(B));
         r->progress->end(end_msg);
     }
@@ -1063,9 +1043,9 @@ static LqrRetVal group_resize_dir(Group *g, int w1, int want_transposed)
 static int same_config(const LqrCarver *a, const LqrCarver *b)
 {
     LqrCarverList *la = a->attached, *lb = b->attached;
-    if (a->w0 != b->w0 || a->h0 != b->h0 || a->w != b->w || a->h != b->h || a->w_start != b->w_start ||
-        a->h_start != b->h_start || a->level != b->level || a->max_level != b->max_level || a->channels != b->channels ||
-        a->transposed != b->transposed || a->active != b->active || a->delta_x != b->delta_x || a->rigidity != b->rigidity ||
+    if (a->geo.w0 != b->geo.w0 || a->geo.h0 != b->geo.h0 || a->geo.w != b->geo.w || a->geo.h != b->geo.h || a->geo.w_start != b->geo.w_start ||
+        a->geo.h_start != b->geo.h_start || a->geo.level != b->geo.level || a->geo.max_level != b->geo.max_level || a->channels != b->channels ||
+        a->geo.transposed != b->geo.transposed || a->active != b->active || a->delta_x != b->delta_x || a->rigidity != b->rigidity ||
         a->has_bias != b->has_bias || a->has_rigmask != b->has_rigmask || a->nrg_func != b->nrg_func ||
         a->leftright != b->leftright || a->lr_switch_frequency != b->lr_switch_frequency || a->enl_step != b->enl_step ||
         a->resize_order != b->resize_order || a->wk_valid != b->wk_valid || a->col_depth != b->col_depth ||
@@ -1076,43 +1056,19 @@ static int same_config(const LqrCarver *a, const LqrCarver *b)
     return !la && !lb;
 }
 
-/* The supported geometry: a session starts from a frame of at most LQRHIP_MAX_FRAME_WIDTH
- * px in the direction it carves.  Which kernels a wider frame would meet depends on the path it happens to take (the persistent
- * tiled kernels have no such bound, k_dp_sweep behind the band kernels and on the recovery path has), so the rule is decided here,
- * from the sizes alone and before the resize touches the device: the walk below is group_resize_dir's bookkeeping -- the frame the
- * carver has now, and the frame after every flatten of a stepwise enlargement. */
+/* Two refusals, both decided from the sizes alone, before the resize touches the device, by the walk group_resize_dir follows.
+ * The supported geometry: a session starts from a frame of at most LQRHIP_MAX_FRAME_WIDTH px
+ * in the direction it carves.  Which kernels a wider frame would meet depends on the path it happens to take (the persistent tiled
+ * kernels have no such bound, k_dp_sweep behind the band kernels and on the recovery path has), so the rule is decided here. */
 static int frame_refused(const LqrCarver *r, int w1, int want_transposed)
 {
-    const int same = (r->transposed == want_transposed);
-    int ws = same ? r->w_start : r->h_start, wc = same ? r->w : r->h, delta_max;
-    if (w1 == wc) return 0;                             /* nothing to carve in this direction */
-    if (ws > LQRHIP_MAX_FRAME_WIDTH || wc > LQRHIP_MAX_FRAME_WIDTH) return 1;
-    for (;;) {
-        int new_w;
-        delta_max = (int) ((r->enl_step - 1) * ws) - 1;
-        if (delta_max < 1) delta_max = 1;
-        new_w = MINI(w1, ws + delta_max);
-        if (new_w >= w1) return 0;
-        ws = new_w;                                     /* flattened: the next session starts from here */
-        if (ws > LQRHIP_MAX_FRAME_WIDTH) return 1;
-    }
+    return lqr_walk_frame_refused(&r->geo, r->enl_step, w1, want_transposed, LQRHIP_MAX_FRAME_WIDTH);
 }
-
 /* A carver lqr_carver_init has not seen cannot build maps: it serves the sizes the map it was given covers (lqr_vmap_load), in that
- * map's direction, and nothing else.  The walk is group_resize_dir's: what is asked of group_build_maps must lie within max_level,
- * without a transposition and without a second step.  Decided from the sizes alone, before the resize touches anything (lqr_vmap.h 3) */
+ * map's direction, and nothing else (lqr_vmap.h 3) */
 static int inactive_refused(const LqrCarver *r, int w1, int want_transposed)
 {
-    const int same = (r->transposed == want_transposed);
-    int delta, delta_max;
-    if (r->active) return 0;
-    if (w1 == (same ? r->w : r->h)) return 0;           /* nothing to do in this direction */
-    if (!same) return 1;
-    delta = w1 - r->w_start;
-    if (delta < 0) return -delta + 1 > r->max_level;
-    delta_max = (int) ((r->enl_step - 1) * r->w_start) - 1;
-    if (delta_max < 1) delta_max = 1;
-    return delta > delta_max || delta + 1 > r->max_level;
+    return !r->active && lqr_walk_needs_maps(&r->geo, r->enl_step, w1, want_transposed);
 }
 
 static LqrRetVal group_resize(LqrCarver **rs, int n, int w1, int h1)
@@ -1147,7 +1103,7 @@ static LqrRetVal group_resize(LqrCarver **rs, int n, int w1, int h1)
         for (k = 0; k < g.nb; k++) { LqrRetVal rk = hip_ret(lqrhip_batch_sync(g.b[k])); if (ret == LQR_OK) ret = rk; }
     }
     if (ret != LQR_OK) { int k; for (k = 0; k < g.nb; k++) lqrhip_batch_abort(g.b[k]); }      /* nothing of this resize may surface in the next one */
-    FOR_TREE(&g, i, r, { r->ro_valid = 0; r->ro_line = 0; r->ro_x = 0; });
+    FOR_TREE(&g, i, r, ro_invalidate(r));
     {
         T_BEGIN(T_CLOSE);
         group_close(&g);
@@ -1166,10 +1122,10 @@ LqrRetVal lqrx_carver_resize_batch(LqrCarver **carvers, gint n, gint w1, gint h1
     if (same) {
         /* delta_x = 2 .. 4 and rigidity masks (with rigidity) run on the tiled kernels only while the whole group's tiles are
          * co-resident; a larger group would fall to the one-wave-per-image kernels (~30x slower).  The images are
-         * independent, so such a group is carved in consecutive sub-groups that fit (DESIGN.md 4.13). */
+         * independent, so such a group is carved in consecutive sub-groups that fit (DESIGN.md 4.1). */
         const LqrCarver *c = carvers[0];
         if (is_general(c)) {
-            int wmax = c->w_start > c->h_start ? c->w_start : c->h_start, lim;   /* either direction may be carved, shrinking or enlarging */
+            int wmax = c->geo.w_start > c->geo.h_start ? c->geo.w_start : c->geo.h_start, lim;   /* either direction may be carved, shrinking or enlarging */
             if (w1 > wmax) wmax = w1;
             if (h1 > wmax) wmax = h1;
             lim = lqrhip_general_batch_limit_delta(wmax, c->delta_x);
@@ -1192,7 +1148,7 @@ LqrRetVal lqrx_carver_resize_batch(LqrCarver **carvers, gint n, gint w1, gint h1
 /* ======================= readout (E12) =================================== */
 static LqrRetVal fetch_visible(LqrCarver *r)
 {
-    size_t n = (size_t) r->w * r->h * PX_BYTES(r);
+    size_t n = (size_t) r->geo.w * r->geo.h * PX_BYTES(r);
     if (r->ro_valid) return LQR_OK;
     if (!r->ro_image && r->in_buffer && !r->preserve_input && r->in_buffer_len >= n) {     /* the block the image arrived in */
         r->ro_image = r->in_buffer; r->ro_image_len = r->in_buffer_len;
@@ -1204,19 +1160,19 @@ static LqrRetVal fetch_visible(LqrCarver *r)
         if (!r->ro_image) { r->ro_image_len = 0; return LQR_NOMEM; }
         r->ro_image_len = n;
     }
-    HIP_CATCH(lqrhip_read_visible(r->dev, r->w0, r->h0, r->w, r->level, r->ro_image));
-    if ((size_t) r->ro_buffer_len < r->w * PX_BYTES(r)) {
+    HIP_CATCH(lqrhip_read_visible(r->dev, r->geo.w0, r->geo.h0, r->geo.w, r->geo.level, r->ro_image));
+    if ((size_t) r->ro_buffer_len < r->geo.w * PX_BYTES(r)) {
         free(r->ro_buffer);
-        r->ro_buffer = (guchar *) malloc(r->w * PX_BYTES(r));
+        r->ro_buffer = (guchar *) malloc(r->geo.w * PX_BYTES(r));
         if (!r->ro_buffer) return LQR_NOMEM;
-        r->ro_buffer_len = (int) (r->w * PX_BYTES(r));
+        r->ro_buffer_len = (int) (r->geo.w * PX_BYTES(r));
     }
     r->ro_valid = 1;
     return LQR_OK;
 }
 
 void lqr_carver_scan_reset(LqrCarver *r) { r->ro_line = 0; r->ro_x = 0; }
-gboolean lqr_carver_scan_by_row(LqrCarver *r) { return r->transposed ? FALSE : TRUE; }
+gboolean lqr_carver_scan_by_row(LqrCarver *r) { return r->geo.transposed ? FALSE : TRUE; }
 
 /* One packed device->host transfer feeds the whole scan (io_functions.c:155-164
  * calls this once per line); a line is a carver-frame row, i.e. an image column
@@ -1230,8 +1186,8 @@ gboolean lqr_carver_scan_line(LqrCarver *r, gint *n, guchar **rgb)
 /* liblqr's cursor: a line scan starts over at the beginning of the line a pixel scan is in */
 gboolean lqr_carver_scan_line_ext(LqrCarver *r, gint *n, void **rgb)
 {
-    const size_t line = r->w * PX_BYTES(r);
-    if (r->ro_line >= r->h) { r->ro_line = 0; r->ro_x = 0; return FALSE; }
+    const size_t line = r->geo.w * PX_BYTES(r);
+    if (r->ro_line >= r->geo.h) { r->ro_line = 0; r->ro_x = 0; return FALSE; }
     if (fetch_visible(r) != LQR_OK) return FALSE;
     memcpy(r->ro_buffer, r->ro_image + (size_t) r->ro_line * line, line);
     *n = r->ro_line;
@@ -1245,14 +1201,14 @@ gboolean lqr_carver_scan_line_ext(LqrCarver *r, gint *n, void **rgb)
 gboolean lqr_carver_scan_ext(LqrCarver *r, gint *x, gint *y, void **rgb)
 {
     const size_t px = PX_BYTES(r);
-    if (r->ro_x >= r->w) r->ro_x = 0;          /* (never left outside the frame: every reset of ro_line resets it too) */
-    if (r->ro_line >= r->h) { r->ro_line = 0; r->ro_x = 0; return FALSE; }
+    if (r->ro_x >= r->geo.w) r->ro_x = 0;          /* (never left outside the frame: every reset of ro_line resets it too) */
+    if (r->ro_line >= r->geo.h) { r->ro_line = 0; r->ro_x = 0; return FALSE; }
     if (fetch_visible(r) != LQR_OK) return FALSE;
-    *x = r->transposed ? r->ro_line : r->ro_x;
-    *y = r->transposed ? r->ro_x : r->ro_line;
-    memcpy(r->ro_buffer, r->ro_image + ((size_t) r->ro_line * r->w + r->ro_x) * px, px);
+    *x = r->geo.transposed ? r->ro_line : r->ro_x;
+    *y = r->geo.transposed ? r->ro_x : r->ro_line;
+    memcpy(r->ro_buffer, r->ro_image + ((size_t) r->ro_line * r->geo.w + r->ro_x) * px, px);
     *rgb = r->ro_buffer;
-    if (++r->ro_x == r->w) { r->ro_x = 0; r->ro_line++; }
+    if (++r->ro_x == r->geo.w) { r->ro_x = 0; r->ro_line++; }
     return TRUE;
 }
 
@@ -1266,23 +1222,23 @@ LqrRetVal lqrx_carver_read_image(LqrCarver *r, guchar *out)
 {
     int x, y;
     const size_t ch = PX_BYTES(r);     /* bytes per pixel */
-    if (!r->transposed && !r->ro_valid) {      /* straight into the caller's buffer: no second host copy */
-        HIP_CATCH(lqrhip_read_visible(r->dev, r->w0, r->h0, r->w, r->level, out));
+    if (!r->geo.transposed && !r->ro_valid) {      /* straight into the caller's buffer: no second host copy */
+        HIP_CATCH(lqrhip_read_visible(r->dev, r->geo.w0, r->geo.h0, r->geo.w, r->geo.level, out));
         return LQR_OK;
     }
     LQR_CATCH(fetch_visible(r));
-    if (!r->transposed) {
-        memcpy(out, r->ro_image, (size_t) r->w * r->h * ch);
+    if (!r->geo.transposed) {
+        memcpy(out, r->ro_image, (size_t) r->geo.w * r->geo.h * ch);
     } else {
-        for (y = 0; y < r->h; y++)
-            for (x = 0; x < r->w; x++) memcpy(out + ((size_t) x * r->h + y) * ch, r->ro_image + ((size_t) y * r->w + x) * ch, ch);
+        for (y = 0; y < r->geo.h; y++)
+            for (x = 0; x < r->geo.w; x++) memcpy(out + ((size_t) x * r->geo.h + y) * ch, r->ro_image + ((size_t) y * r->geo.w + x) * ch, ch);
     }
     return LQR_OK;
 }
 
 LqrRetVal lqrx_carver_read_image_device(LqrCarver *r, void *device_ptr)
 {
-    HIP_CATCH(lqrhip_read_visible_device(r->dev, r->w0, r->h0, r->w, r->level, device_ptr));
+    HIP_CATCH(lqrhip_read_visible_device(r->dev, r->geo.w0, r->geo.h0, r->geo.w, r->geo.level, device_ptr));
     return LQR_OK;
 }
 
@@ -1297,7 +1253,7 @@ LqrRetVal lqrx_vmap_to_rgba(LqrVMap *v, const gdouble col_start[3], const gdoubl
 /* ======================= reload from device memory ======================= */
 LqrRetVal lqrx_carver_reload_device_batch(LqrCarver **rs, gint n, void *const *device_rgb)
 {
-    int i, x, lo, rc = 0, done = 0;
+    int i, lo, rc = 0, done = 0;
     LqrHipCarver **ds;
     T_BEGIN(T_RELOAD);
     if (n < 1) return LQR_ERROR;
@@ -1320,17 +1276,12 @@ LqrRetVal lqrx_carver_reload_device_batch(LqrCarver **rs, gint n, void *const *d
         lqr_maskq_reset(&r->mq[0]); lqr_maskq_reset(&r->mq[1]);        /* masks are dropped, queued ones too */
         for (v = r->flushed_vs; v; v = vn) { vn = v->next; lqr_vmap_destroy(v->current); free(v); }
         r->flushed_vs = NULL;
-        r->level = r->max_level = 1;
-        r->w = r->w0 = r->w_start = r->img_w;
-        r->h = r->h0 = r->h_start = r->img_h;
-        r->transposed = 0;
+        lqr_geom_reset(&r->geo, r->img_w, r->img_h);
         r->leftright = 0;
         r->has_bias = r->has_rigmask = 0;
         r->wk_valid = 0;
-        r->ro_valid = 0; r->ro_line = 0; r->ro_x = 0;
-        if (r->active)      /* as lqr_carver_init */
-            for (x = -r->delta_x; x <= r->delta_x; x++)
-                r->rigidity_map[x + r->delta_x] = r->rigidity * powf(fabsf((float) x), 1.5f) / r->h;
+        ro_invalidate(r);
+        if (r->active) rigidity_table(r);       /* as lqr_carver_init */
     }
     HIP_CATCH(rc);
     HIP_CATCH(lqrhip_reset_sync());
@@ -1358,56 +1309,45 @@ gint lqrx_guess_new_size(const guchar *mask, gint channels, gint width, gint hei
 }
 
 /* ======================= test hooks ====================================== */
-LqrRetVal lqrx_carver_get_energy(LqrCarver *r, gfloat *buffer)
+/* What every energy read-out does: the carver is brought to the frame seams of `orientation` are carved in, as lqr_carver_resize
+ * brings it there (flattened if it is not at the width of its visibility map, transposed -- and left so -- if it lies the other way),
+ * its energy is built, and the output stage writes it in image orientation.  form 0: the values as they are, 1: normalised, 2: pixels
+ * of depth / image_type; -1: the working plane as it lies, in the carver's frame and without a transposition (the test hook).  A
+ * failure leaves the carver in one of the states this sequence passes through. */
+static LqrRetVal energy_run(LqrCarver *r, void *buffer, int on_device, int orientation, int form, int depth, int image_type)
 {
     Group g;
     LqrHipDpParams p;
     LqrRetVal ret = LQR_OK;
-    if (r->root) return LQR_ERROR;
-    LQR_CATCH(mask_queue_flush(r));
-    LQR_CATCH(group_open(&g, &r, 1));
-    if (r->w != r->w_start - r->max_level + 1) ret = group_flatten(&g);
-    if (ret == LQR_OK && !r->wk_valid) {
-        if ((ret = hip_ret(lqrhip_wk_init(g.b[0], r->max_level != 1 || r->w0 != r->w_start))) == LQR_OK) r->wk_valid = 1;
-    }
-    if (ret == LQR_OK) {
-        dp_params(r, &p);
-        ret = hip_ret(lqrhip_emap_build(g.b[0], &p, r->w, r->h));
-    }
-    if (ret == LQR_OK) ret = hip_ret(lqrhip_read_working(r->dev, r->w, r->h, buffer, NULL, NULL));
-    group_close(&g);
-    return ret;
-}
-
-/* ======================= energy read-outs (lqr_energy.h) ================= */
-/* All five entry points: the carver is brought to the frame seams of `orientation` are carved in, as lqr_carver_resize brings it there
- * (flattened if it is not at the width of its visibility map, transposed -- and left so -- if it lies the other way), its energy is
- * built, and the output stage writes it in image orientation.  form 0: the values as they are, 1: normalised, 2: pixels of depth /
- * image_type.  A failure leaves the carver in one of the states this sequence passes through. */
-static LqrRetVal energy_read(LqrCarver *r, void *buffer, int on_device, int orientation, int form, int depth, int image_type)
-{
-    Group g;
-    LqrHipDpParams p;
-    LqrRetVal ret = LQR_OK;
-    if (!r || !buffer || (orientation != 0 && orientation != 1)) return LQR_ERROR;
-    if (form == 2 && (depth < LQR_COLDEPTH_8I || depth > LQR_COLDEPTH_64F || image_type < LQR_RGB_IMAGE || image_type >= LQR_CUSTOM_IMAGE))
-        return LQR_ERROR;
     if (r->root) return LQR_ERROR;          /* (lqr_energy.h: an attached carver cannot be re-laid alone) */
     LQR_CATCH(mask_queue_flush(r));
     LQR_CATCH(group_open(&g, &r, 1));
-    if (r->w != r->w_start - r->max_level + 1) ret = group_flatten(&g);
-    if (ret == LQR_OK && r->transposed != orientation) ret = group_transpose(&g);
+    if (r->geo.w != r->geo.w_start - r->geo.max_level + 1) ret = group_flatten(&g);
+    if (ret == LQR_OK && form >= 0 && r->geo.transposed != orientation) ret = group_transpose(&g);
     /* (a carver lqr_carver_init has not seen gets its working planes here too, and stays inactive) */
     if (ret == LQR_OK && !r->wk_valid) {
-        if ((ret = hip_ret(lqrhip_wk_init(g.b[0], r->max_level != 1 || r->w0 != r->w_start))) == LQR_OK) r->wk_valid = 1;
+        if ((ret = hip_ret(lqrhip_wk_init(g.b[0], r->geo.max_level != 1 || r->geo.w0 != r->geo.w_start))) == LQR_OK) r->wk_valid = 1;
     }
     if (ret == LQR_OK) {
         dp_params(r, &p);
-        ret = hip_ret(lqrhip_emap_build(g.b[0], &p, r->w, r->h));
+        ret = hip_ret(lqrhip_emap_build(g.b[0], &p, r->geo.w, r->geo.h));
     }
-    if (ret == LQR_OK) ret = hip_ret(lqrhip_energy_out(g.b[0], r->w, r->h, r->transposed, form, depth, image_type, buffer, on_device));
+    if (ret == LQR_OK)
+        ret = hip_ret(form < 0 ? lqrhip_read_working(r->dev, r->geo.w, r->geo.h, (float *) buffer, NULL, NULL)
+                               : lqrhip_energy_out(g.b[0], r->geo.w, r->geo.h, r->geo.transposed, form, depth, image_type, buffer, on_device));
     group_close(&g);
     return ret;
+}
+LqrRetVal lqrx_carver_get_energy(LqrCarver *r, gfloat *buffer) { return energy_run(r, buffer, 0, 0, -1, 0, 0); }
+
+/* ======================= energy read-outs (lqr_energy.h) ================= */
+/* all five entry points, arguments checked */
+static LqrRetVal energy_read(LqrCarver *r, void *buffer, int on_device, int orientation, int form, int depth, int image_type)
+{
+    if (!r || !buffer || (orientation != 0 && orientation != 1)) return LQR_ERROR;
+    if (form == 2 && (depth < LQR_COLDEPTH_8I || depth > LQR_COLDEPTH_64F || image_type < LQR_RGB_IMAGE || image_type >= LQR_CUSTOM_IMAGE))
+        return LQR_ERROR;
+    return energy_run(r, buffer, on_device, orientation, form, depth, image_type);
 }
 LqrRetVal lqr_carver_get_energy(LqrCarver *r, gfloat *buffer, gint orientation) { return energy_read(r, buffer, 0, orientation, 1, 0, 0); }
 LqrRetVal lqr_carver_get_true_energy(LqrCarver *r, gfloat *buffer, gint orientation) { return energy_read(r, buffer, 0, orientation, 0, 0, 0); }
@@ -1427,7 +1367,7 @@ LqrRetVal lqrx_carver_get_energy_image_device(LqrCarver *r, void *device_buffer,
 LqrRetVal lqrx_carver_debug_maps(LqrCarver *r, gfloat *en, gfloat *m, gint *least_dx)
 {
     if (!r->active || !r->wk_valid) return LQR_ERROR;
-    HIP_CATCH(lqrhip_read_working(r->dev, r->w, r->h, en, m, least_dx));
+    HIP_CATCH(lqrhip_read_working(r->dev, r->geo.w, r->geo.h, en, m, least_dx));
     return LQR_OK;
 }
 gint lqrx_carver_debug_width(LqrCarver *r) { return r->dbg_w; }

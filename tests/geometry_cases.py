@@ -124,7 +124,8 @@ def band_form(case, wnew, h):
 
 
 def sessions(case):
-    """liblqr's bookkeeping (host/lqr_carver.c group_resize_dir): the sessions of the case's resize, as dicts fw, fh, seams"""
+    """liblqr's bookkeeping (host/lqr_sched.c lqr_walk_next, which host/lqr_carver.c group_resize_dir follows), restated independently
+    of it -- tests/test_sched.py compares the two without a GPU: the sessions of the case's resize, as dicts fw, fh, seams"""
     w, h, nw, nh = case["w"], case["h"], case["nw"], case["nh"]
     enl = case["kw"].get("enl_step", 150.0) / 100.0
     out = []
@@ -147,7 +148,7 @@ def sessions(case):
 
 
 def seam_steps(case, s):
-    """(w_before, wnew, full_rebuild) of every seam of session s (group_build_vsmap's side-switch rule)"""
+    """(w_before, wnew, full_rebuild) of every seam of session s (the side-switch rule of host/lqr_sched.c lqr_session_seam, restated)"""
     sf = case["kw"].get("switch_freq", 2)
     interval = (s["seams"] - 1) // sf + 1 if sf else 0
     for i in range(s["seams"]):
