@@ -98,6 +98,64 @@ __device__ __forceinline__ void st_right_u32(gu32 *row, int gbase, int pbeg, int
     }
 }
 
+// ---- the en plane while the energy update runs BESIDE the carve (k_carve_u).  Other workgroups of the same launch write the fresh
+// energies of this row to the physical positions [pa, pb] (nrg_interval in the frame after the carve, which starts at org + side;
+// pa > pb: nothing).  The carve leaves them alone.  A 16-byte vector that lies wholly outside the interval and is wholly the carve's is
+// stored as above (`whole` vectors: x in [x0, x1)).  Of the other vectors the carve stores only the elements that are its own AND outside
+// the interval, one dword at a time (en_fix_*: at most 3 per end of the whole vectors, one lane each, loaded before the row's first
+// store and stored after its last) and nothing else -- in particular not the "as loaded" elements of the boundary vector, which may
+// hold an energy that is stale by now.  The vector LOADS still cover the interval, and what they return from there is the old energy
+// or the fresh one; no output outside the interval is made from such an element.  With xmin <= v (nrg_interval starts from the row's
+// own seam pixel) and, unless the interval is empty, xmax >= v - 1:
+//   side 0: pa = org + xmin <= pv, so an output p >= pv outside the interval has p > pb and takes old[p + 1] >= pb + 2;
+//   side 1: pb = org + 1 + xmax >= pv, so an output p = org + 1 + xx outside it has xx < xmin and takes old[org + xx] < pa - 1.
+// Positions left of the seam on side 0 and right of it on side 1 are not written at all.
+__device__ __forceinline__ void st_left_en(gu32 *row, int base, int x0, int pend, int lane, const G32 &g)
+{
+#pragma unroll
+    for (int u = 0; u < CG; u++) {
+        const int x = base + u * 256 + lane * 4;
+        const uint32_t first_next = (u < CG - 1) ? (uint32_t) __builtin_amdgcn_readlane((int) g.a[u < CG - 1 ? u + 1 : CG - 1].x, 0) : 0u;
+        const uint32_t lane63 = (u < CG - 1) ? first_next : g.edge;
+        const uint32_t nx = (uint32_t) __builtin_amdgcn_update_dpp((int) lane63, (int) g.a[u].x, DPP_WAVE_SHL1, 0xf, 0xf, false);
+        if (x >= x0 && x < pend) __builtin_nontemporal_store((u32x4) {g.a[u].y, g.a[u].z, g.a[u].w, nx}, (GLOBAL_AS u32x4 *) (row + x));
+    }
+}
+__device__ __forceinline__ void st_right_en(gu32 *row, int gbase, int x0, int x1, int lane, const G32 &g)
+{
+#pragma unroll
+    for (int u = 0; u < CG; u++) {
+        const int x = gbase + u * 256 + lane * 4;
+        const uint32_t last_prev = (u > 0) ? (uint32_t) __builtin_amdgcn_readlane((int) g.a[u > 0 ? u - 1 : 0].w, 63) : 0u;
+        const uint32_t lane0 = (u > 0) ? last_prev : g.edge;
+        const uint32_t pw = (uint32_t) __builtin_amdgcn_update_dpp((int) lane0, (int) g.a[u].w, DPP_WAVE_SHR1, 0xf, 0xf, false);
+        if (x >= x0 && x < x1) __builtin_nontemporal_store((u32x4) {pw, g.a[u].x, g.a[u].y, g.a[u].z}, (GLOBAL_AS u32x4 *) (row + x));
+    }
+}
+// side 0: the carve's outputs outside the interval are [qa, pend), qa = max(pb + 1, pv); whole vectors from x0 = qa rounded up to a
+// vector; lanes 0 .. 2 take q = qa + lane < x0.  Returns the lane's position (-1: none), its value through `val`
+__device__ __forceinline__ int en_fix_left(const gu32 *row, int pv, int pend, int pb, int lane, int &x0, uint32_t &val)
+{
+    const int qa = max(pb + 1, pv);
+    x0 = (qa + 3) & ~3;
+    const int q = qa + lane;
+    const bool mine = q < x0 && q < pend;
+    val = mine ? row[q + 1] : 0u;
+    return mine ? q : -1;
+}
+// side 1: the carve's outputs outside the interval are (pbeg, lim], lim = min(pa - 1, pv); whole vectors [x0, x1) = the vectors
+// inside; lanes 0 .. 2 take q = pbeg + 1 + lane below x0, lanes 4 .. 6 take q = max(x0, x1) + lane - 4 up to lim
+__device__ __forceinline__ int en_fix_right(const gu32 *row, int pbeg, int pv, int pa, int lane, int &x0, int &x1, uint32_t &val)
+{
+    const int lim = min(pa - 1, pv);
+    x0 = (pbeg + 4) & ~3;
+    x1 = (lim + 1) & ~3;
+    const int q = lane < 4 ? pbeg + 1 + lane : max(x0, x1) + lane - 4;
+    const bool mine = q <= lim && (lane < 4 ? (lane < 3 && q < x0) : lane < 7);
+    val = mine ? row[q - 1] : 0u;
+    return mine ? q : -1;
+}
+
 // one back pointer of the carved frame: the pixel that lands on new frame column xx came from old column
 // xo = xx + right with back pointer dx (parent at old column xo + dx on row y - 1, whose seam pixel was vprev)
 __device__ __forceinline__ int rebase_dx(int dx, int xx, int xo, int vprev, int y)
@@ -195,9 +253,17 @@ __device__ __forceinline__ void st_right_8(gu32 *row32, int gbase, int org, int 
 
 // one row of the carve, by one wave (the body of k_carve's row loop).  c = the
 // PHYSICAL view, org / side = what k_vpath* published for this seam, w = the width before the carve.
-__device__ __forceinline__ void carve_row(const GCarver &c, int org, int side, int y, int w, int stride, int delta, int move_dp, int lane)
+// BESIDE (k_carve_u): the energy role of the same launch writes en[pa .. pb] of this row; h and radius are read for that interval only
+template <bool BESIDE>
+__device__ __forceinline__ void carve_row(const GCarver &c, int org, int side, int y, int w, int stride, int delta, int move_dp, int lane, int h = 0, int radius = 0)
 {
     const int wnew = w - 1;
+    int pa = 0x7fffffff, pb = -1;
+    if (BESIDE) {
+        int xmin, xmax;
+        nrg_interval(c.seam_x, y, h, wnew, radius, xmin, xmax);
+        if (xmin <= xmax) { pa = org + side + xmin; pb = org + side + xmax; }
+    }
     const int v = c.seam_x[y];
     const size_t ro = (size_t) y * stride;
     const int vprev = y > 0 ? c.seam_x[y - 1] : 0;
@@ -209,14 +275,18 @@ __device__ __forceinline__ void carve_row(const GCarver &c, int org, int side, i
         const int pv = org + v, pend = org + wnew;
         int start = (y > 0) ? min(v, vprev - delta) : v;       // where the back pointers' job starts (<= v)
         if (start < 0) start = 0;
+        int x0 = 0, fq = -1;
+        uint32_t fval = 0;
+        if (BESIDE) fq = en_fix_left(en, pv, pend, pb, lane, x0, fval);
         for (int base = (org + (move_dp ? start : v)) & ~3; base < pend; base += CGPX) {
             G32 E, M;
             G8 L;
             ld_left_u32(en, base, pend, lane, E);
             if (move_dp) { ld_left_u32(mm, base, pend, lane, M); ld_left_8(l32, base, pend, lane, L); }
-            st_left_u32(en, base, pv, pend, lane, E);
+            if (BESIDE) st_left_en(en, base, x0, pend, lane, E); else st_left_u32(en, base, pv, pend, lane, E);
             if (move_dp) { st_left_u32(mm, base, pv, pend, lane, M); st_left_8(l32, base, org, start, v, vprev, y, wnew, lane, L); }
         }
+        if (BESIDE && fq >= 0) __builtin_nontemporal_store(fval, en + fq);
         if (rg)
             for (int base = pv & ~3; base < pend; base += CGPX) { G32 R; ld_left_u32(rg, base, pend, lane, R); st_left_u32(rg, base, pv, pend, lane, R); }
     } else {
@@ -224,15 +294,19 @@ __device__ __forceinline__ void carve_row(const GCarver &c, int org, int side, i
         const int end_l = (y > 0) ? min(wnew, max(v, vprev + delta)) : min(wnew, v);      // back pointers' job: new columns [0, end_l)
         const int ptop = org + 1 + max(end_l, 0);
         const int top_u = (pv | 3) + 1;
+        int x0 = 0, x1 = 0, fq = -1;
+        uint32_t fval = 0;
+        if (BESIDE) fq = en_fix_right(en, org, pv, pa, lane, x0, x1, fval);
         for (int top = move_dp ? max(top_u, (ptop + 3) & ~3) : top_u; top > org + 1; top -= CGPX) {
             const int gbase = top - CGPX;
             G32 E, M;
             G8 L;
             ld_right_u32(en, gbase, org, pv, lane, E);
             if (move_dp) { ld_right_u32(mm, gbase, org, pv, lane, M); ld_right_8(l32, gbase, org, ptop, lane, L); }
-            st_right_u32(en, gbase, org, pv, lane, E);
+            if (BESIDE) st_right_en(en, gbase, x0, x1, lane, E); else st_right_u32(en, gbase, org, pv, lane, E);
             if (move_dp) { st_right_u32(mm, gbase, org, pv, lane, M); st_right_8(l32, gbase, org, max(end_l, 0), v, vprev, y, lane, L); }
         }
+        if (BESIDE && fq >= 0) __builtin_nontemporal_store(fval, en + fq);
         if (rg)
             for (int top = top_u; top > org + 1; top -= CGPX) { G32 R; ld_right_u32(rg, top - CGPX, org, pv, lane, R); st_right_u32(rg, top - CGPX, org, pv, lane, R); }
     }
@@ -246,7 +320,7 @@ __global__ __launch_bounds__(256) void k_carve(const DevCarver *cs, int w, int h
     const int org = c.flags[FLAG_ORG_PREV], side = c.flags[FLAG_SIDE];      // published by k_vpath* for this seam
     const int lane = threadIdx.x & 63;
     if (blockIdx.x == 0 && threadIdx.x == 0) c.flags[FLAG_OVF_ROW] = h;       // the band kernels lower / overwrite it when they hand rows over to k_dp_sweep<UPDATE>
-    for (int y = blockIdx.x * 4 + (threadIdx.x >> 6); y < h; y += gridDim.x * 4) carve_row(c, org, side, y, w, stride, delta, move_dp, lane);
+    for (int y = blockIdx.x * 4 + (threadIdx.x >> 6); y < h; y += gridDim.x * 4) carve_row<false>(c, org, side, y, w, stride, delta, move_dp, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -277,7 +351,7 @@ __global__ __launch_bounds__(256) void k_carve_e(const DevCarver *cs, DpK p, int
     const int wn = w - 1;                                        // the frame after the carve
     gf32 *en = c.en + org + side;                                // its logical view (the origin after this seam)
     for (int y = blockIdx.x * 4 + wv; y < h; y += gridDim.x * 4) {
-        carve_row(c, org, side, y, w, stride, p.delta, move_dp, lane);
+        carve_row<false>(c, org, side, y, w, stride, p.delta, move_dp, lane);
         if (wn <= 1) continue;
         // ---- the energy of row y next to the seam (k_emap_update, one row)
         const int g = lane / NT, i = lane - g * NT, t = y - 1 + g;          // lanes 0 .. 35: sample i of row t
@@ -321,8 +395,45 @@ __global__ __launch_bounds__(256) void k_carve_e(const DevCarver *cs, DpK p, int
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_carve_u<NRG>: k_carve and k_emap_update<NRG, 12, false> in ONE launch, side by side, for the groups too large for k_carve_e.  On
+// one stream the energy update used to run alone behind the carve: n * ceil(h / EU_ROWS) one-wave workgroups walking the seam log, the
+// chip almost empty.  It is no true dependency of the carve: it reads seam_x, the seam log and the frozen pix / bias planes, none of
+// which the carve writes, and it writes en[xmin .. xmax] of every row -- which the carve of this kernel neither writes nor uses
+// (st_left_en / st_right_en).  So the two run as separate workgroups of one 1-D grid, each role with its own code:
+//   * workgroups [0, n * ceil(h / EU_ROWS)): the energy role, all images.  FIRST in dispatch order: their log walk is the longest
+//     dependent chain of the launch and has to start with it, not form its tail.  All four waves fill the table of v / 255, wave 0
+//     then runs k_emap_update's body (emap_update_block, lqr_pixel.h: bit-identical energies) and the others leave.  Its en pointer
+//     comes from FLAG_ORG, which the backtrack published before this launch; the carve role writes no origin flag.
+//   * the rest: the carve role, as k_carve's grid (row blocks fastest within an image), one row per wave.
+// The branch is uniform over the workgroup.  delta_x <= 2 (12 samples per row), packed pixels; everything else keeps the two launches.
+// ---------------------------------------------------------------------------
+template <int NRG>
+__global__ __launch_bounds__(256) void k_carve_u(const DevCarver *cs, DpK p, int w, int h, int stride, int move_dp, int k, int epoch, int n)
+{
+    const int eblk = (h + EU_ROWS - 1) / EU_ROWS, ne = n * eblk;
+    if ((int) blockIdx.x < ne) {
+        const int img = blockIdx.x / eblk, blk = blockIdx.x - img * eblk;
+        PixRead<false> rd;
+        rd.setup(threadIdx.x, 256);
+        if (threadIdx.x >= 64) return;
+        const GCarver c = gview(cs[img]);                                    // the frame after this seam
+        emap_update_block<NRG, 12, false, true>(c, rd, p, w - 1, h, stride, k, epoch, blk, threadIdx.x);
+        return;
+    }
+    const int rblk = (h + 3) / 4, cb = blockIdx.x - ne, img = cb / rblk, rb = cb - img * rblk;
+    const GCarver c = gview_phys(cs[img]);
+    const int org = c.flags[FLAG_ORG_PREV], side = c.flags[FLAG_SIDE];      // published by k_vpath* for this seam
+    if (rb == 0 && threadIdx.x == 0) c.flags[FLAG_OVF_ROW] = h;
+    const int y = rb * 4 + (threadIdx.x >> 6);
+    if (y < h) carve_row<true>(c, org, side, y, w, stride, p.delta, move_dp, threadIdx.x & 63, h, p.radius);
+}
+
 // ---- the instantiations the shim launches (lqr_kernels.h lists them)
 // (k_carve is not a template)
+#define INST(N) template __global__ void k_carve_u<N>(const DevCarver *, DpK, int, int, int, int, int, int, int);
+K_CARVE_U_FORMS(INST)
+#undef INST
 #define INST(N) template __global__ void k_carve_e<N>(const DevCarver *, DpK, int, int, int, int, int, int);
 K_CARVE_E_FORMS(INST)
 #undef INST

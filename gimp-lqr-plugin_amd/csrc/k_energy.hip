@@ -206,58 +206,9 @@ template <int NRG, int EU_NT, bool VALUE>
 __global__ __launch_bounds__(64) void k_emap_update(const DevCarver *cs, DpK p, int w, int h, int stride, int k, int epoch)
 {
     const GCarver c = gview(cs[blockIdx.y]);
-    __shared__ double bt[64][EU_NT];
-    __shared__ float bb[64][EU_NT];
-    __shared__ int slo[64];
-    const int tid = threadIdx.x;
     PixRead<VALUE> rd;
-    rd.setup(tid, 64);
-    const int y = blockIdx.x * EU_ROWS + tid - 1;
-    const bool row_ok = (y >= 0 && y < h);
-    constexpr bool luma = (NRG >= 3);
-    int xmin = 0, xmax = -1, lo = 0;
-    if (row_ok) {
-        nrg_interval(c.seam_x, y, h, w, p.radius, xmin, xmax);
-        // samples of this row that rows y-1, y, y+1 will ask for
-        int l = xmin - 1, r = xmax + 1;
-        if (y > 0) { int a, b; nrg_interval(c.seam_x, y - 1, h, w, p.radius, a, b); if (b >= a) { l = min(l, a); r = max(r, b); } }
-        if (y < h - 1) { int a, b; nrg_interval(c.seam_x, y + 1, h, w, p.radius, a, b); if (b >= a) { l = min(l, a); r = max(r, b); } }
-        lo = max(l, 0);
-        int pos[EU_NT];
-#pragma unroll
-        for (int i = 0; i < EU_NT; i++) pos[i] = lo + i;
-        // undo seams k .. epoch, newest first.  The log entries are loaded eight at a time (unconditionally: indices
-        // below `epoch` are clamped and their values replaced by one that moves nothing), so that a row does not wait
-        // for one global load per logged seam
-        const gi32 *lg = c.seam_log + y;
-        for (int j = k; j >= epoch; j -= EU_LOGB) {
-            int v[EU_LOGB];
-#pragma unroll
-            for (int u = 0; u < EU_LOGB; u++) v[u] = lg[(size_t) max(j - u, epoch) * h];
-#pragma unroll
-            for (int u = 0; u < EU_LOGB; u++) {
-                const int vu = (j - u >= epoch) ? v[u] : 0x7fffffff;
-#pragma unroll
-                for (int i = 0; i < EU_NT; i++) pos[i] += (vu <= pos[i]) ? 1 : 0;
-            }
-        }
-        const int wf = w + (k - epoch) + 1;           // width of the frozen frame
-#pragma unroll
-        for (int i = 0; i < EU_NT; i++) {
-            const bool ok = (lo + i <= min(r, w - 1)) && pos[i] < wf;
-            const size_t o = (size_t) y * stride + (ok ? pos[i] : 0);
-            bt[tid][i] = ok ? rd(c.pix, o, p.ch, luma) : 0.0;
-            bb[tid][i] = (ok && c.bias) ? c.bias[o] : 0.0f;
-        }
-    }
-    slo[tid] = lo;
-    __syncthreads();
-    if (!row_ok || tid == 0 || tid == 63) return;
-    for (int x = xmin; x <= xmax; x++) {
-        float e = grad_energy_f<NRG>([&](int xx, int yy) { const int t = tid + (yy - y); return bt[t][xx - slo[t]]; }, x, y, w, h);
-        if (c.bias) e = __fadd_rn(e, __fdiv_rn(bb[tid][x - lo], (float) p.w_start));
-        c.en[(size_t) y * stride + x] = e;
-    }
+    rd.setup(threadIdx.x, 64);
+    emap_update_block<NRG, EU_NT, VALUE, false>(c, rd, p, w, h, stride, k, epoch, blockIdx.x, threadIdx.x);      // (lqr_pixel.h: shared with k_carve_u)
 }
 
 // bring the frozen planes (pix, bias) forward: remove seams [from, to) of the session log from

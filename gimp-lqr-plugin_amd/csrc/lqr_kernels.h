@@ -38,6 +38,8 @@ template <int DELTA> __global__ __launch_bounds__(VPATH_THREADS) void k_vp_solve
 __global__ __launch_bounds__(256) void k_carve(const DevCarver *cs, int w, int h, int stride, int delta, int move_dp);
 #define K_CARVE_E_FORMS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6)      // LqrEnergyFuncBuiltinType
 template <int NRG> __global__ __launch_bounds__(256) void k_carve_e(const DevCarver *cs, DpK p, int w, int h, int stride, int move_dp, int k, int epoch);
+#define K_CARVE_U_FORMS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6)      // LqrEnergyFuncBuiltinType; 12 samples per row (delta_x <= 2), packed pixels
+template <int NRG> __global__ __launch_bounds__(256) void k_carve_u(const DevCarver *cs, DpK p, int w, int h, int stride, int move_dp, int k, int epoch, int n);
 
 // k_band.hip
 #define K_DP_SWEEP_PXT_FORMS(X) X(1) X(2) X(4) X(8) X(16)       // each as <P, false, DP_THREADS>, <P, true, DP_THREADS> and <P, true, 256>

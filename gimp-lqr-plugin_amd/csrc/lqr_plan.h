@@ -58,6 +58,7 @@ struct PlanKnobs {
     int vpath_par_max = 3, vpath_min_rows = 1000;     // (3 x 4K: 58 -> 46 us per seam; 4: equal; 8: slower -- the maps of n images are n times the work)
     int sweep_threads = 256;        // threads of the k_dp_sweep<UPDATE> launch behind the band kernels (256, or 1024 as in rounds 1 - 5)
     int carve_fused = 4;            // k_carve_e (carve + energy update in one launch) for groups up to this many images (0: the two kernels always)
+    int carve_beside = -1;          // k_carve_u (the energy update beside the carve, one launch): -1 automatic (plan_carve_beside); 0 never; 1 wherever a form exists
     int update_mode = -1;           // lqrhip_set_update_mode
     int band_levels = -1;           // k_band_levels: -1 automatic; 0 never; n: n slots per image
     int dpp_limit = -1;             // -1: the occupancy-derived bounds; >= 0: at most that many workgroups for a spinning grid
@@ -100,6 +101,7 @@ struct StepPlan {
     int backtrack = 0;              // LQRHIP_CENSUS_VP_PARALLEL (vp_rows per chunk, vp_chunks chunks), _VPATH1 or _VPATH
     int vp_rows = 0, vp_chunks = 0;
     int carve = 0;                  // LQRHIP_CENSUS_CARVE_E (the energy update fused in) or _CARVE
+    bool energy_beside = false;     // _CARVE only: k_carve_u, the energy update as workgroups of the carve's launch (counted under _CARVE)
     bool catchup = false;           // the frozen planes lag too far: compact them before the energy update
     int eu_nt = 0;                  // k_emap_update's samples per row
     bool full = false;              // dp is a full DP (after a side switch), not an update
@@ -232,6 +234,26 @@ static inline int plan_general_batch_limit(const PlanKnobs &k, const PlanDevice 
     return levels_auto(k, delta, (size_t) std::max(lv, 0), false) && k.band_levels != 0 && tiles_of(w, 64) <= LV_MAX_TILES ? std::max(tiled, lv) : tiled;
 }
 
+// The energy update beside the carve, as workgroups of one launch (k_carve_u, k_carve.hip), for the groups too large for k_carve_e.
+// A form exists for delta_x <= 2 (12 brightness samples per row) on packed pixels while a frame is left to update (wnew > 1); the
+// knob at 1 takes it wherever it exists.  Automatic: batches that have their stream to themselves (what a process with fewer than 8
+// hardware queues runs, plan_streams) of at least CARVE_BESIDE_MIN images.  There the energy update ran alone behind the carve, the
+// chip almost empty; beside the carve its launch and its dispatch leave the step.
+// Measured on one stream (profiles/carve_beside/README.md; 4K, 200 seams, parent / new): per launch k_carve 477.7 + k_emap_update 28.4 us
+// -> k_carve_u 490.7 us (the carve role is 13 us longer with the energy role beside it); 64 images, three alternating runs of 20
+// steps: 196.13 196.28 196.61 -> 194.56 194.34 194.65 ms per step (+0.9 %, the parent's spread 0.25 %).  Mseams*px/s in the order
+// parent, new, new, parent: 8 images 170.6 k 176.4 k 177.6 k 171.9 k, 16: 292.1 303.3 300.8 294.0, 32: 399.9 403.6 407.6 396.6,
+// 48: 485.6 490.4 489.9 482.7 -- every size run gains, so the threshold is the smallest size run, 8; 5 .. 7 were not run and keep
+// the two launches.  Sub-batches on sibling streams (b.shared): 64 images on four streams with 16 hardware queues, parent / rule
+// extended to them, two rounds: 592.3 k / 587.6 k, 583.4 k / 585.6 k -- inside the parent's own spread (the energy update never runs
+// alone there: the sibling streams' kernels fill the chip around it); left out.
+constexpr int CARVE_BESIDE_MIN = 8;
+static inline bool plan_carve_beside(const PlanKnobs &k, const PlanBatch &b, int delta, int wnew)
+{
+    if (k.carve_beside == 0 || delta > 2 || b.value || wnew <= 1) return false;
+    return k.carve_beside > 0 || (!b.shared && b.group() >= (size_t) CARVE_BESIDE_MIN);
+}
+
 // One seam of a lock-step batch: the frame is w wide before it; `lag` seams separate the frozen planes from the frame after it
 static inline StepPlan plan_seam_step(const PlanKnobs &k, const PlanDevice &d, const PlanBatch &b, int delta, bool use_rig, int w, int h, bool full_rebuild, int lag)
 {
@@ -254,6 +276,7 @@ static inline StepPlan plan_seam_step(const PlanKnobs &k, const PlanDevice &d, c
     // a row refreshes that row's energies; one dependent launch less per seam.  delta_x <= 2 (12 brightness samples per row);
     // value-plane carvers: the two kernels
     s.carve = delta <= 2 && b.group() <= (size_t) k.carve_fused && wnew > 1 && !b.value ? LQRHIP_CENSUS_CARVE_E : LQRHIP_CENSUS_CARVE;
+    s.energy_beside = s.carve == LQRHIP_CENSUS_CARVE && plan_carve_beside(k, b, delta, wnew);
     s.catchup = lag > frozen_lag(b.images);
     s.eu_nt = eu_samples(delta);
     if (wnew <= 1) return s;

@@ -1094,6 +1094,14 @@ static int launch_dp_tiled(LqrHipBatch *b, const DpK &k, int w, int h, int lr)
 extern "C" void lqrhip_set_vpath_mode(int mode, int par_max) { g_knobs.vpath_mode = mode; if (par_max > 0) g_knobs.vpath_par_max = par_max; }
 extern "C" void lqrhip_set_sweep_threads(int n) { g_knobs.sweep_threads = n == 256 ? 256 : DP_THREADS; }
 extern "C" void lqrhip_set_carve_fused(int max_images) { g_knobs.carve_fused = max_images == 1 ? 4 : max_images < 0 ? 0 : max_images; }
+extern "C" void lqrhip_set_carve_beside(int mode) { g_knobs.carve_beside = mode < 0 ? -1 : mode ? 1 : 0; }
+static unsigned long long g_carve_beside_launches;          // k_carve_u launches (they are counted under LQRHIP_CENSUS_CARVE as well)
+extern "C" unsigned long long lqrhip_carve_beside_launches(int reset)
+{
+    const unsigned long long v = g_carve_beside_launches;
+    if (reset) g_carve_beside_launches = 0;
+    return v;
+}
 extern "C" void lqrhip_set_update_mode(int mode) { g_knobs.update_mode = mode; }
 extern "C" void lqrhip_set_dp_persistent_px(int px) { g_knobs.dpp_px = (px == 2 || px == 3 || px == 4) ? px : 0; }
 // (0 sends every full DP to k_dp_tile and every incremental update to a band kernel)
@@ -1410,6 +1418,18 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
         if (!with_listed(K_CARVE_E_FORMS, nrg_index(p->nrg_func), [&](auto nrg) {
                 hipLaunchKernelGGL((k_carve_e<nrg>), dim3((h + 3) / 4, n), dim3(256), 0, b->stream, b->d_desc, k, w, h, stride, move_dp, log_index, epoch);
             })) return no_form("k_carve_e");
+    } else if (s.energy_beside) {
+        // k_carve_u: the energy update's workgroups first, then the carve's, in one 1-D grid (k_carve.hip).  The same algorithmic bytes as
+        // k_carve's; "emap_update" has no launch on this path
+        if ((rc = frozen_within_lag())) return rc;      // (needs the seam log only: before the carve)
+        const int epoch = c0->frozen_epoch;
+        ProfScope ps("carve", b->stream, 4.0 * (double) w * h * n);
+        CENSUS(LQRHIP_CENSUS_CARVE);
+        g_carve_beside_launches++;
+        const unsigned grid = n * (unsigned) ((h + EU_ROWS - 1) / EU_ROWS) + n * (unsigned) ((h + 3) / 4);
+        if (!with_listed(K_CARVE_U_FORMS, nrg_index(p->nrg_func), [&](auto nrg) {
+                hipLaunchKernelGGL((k_carve_u<nrg>), dim3(grid), dim3(256), 0, b->stream, b->d_desc, k, w, h, stride, move_dp, log_index, epoch, (int) n);
+            })) return no_form("k_carve_u");
     } else {
         // algorithmic bytes of one carve launch: read + write of one 4-byte
         // plane over the half of each row right of the seam = 8 B * w*h/2 per image
@@ -1423,7 +1443,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
         HIPCK(hipGetLastError());
         return 0;
     }
-    if (!fuse_e) {
+    if (!fuse_e && !s.energy_beside) {
         ProfScope ps("emap_update", b->stream, 0);
         if ((rc = frozen_within_lag())) return rc;
         const int epoch = c0->frozen_epoch;

@@ -293,6 +293,12 @@ void lqrhip_set_sweep_threads(int n);
 /* Test hook: the largest group that runs the carve and the energy update as one launch (k_carve_e, delta_x <= 2): 0 = never, 1 = the
  * default (4), n = groups up to n images */
 void lqrhip_set_carve_fused(int max_images);
+/* Test hook: the energy update as workgroups of the carve's launch (k_carve_u, delta_x <= 2, packed pixels, groups too large for
+ * k_carve_e): -1 = automatic (groups that have their stream to themselves, from the size lqr_plan.h names), 0 = never (k_carve, then
+ * k_emap_update), 1 = wherever a form exists.  The launch is counted under LQRHIP_CENSUS_CARVE either way;
+ * lqrhip_carve_beside_launches returns how many of them were combined launches since the last reset */
+void lqrhip_set_carve_beside(int mode);
+unsigned long long lqrhip_carve_beside_launches(int reset);
 /* E7 form: -1 = the parallel two-kernel backtrack (k_vp_maps / k_vp_solve) for groups of up to par_max images (default 3; 0 keeps the
  * current value) of 1000 rows and more, the one-wave walk k_vpath1 otherwise; 0 = k_vpath1 always; 1 = the parallel form
  * always (delta_x 1 .. 4) */
