@@ -2,6 +2,7 @@
 // (gfx950 / CDNA4, wave64; see lqr_common.h for the file map and DESIGN.md section 4 for the measurements)
 #include "lqr_common.h"
 #include "lqr_kernels.h"
+#include "lqr_walk.h"
 
 // ---------------------------------------------------------------------------
 // E7 build_vpath: argmin of the last row of m with liblqr's tie rule, then the
@@ -13,58 +14,8 @@
 // scalar ops -- no memory or LDS on the dependency chain.  The next chunk starts
 // within +-R*delta of this chunk's start column, so its (256-wide) window can be
 // loaded into a second register set before this chunk's chase has finished.
+// (row_argmin, the pick, and vpath1_walk, the chase of k_vpath1, are in lqr_walk.h: the walk role of k_carve_v runs them too)
 // ---------------------------------------------------------------------------
-// argmin of row `mrow` (w floats) over a VPATH_THREADS-thread block with liblqr's tie rule: leftmost (lr = 0) / rightmost
-// (lr = 1) of equal minima; returns (to every thread) the column, or -1 if no candidate beat liblqr's start value 2^29.
-// A thread takes 16 B at a time (4 loads in flight per thread, all issued before the first compare: the row is one
-// memory round trip, not fifteen), keeps its own ascending scan, then the block reduces on (value, index) pairs: within
-// a wave by DPP-free shuffles, across the four waves through LDS.
-__device__ __forceinline__ int row_argmin(const gf32 *mrow, int w, int lr, float *s_val, int *s_idx)
-{
-    const int tid = threadIdx.x;
-    const float INF = __int_as_float(0x7f800000);
-    float bv = INF;
-    int bi = -1;
-    for (int base = 0; base < w; base += 16 * VPATH_THREADS) {
-        f32x4 v[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int x = base + 4 * (tid + VPATH_THREADS * i);
-            // whole vectors only where they are inside the row (the planes have >= 16 floats of padding, but not initialised)
-            if (x + 3 < w) v[i] = *(const GLOBAL_AS f32x4 *) (mrow + x);
-            else { v[i] = (f32x4) {INF, INF, INF, INF}; for (int j = 0; j < 4; j++) if (x + j < w) v[i][j] = mrow[x + j]; }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int x = base + 4 * (tid + VPATH_THREADS * i) + j;
-                const float f = v[i][j];
-                if (x < w && (f < bv || (f == bv && lr))) { bv = f; bi = x; }
-            }
-    }
-    auto better = [&](float v2, int i2, float v1, int i1) {        // does (v2, i2) replace (v1, i1)?
-        if (i2 < 0) return false;
-        if (i1 < 0) return true;
-        if (v2 < v1) return true;
-        if (v2 > v1) return false;
-        return lr ? (i2 > i1) : (i2 < i1);
-    };
-    for (int o = 32; o > 0; o >>= 1) {
-        const float v2 = __shfl_xor(bv, o);
-        const int i2 = __shfl_xor(bi, o);
-        if (better(v2, i2, bv, bi)) { bv = v2; bi = i2; }
-    }
-    if ((tid & 63) == 0) { s_val[tid >> 6] = bv; s_idx[tid >> 6] = bi; }
-    __syncthreads();
-    bv = s_val[0]; bi = s_idx[0];
-#pragma unroll
-    for (int k = 1; k < VPATH_THREADS / 64; k++) if (better(s_val[k], s_idx[k], bv, bi)) { bv = s_val[k]; bi = s_idx[k]; }
-    // liblqr starts from m = 2^29: a candidate must beat it (or tie it when lr == 1)
-    const float lim = 536870912.0f;
-    const bool ok = (bi >= 0) && (bv < lim || (bv == lim && lr));
-    return ok ? bi : -1;
-}
 
 // Which side of the seam the carve moves (wave 0 of k_vpath*, after the backtrack): the part right of the
 // seam holds sum(w - 1 - x), the part left of it sum(x) elements over the rows; the shorter one moves, and
@@ -90,6 +41,12 @@ extern "C" int lqrhip_moved_bytes(unsigned long long *out, int reset)
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_moved_bytes), sizeof(unsigned long long)) != hipSuccess) return -1;
     if (reset) { unsigned long long z = 0; (void) hipMemcpyToSymbol(HIP_SYMBOL(g_moved_bytes), &z, sizeof z); }
     return 0;
+}
+// the counter's device address, for the walk role of k_carve_v (another translation unit: it gets the address as an argument)
+unsigned long long *lqr_moved_bytes_dev(void)
+{
+    void *p = nullptr;
+    return hipGetSymbolAddress(&p, HIP_SYMBOL(g_moved_bytes)) == hipSuccess ? (unsigned long long *) p : nullptr;
 }
 
 __global__ __launch_bounds__(VPATH_THREADS) void k_vpath(const DevCarver *cs, int w, int h, int stride, int lr, int delta,
@@ -179,22 +136,6 @@ __global__ __launch_bounds__(VPATH_THREADS) void k_vpath(const DevCarver *cs, in
 // No LEAST_INVALID test: the carve marks a back pointer invalid only next to the seam, inside the interval
 // every form of update_mmap recomputes before the next backtrack, so none survives to this point.
 // ---------------------------------------------------------------------------
-// rows per chunk by delta_x: the path drifts up to ROWS * delta_x columns inside a chunk and must stay within lanes 4 .. 60 of the 64
-// spread around its start (<= 28), and the window loaded VP1_AHEAD chunks ahead must still hold those 64 columns
-constexpr int vp1_rows(int delta) { return delta == 1 ? 28 : delta == 2 ? 12 : delta == 3 ? 8 : 4; }      // (delta_x 4 .. 7: 4 rows)
-#define VP1_AHEAD 3
-template <int r>
-__device__ __forceinline__ void vp1_step(const int e, int &o, int &path)
-{
-    asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(path) : "s"(o), "n"(r));      // lane r <- window offset at row y_top - r
-    o += __builtin_amdgcn_readlane(e, o);
-}
-template <int N, int... Rs>
-__device__ __forceinline__ void vp1_chase(const int (&e)[N], int &o, int &path, std::integer_sequence<int, Rs...>)
-{
-    (vp1_step<Rs>(e[Rs], o, path), ...);
-}
-
 template <int DELTA>
 __global__ __launch_bounds__(VPATH_THREADS) void k_vpath1(const DevCarver *cs, int w, int h, int stride, int lr, int log_index, int moved_unit)
 {
@@ -211,75 +152,16 @@ __global__ __launch_bounds__(VPATH_THREADS) void k_vpath1(const DevCarver *cs, i
     if (tid >= 64) return;                       // the chase is one wave
     int x = __builtin_amdgcn_readfirstlane(max(xmin, 0));
 
-    // ---- backtrack
+    // ---- backtrack (vpath1_walk.inc)
     const int lane = tid;
     gi32 *seam = c.seam_x;
     gi32 *logp = c.seam_log + (size_t) log_index * h;
-    constexpr int R = VP1_ROWS, NB = VP1_AHEAD + 1, RL = VP1_ROWS / 4;      // RL loads per chunk, four rows each
-    // window [base, base + 256) with base in [cx - 135, cx - 120]: the 64 columns around a start column that has moved up to
-    // 88 either way since the load are inside
-    static_assert(VP1_ROWS % 4 == 0 && VP1_ROWS * DELTA <= 28 && VP1_AHEAD * VP1_ROWS * DELTA + 32 <= 120, "window margin");
-    u32x4 regs[NB][RL];                          // ring of packed windows: chunk k lives in regs[k % NB]
-    int xa[NB];                                  // their base columns
-    auto window_base = [&](int cx) { return (cx - 120) & ~15; };     // multiple of 16: a lane's 16 columns never straddle column 0
-    // Nothing is predicated (a select per load cost more instructions than the chase itself): columns outside
-    // the plane are clamped into it -- the path never goes there -- and rows above row 1 re-read row 1; the steps
-    // taken on those are discarded (see run_chunk).  Uniform row base + 32-bit lane offset: one VALU per load.
-    auto load_chunk = [&](int b, int y_top, int cx) {
-        const int base = window_base(cx);
-        xa[b] = base;
-        // lanes 16s .. 16s + 15: row y_top - 4q - s, 16 columns per lane
-        const int voff = min(max(base + 16 * (lane & 15), 0), stride - 16);
-        const int rsub = (lane >> 4) * stride;
-#pragma unroll
-        for (int q = 0; q < RL; q++) {
-            const int row = max((y_top - 4 * q) * stride - rsub, stride);          // rows above row 1 re-read row 1
-            regs[b][q] = *(const GLOBAL_AS u32x4 *) (c.least + (unsigned) (row + voff));
-        }
-    };
-    // one chunk: spread the 64 columns around the start column out over the lanes, chase, record
     int acc = 0;
-    auto run_chunk = [&](int b, int y_top) {
-        const int relbase = x - 32 - xa[b];                  // window column of lane 0's column
-        int e[R];
-        // through LDS: what the loads hold lane by lane IS row-major [row][256 columns]; same wave writes and reads, LDS
-        // operations of a wave execute in order
-#pragma unroll
-        for (int q = 0; q < RL; q++) *(u32x4 *) (s_win + q * 1024 + lane * 16) = regs[b][q];
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int r = 0; r < R; r++) e[r] = s_win[r * 256 + relbase + lane];
-        // two-row displacements of every column (the path stays within lanes 4 .. 60, so the wrap-around of the
-        // outermost lanes' neighbours never matters)
-        int e2[R / 2];
-#pragma unroll
-        for (int k = 0; k < R / 2; k++) e2[k] = e[2 * k] + __builtin_amdgcn_ds_bpermute((lane + e[2 * k]) << 2, e[2 * k + 1]);
-        int o = 32, path = 0;
-        vp1_chase<R / 2>(e2, o, path, std::make_integer_sequence<int, R / 2>{});          // lane k <- window offset at row y_top - 2k
-        // the odd rows, all at once: lane k looks its even row's displacement up at the column it stands on
-        const int odd = path + s_win[min(lane, R / 2 - 1) * 512 + relbase + path];
-        __builtin_amdgcn_wave_barrier();
-        const int pe = path + x - 32, po = odd + x - 32;     // columns at rows y_top - 2k and y_top - 2k - 1
-        const int nrows = min(R, y_top);
-        if (2 * lane < nrows) { seam[y_top - 2 * lane] = pe; logp[y_top - 2 * lane] = pe; acc += pe; }
+#define VP1_RECORD(y_top, nrows, pe, po) \
+        if (2 * lane < nrows) { seam[y_top - 2 * lane] = pe; logp[y_top - 2 * lane] = pe; acc += pe; } \
         if (2 * lane + 1 < nrows) { seam[y_top - 2 * lane - 1] = po; logp[y_top - 2 * lane - 1] = po; acc += po; }
-        // the column after `nrows` steps: the last chunk may hold fewer real rows than R (the rest re-read row 1)
-        x = (nrows == R) ? x + o - 32 : __builtin_amdgcn_readlane((nrows & 1) ? po : pe, nrows >> 1);
-    };
-    int y_top = h - 1;
-    // chunks are issued VP1_AHEAD ahead; the first ones all around the argmin
-#pragma unroll
-    for (int k = 0; k < VP1_AHEAD; k++) load_chunk(k, y_top - k * R, x);
-    while (true) {
-#pragma unroll
-        for (int k = 0; k < NB; k++) {
-            load_chunk((k + VP1_AHEAD) % NB, y_top - VP1_AHEAD * R, x);      // in flight during this and the next two chases
-            run_chunk(k, y_top);
-            y_top -= R;
-            if (y_top < 1) break;
-        }
-        if (y_top < 1) break;
-    }
+#include "vpath1_walk.inc"
+#undef VP1_RECORD
     if (lane == 0) { seam[0] = x; logp[0] = x; acc += x; }
     publish_side(c, org, acc, w, h, lane, moved_unit);
 }

@@ -2,6 +2,7 @@
 // (gfx950 / CDNA4, wave64; see lqr_common.h for the file map and DESIGN.md section 4 for the measurements)
 #include "lqr_common.h"
 #include "lqr_kernels.h"
+#include "lqr_walk.h"
 
 // ---------------------------------------------------------------------------
 // E8 carve: remove the seam from every carved plane (en, m, back pointers, rigidity mask), in place, one
@@ -253,20 +254,21 @@ __device__ __forceinline__ void st_right_8(gu32 *row32, int gbase, int org, int 
 
 // one row of the carve, by one wave (the body of k_carve's row loop).  c = the
 // PHYSICAL view, org / side = what k_vpath* published for this seam, w = the width before the carve.
-// BESIDE (k_carve_u): the energy role of the same launch writes en[pa .. pb] of this row; h and radius are read for that interval only
-template <bool BESIDE>
-__device__ __forceinline__ void carve_row(const GCarver &c, int org, int side, int y, int w, int stride, int delta, int move_dp, int lane, int h = 0, int radius = 0)
+// BESIDE (k_carve_u, k_carve_v): the energy role of the same launch writes en[pa .. pb] of this row; h and radius are read for that interval only
+// SR (lqr_common.h): how seam_x is read -- SeamLive where the walk role of the same launch writes it (k_carve_v)
+template <bool BESIDE, class SR = SeamPlain>
+__device__ __forceinline__ void carve_row(const GCarver &c, int org, int side, int y, int w, int stride, int delta, int move_dp, int lane, int h = 0, int radius = 0, SR sr = SR())
 {
     const int wnew = w - 1;
     int pa = 0x7fffffff, pb = -1;
     if (BESIDE) {
         int xmin, xmax;
-        nrg_interval(c.seam_x, y, h, wnew, radius, xmin, xmax);
+        nrg_interval(c.seam_x, y, h, wnew, radius, xmin, xmax, sr);
         if (xmin <= xmax) { pa = org + side + xmin; pb = org + side + xmax; }
     }
-    const int v = c.seam_x[y];
+    const int v = sr(c.seam_x + y);
     const size_t ro = (size_t) y * stride;
-    const int vprev = y > 0 ? c.seam_x[y - 1] : 0;
+    const int vprev = y > 0 ? sr(c.seam_x + (y - 1)) : 0;
     gu32 *en = (gu32 *) (c.en + ro), *mm = (gu32 *) (c.m + ro), *l32 = (gu32 *) (c.least + ro);
     gu32 *rg = c.rig ? (gu32 *) (c.rig + ro) : (gu32 *) nullptr;
     // pix and bias are NOT moved: they stay in the frame of `frozen epoch` and the energy
@@ -429,10 +431,176 @@ __global__ __launch_bounds__(256) void k_carve_u(const DevCarver *cs, DpK p, int
     if (y < h) carve_row<true>(c, org, side, y, w, stride, p.delta, move_dp, threadIdx.x & 63, h, p.radius);
 }
 
+// ---------------------------------------------------------------------------
+// k_carve_v<NRG, DELTA>: k_vpath1, k_carve and k_emap_update<NRG, 12, false> in ONE launch.  On one stream the backtrack ran alone in
+// front of the carve: one chasing wave per image for 59 us per 4K seam, the chip otherwise empty.  The carve depends on it only row
+// by row (carve_row reads seam_x[y] and seam_x[y - 1], nrg_interval `radius` rows either way) plus one bit, the side -- and the side,
+// decided today from the whole path's sum(x), is often fixed long before the walk ends: seams are delta_x-connected, so the rows to
+// come lie in a cone (bb_side_bound, lqr_beside.h).  Three roles in one 1-D grid, the branch uniform over the workgroup:
+//   * workgroups [0, n): the WALK, one per image, first in dispatch order.  row_argmin on 256 threads; then wave 0 chases (vpath1_walk
+//     with BB_WALK_ROWS-row chunks for either delta_x: k_vpath1's 28-row chunks need 171 VGPRs) and leaves every chunk's columns in LDS
+//     (s_path, then s_lo = the lowest row found: a wave's LDS operations execute in order); wave 1 PUBLISHES what it finds there, so
+//     that no store acknowledgement and no atomic's round trip is on the chase: it writes the rows to seam_x and the session log
+//     (write-through), waits for the acknowledgements, evaluates the bound on the sum so far -- once decided it writes the flags
+//     exactly as publish_side does -- and pushes the entries whose inputs are final now (bb_first_quad / bb_first_eblk; an image that
+//     decides late pushes its backlog at once): one atomic add on the list's tail reserves the slots, write-through stores fill
+//     them.  Every image pushes ceil(h / 4) carve and ceil(h / EU_ROWS) energy entries in all.  Neither wave waits for anything
+//     outside its workgroup.
+//   * the rest, n * (ceil(h / 4) + ceil(h / EU_ROWS)) CONSUMERS: workgroup b polls entry b - n with one lane (agent-scope load,
+//     bounded spin, DEVERR_TILE_TIMEOUT as in the other spinning kernels: the session is then redone on the kernels without spins),
+//     then is the carve of the entry's four rows (carve_row<true>) or the energy update of its block (emap_update_block), with
+//     origin and side from the entry.  Dispatch order is consumption order, so a consumer only ever waits for an entry some walk
+//     -- resident since before it -- will push.
+// Every read of the CURRENT seam by a consumer (seam_x; log entry k) is an agent-scope load (SeamLive): an XCD's L2 may hold a line
+// of it fetched earlier in the launch.  Tags carry the launch (bb_tag): the list is never cleared; of the two tail words a launch
+// counts on the one of its tag's parity and image 0's walk clears the other for the next launch.
+// Same seams, planes, flags and g_moved_bytes as the separate launches by construction; tests/test_backtrack_beside_gpu.py compares.
+// ---------------------------------------------------------------------------
+static_assert(BB_EU_ROWS == EU_ROWS, "lqr_beside.h restates EU_ROWS");
+typedef GLOBAL_AS unsigned long long gu64;
+#ifdef LQR_TIMING
+__device__ unsigned long long g_walk_cycles[2];       // image 0's walk role, wall-clock ticks (s_memrealtime, 100 MHz): [0] the chase, [1] until the last entry is pushed
+extern "C" int lqrhip_walk_timing(unsigned long long *out) { (void) hipDeviceSynchronize(); return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_walk_cycles), sizeof(unsigned long long) * 2) == hipSuccess ? 0 : -1; }
+#endif
+__device__ __forceinline__ void st_wt(gi32 *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }      // write-through
+
+template <int NRG, int DELTA>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_carve_v(const DevCarver *cs, DpK p, int w, int h, int stride, int lr, int move_dp, int k, int epoch, int n,
+                                                 int moved_unit, unsigned tag, unsigned long long *list, unsigned long long *moved_bytes, int *dev_err)
+{
+    const int eblk = bb_energy_entries(h), rblk = bb_carve_entries(h);
+    const unsigned total = (unsigned) n * (unsigned) (eblk + rblk);
+    gu64 *entries = (gu64 *) list + BB_LIST_HEAD;
+    const int tid = threadIdx.x;
+    if ((int) blockIdx.x < n) {
+        // ---- the walk role
+        __shared__ float s_val[VPATH_THREADS / 64];
+        __shared__ int s_idx[VPATH_THREADS / 64];
+        __shared__ int s_path[BB_MAX_ROWS];          // the seam's column on every row found so far (h <= BB_MAX_ROWS: lqr_plan.h)
+        __shared__ int s_lo;                         // the lowest of them
+        __shared__ __attribute__((aligned(16))) int8_t s_win[BB_WALK_ROWS * 256];      // the chase's current chunk (vpath1_walk.inc)
+        const int img = blockIdx.x;
+        const GCarver c = gview(cs[img]);
+        const int org = c.flags[FLAG_ORG];           // read before the publishing wave writes the next one
+        if (tid == 0) {
+            s_lo = h;
+            if (img == 0) __hip_atomic_store((gu64 *) list + ((tag + 1) & 1), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // the next launch's tail
+        }
+        const int xmin = row_argmin(c.m + (size_t) (h - 1) * stride, w, lr, s_val, s_idx);       // (a barrier inside: s_lo is set)
+        if (tid >= 128) return;
+        const int lane = tid & 63;
+#ifdef LQR_TIMING
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+#endif
+        if (tid < 64) {
+            // wave 0: the chase.  Rows go to LDS; the publishing wave takes them from there
+            int x = __builtin_amdgcn_readfirstlane(max(xmin, 0));
+            __builtin_amdgcn_s_setprio(3);
+            constexpr int VP1_ROWS = BB_WALK_ROWS;
+#define VP1_RECORD(y_top, nrows, pe, po) \
+            if (2 * lane < nrows) LDS_FLAG(s_path[y_top - 2 * lane]) = pe; \
+            if (2 * lane + 1 < nrows) LDS_FLAG(s_path[y_top - 2 * lane - 1]) = po; \
+            LDS_FLAG(s_lo) = y_top - nrows + 1;
+#include "vpath1_walk.inc"
+#undef VP1_RECORD
+            LDS_FLAG(s_path[0]) = x;
+            LDS_FLAG(s_lo) = 0;
+#ifdef LQR_TIMING
+            if (img == 0 && lane == 0) g_walk_cycles[0] = __builtin_amdgcn_s_memrealtime() - t0;
+#endif
+            return;
+        }
+        // wave 1: publish
+        gi32 *seam = c.seam_x, *logp = c.seam_log + (size_t) k * h;
+        gu64 *tail = (gu64 *) list + (tag & 1);
+        int done = h, acc = 0, side = -1, next_q = rblk - 1, next_e = eblk - 1;
+        for (unsigned spins = 0; done > 0;) {
+            const int lo = __builtin_amdgcn_readfirstlane(LDS_FLAG(s_lo));
+            if (lo >= done) {
+                __builtin_amdgcn_s_sleep(2);
+                if (++spins > (1u << 24)) { if (lane == 0) dev_fail(dev_err, DEVERR_TILE_TIMEOUT); return; }      // (the chase waits for nothing but memory)
+                continue;
+            }
+            for (int y = done - 1 - lane; y >= lo; y -= 64) { const int v = LDS_FLAG(s_path[y]); st_wt(seam + y, v); st_wt(logp + y, v); acc += v; }
+            const int xlo = __builtin_amdgcn_readfirstlane(LDS_FLAG(s_path[lo]));
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the rows have arrived before an entry says so
+            done = lo;
+            if (side < 0) {
+                int S = acc;
+                for (int o = 32; o > 0; o >>= 1) S += __shfl_xor(S, o);
+                side = bb_side_bound(S, xlo, lo, DELTA, w, h);        // (lo = 0: the rule itself)
+                if (side >= 0 && lane == 0) { c.flags[FLAG_ORG_PREV] = org; c.flags[FLAG_SIDE] = side; c.flags[FLAG_ORG] = org + side; c.flags[FLAG_OVF_ROW] = h; }
+            }
+            if (side < 0) continue;
+            const int e0 = bb_first_eblk(lo, p.radius), q0 = bb_first_quad(lo, p.radius);
+            const int ne = max(next_e - e0 + 1, 0), nq = max(next_q - q0 + 1, 0), cnt = ne + nq;
+            if (cnt == 0) continue;
+            unsigned base = 0;
+            if (lane == 0) base = (unsigned) __hip_atomic_fetch_add(tail, (unsigned long long) cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            base = (unsigned) __builtin_amdgcn_readfirstlane((int) base);
+            for (int i = lane; i < cnt; i += 64) {
+                const bool en = i < ne;
+                const unsigned slot = base + (unsigned) i;
+                if (slot < total)        // (always, while every image pushes its count: never a store past the list)
+                    __hip_atomic_store(entries + slot, bb_pack(tag, en ? 1 : 0, img, en ? next_e - i : next_q - (i - ne), side, org), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            next_e -= ne; next_q -= nq;
+        }
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        if (lane == 0) {
+            const long long all = (long long) h * (w - 1);
+            atomicAdd(moved_bytes, (unsigned long long) (side ? (long long) acc : all - acc) * (unsigned long long) moved_unit);
+#ifdef LQR_TIMING
+            if (img == 0) g_walk_cycles[1] = __builtin_amdgcn_s_memrealtime() - t0;
+#endif
+        }
+        return;
+    }
+    // ---- a consumer: wait for the entry of this workgroup's place in the dispatch order
+    __shared__ unsigned long long s_entry;
+    if (tid == 0) {
+        gu64 *src = entries + (blockIdx.x - (unsigned) n);
+        unsigned long long e = 0;
+        for (unsigned sp = 0;;) {
+            e = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((unsigned) (e >> BB_TAG_SHIFT) == tag) break;
+            e = 0;
+            if (sp < 16) __builtin_amdgcn_s_sleep(4); else __builtin_amdgcn_s_sleep(32);
+            ++sp;
+            if ((sp & 255) == 0 && dev_failed(dev_err)) break;
+            if (sp > (1u << 18)) { dev_fail(dev_err, DEVERR_TILE_TIMEOUT); break; }
+        }
+        s_entry = e;
+    }
+    __syncthreads();
+    // (uniform, and said so: image, rows, origin and side stay in scalar registers, as where they come from the block index and the flags)
+    const unsigned long long ew = ((unsigned long long) (unsigned) __builtin_amdgcn_readfirstlane((int) (s_entry >> 32)) << 32) | (unsigned) __builtin_amdgcn_readfirstlane((int) s_entry);
+    if (ew == 0) return;                             // timed out: the host finds the code
+    const BbEntry e = bb_unpack(ew);
+    if (e.image >= n) return;
+    if (e.energy) {
+        PixRead<false> rd;
+        rd.setup(tid, 256);
+        if (tid >= 64 || e.index >= eblk) return;
+        GCarver c = gview_phys(cs[e.image]);
+        c.en += e.org + e.side;                      // the frame after this seam (the only plane the energy role writes; pix / bias are frozen)
+        emap_update_block<NRG, 12, false, true>(c, rd, p, w - 1, h, stride, k, epoch, (unsigned) e.index, tid, SeamLive());
+        return;
+    }
+    GCarver c = gview_phys(cs[e.image]);
+    // (the descriptor comes by vector loads: the row's plane pointers to scalar registers, or the three roles do not fit 96 VGPRs)
+    c.en = uni_ptr(c.en); c.m = uni_ptr(c.m); c.least = uni_ptr(c.least); c.seam_x = uni_ptr(c.seam_x);
+    const int y = e.index * 4 + (tid >> 6);
+    if (y < h) carve_row<true>(c, e.org, e.side, y, w, stride, DELTA, move_dp, tid & 63, h, p.radius, SeamLive());
+}
+
 // ---- the instantiations the shim launches (lqr_kernels.h lists them)
 // (k_carve is not a template)
 #define INST(N) template __global__ void k_carve_u<N>(const DevCarver *, DpK, int, int, int, int, int, int, int);
 K_CARVE_U_FORMS(INST)
+#undef INST
+#define INST(N, D) template __global__ void k_carve_v<N, D>(const DevCarver *, DpK, int, int, int, int, int, int, int, int, int, unsigned, unsigned long long *, unsigned long long *, int *);
+K_CARVE_V_FORMS(INST)
 #undef INST
 #define INST(N) template __global__ void k_carve_e<N>(const DevCarver *, DpK, int, int, int, int, int, int);
 K_CARVE_E_FORMS(INST)

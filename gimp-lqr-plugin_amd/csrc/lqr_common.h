@@ -5,7 +5,7 @@
 // Translation units (one per stage, so that a change to one protocol rebuilds -- and re-register-allocates -- only that one):
 //   k_energy.hip     E1/E2/E3/E4/E6  k_wk_init(_visible), k_mask_add, k_emap_full, k_emap_update, k_frozen_catchup
 //   k_backtrack.hip  E7              k_vpath, k_vpath1 (they also pick the side the carve moves)
-//   k_carve.hip      E8              k_carve
+//   k_carve.hip      E8 (+ E6, E7)   k_carve; k_carve_e, k_carve_u (the energy update in / beside the carve's launch), k_carve_v (the backtrack beside it too)
 //   k_band.hip       E5/E9           k_dp_sweep, k_band_update, k_band_update_mw, k_band_update_tw (one workgroup per image)
 //   k_tiles.hip      E5/E9           k_dp_tile, k_dp_tile_p (an image spread over several compute units)
 //   k_levels.hip     E9              k_band_levels (the band on several compute units, tiles assigned level by level)
@@ -14,6 +14,8 @@
 //   k_energy_out.hip energy read-outs (lqr_energy.h) k_energy_range (squash, min / max per workgroup), k_energy_out (normalise, expand to pixels, image orientation)
 //   lqr_shim.hip     the lqrhip_* C ABI of include/lqr_hip.h: allocation cache, batches, the per-seam launch sequence
 //   lqr_plan.h       which form of each stage that sequence runs (plain C++17, no HIP: also compiled alone by tests/test_plan.py)
+//   lqr_beside.h     k_carve_v's side bound, work-list entries and their readiness (plain C++17, no HIP: also compiled alone by tests/test_backtrack_beside.py)
+//   lqr_walk.h       the seam pick and the one-wave walk's helpers, vpath1_walk.inc the chase itself: shared by k_vpath1 and k_carve_v's walk role
 //   lqr_own.h        who owns a device block: DevBuf, Scratch (plain C++17, no HIP: also compiled alone by tests/test_own.py)
 //   lqr_pool.h       the allocation cache those blocks come from: BlockCache (plain C++17, no HIP: also compiled alone by tests/test_pool.py)
 //   lqr_stage.h      the ring of pinned buffers and helper threads every image is copied through: StageRing (likewise, tests/test_stage.py)
@@ -298,18 +300,36 @@ __device__ __forceinline__ int block_rank_256(bool flag, int *s_wave, int &total
     return r + off;
 }
 
+// How a word of the CURRENT seam (seam_x, the newest row of the seam log) is read.  SeamPlain: the seam was written by an earlier
+// launch -- every kernel but one.  SeamLive: the walk role of the same launch is writing it (k_carve_v, k_carve.hip): an XCD's L2 may
+// hold a line of it fetched earlier in the launch, so the read goes to where the walk's write-through stores went
+struct SeamPlain {
+    static constexpr bool live = false;
+    __device__ __forceinline__ int operator()(const gi32 *p) const { return *p; }
+};
+struct SeamLive {
+    static constexpr bool live = true;
+    __device__ __forceinline__ int operator()(const gi32 *p) const { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+};
+
 // changed-energy interval of row y after carving (liblqr update_emap), w = new width
-__device__ __forceinline__ void nrg_interval(const gi32 *seam, int y, int h, int w, int radius, int &xmin, int &xmax)
+template <class SR>
+__device__ __forceinline__ void nrg_interval(const gi32 *seam, int y, int h, int w, int radius, int &xmin, int &xmax, SR sr)
 {
     int y1a = max(y - radius, 0), y1b = min(y + radius, h - 1);
-    int lo = seam[y], hi = seam[y] - 1;
+    const int v = sr(seam + y);
+    int lo = v, hi = v - 1;
     for (int y1 = y1a; y1 <= y1b; y1++) {
-        int x = seam[y1];
+        int x = sr(seam + y1);
         lo = min(lo, x - radius);
         hi = max(hi, x + radius - 1);
     }
     xmin = max(0, lo);
     xmax = min(w - 1, hi);
+}
+__device__ __forceinline__ void nrg_interval(const gi32 *seam, int y, int h, int w, int radius, int &xmin, int &xmax)
+{
+    nrg_interval(seam, y, h, w, radius, xmin, xmax, SeamPlain());
 }
 
 // ---------------------------------------------------------------------------

@@ -44,8 +44,9 @@ template <> struct PixRead<true> {
 // role of k_carve_u (k_carve.hip), so that the arithmetic exists once.  c = the logical view of the frame AFTER the carve (w wide),
 // blk = the row block, tid = 0 .. 63, rd set up by the caller.  ONE_WAVE: the 64 threads are one wave that may be alone in its
 // workgroup -- no s_barrier between staging and evaluation then (a wave's LDS operations execute in order)
-template <int NRG, int EU_NT, bool VALUE, bool ONE_WAVE>
-__device__ __forceinline__ void emap_update_block(const GCarver c, const PixRead<VALUE> rd, const DpK p, int w, int h, int stride, int k, int epoch, unsigned blk, int tid)
+// SR (lqr_common.h): how the current seam is read -- seam_x and log entry k; older log entries and the frozen planes are read plainly
+template <int NRG, int EU_NT, bool VALUE, bool ONE_WAVE, class SR = SeamPlain>
+__device__ __forceinline__ void emap_update_block(const GCarver c, const PixRead<VALUE> rd, const DpK p, int w, int h, int stride, int k, int epoch, unsigned blk, int tid, SR sr = SR())
 {
     __shared__ double bt[64][EU_NT];
     __shared__ float bb[64][EU_NT];
@@ -55,11 +56,11 @@ __device__ __forceinline__ void emap_update_block(const GCarver c, const PixRead
     constexpr bool luma = (NRG >= 3);
     int xmin = 0, xmax = -1, lo = 0;
     if (row_ok) {
-        nrg_interval(c.seam_x, y, h, w, p.radius, xmin, xmax);
+        nrg_interval(c.seam_x, y, h, w, p.radius, xmin, xmax, sr);
         // samples of this row that rows y-1, y, y+1 will ask for
         int l = xmin - 1, r = xmax + 1;
-        if (y > 0) { int a, b; nrg_interval(c.seam_x, y - 1, h, w, p.radius, a, b); if (b >= a) { l = min(l, a); r = max(r, b); } }
-        if (y < h - 1) { int a, b; nrg_interval(c.seam_x, y + 1, h, w, p.radius, a, b); if (b >= a) { l = min(l, a); r = max(r, b); } }
+        if (y > 0) { int a, b; nrg_interval(c.seam_x, y - 1, h, w, p.radius, a, b, sr); if (b >= a) { l = min(l, a); r = max(r, b); } }
+        if (y < h - 1) { int a, b; nrg_interval(c.seam_x, y + 1, h, w, p.radius, a, b, sr); if (b >= a) { l = min(l, a); r = max(r, b); } }
         lo = max(l, 0);
         int pos[EU_NT];
 #pragma unroll
@@ -71,7 +72,10 @@ __device__ __forceinline__ void emap_update_block(const GCarver c, const PixRead
         for (int j = k; j >= epoch; j -= EU_LOGB) {
             int v[EU_LOGB];
 #pragma unroll
-            for (int u = 0; u < EU_LOGB; u++) v[u] = lg[(size_t) max(j - u, epoch) * h];
+            for (int u = 0; u < EU_LOGB; u++) {
+                const gi32 *q = lg + (size_t) max(j - u, epoch) * h;
+                if (SR::live && u == 0 && j == k) v[u] = sr(q); else v[u] = *q;
+            }
 #pragma unroll
             for (int u = 0; u < EU_LOGB; u++) {
                 const int vu = (j - u >= epoch) ? v[u] : 0x7fffffff;

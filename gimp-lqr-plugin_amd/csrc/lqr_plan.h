@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <stddef.h>
 #include "../../include/lqr_hip.h"
+#include "lqr_beside.h"         // the backtrack beside the carve: its side bound, its entries and their limits
 
 #define DP_THREADS 1024
 // ---- geometry of the persistent tiled kernels (k_tiles.hip), needed by their launchers too
@@ -59,6 +60,7 @@ struct PlanKnobs {
     int sweep_threads = 256;        // threads of the k_dp_sweep<UPDATE> launch behind the band kernels (256, or 1024 as in rounds 1 - 5)
     int carve_fused = 4;            // k_carve_e (carve + energy update in one launch) for groups up to this many images (0: the two kernels always)
     int carve_beside = -1;          // k_carve_u (the energy update beside the carve, one launch): -1 automatic (plan_carve_beside); 0 never; 1 wherever a form exists
+    int backtrack_beside = -1;      // k_carve_v (the backtrack as a role of the carve's launch too): -1 automatic (plan_backtrack_beside); 0 never; 1 wherever a form exists
     int update_mode = -1;           // lqrhip_set_update_mode
     int band_levels = -1;           // k_band_levels: -1 automatic; 0 never; n: n slots per image
     int dpp_limit = -1;             // -1: the occupancy-derived bounds; >= 0: at most that many workgroups for a spinning grid
@@ -102,6 +104,7 @@ struct StepPlan {
     int vp_rows = 0, vp_chunks = 0;
     int carve = 0;                  // LQRHIP_CENSUS_CARVE_E (the energy update fused in) or _CARVE
     bool energy_beside = false;     // _CARVE only: k_carve_u, the energy update as workgroups of the carve's launch (counted under _CARVE)
+    bool backtrack_beside = false;  // energy_beside only: k_carve_v, the one-wave walk as a role of that launch too (no backtrack launch; counted under _VPATH1 and _CARVE)
     bool catchup = false;           // the frozen planes lag too far: compact them before the energy update
     int eu_nt = 0;                  // k_emap_update's samples per row
     bool full = false;              // dp is a full DP (after a side switch), not an update
@@ -254,6 +257,27 @@ static inline bool plan_carve_beside(const PlanKnobs &k, const PlanBatch &b, int
     return k.carve_beside > 0 || (!b.shared && b.group() >= (size_t) CARVE_BESIDE_MIN);
 }
 
+// The backtrack beside the carve as well (k_carve_v, k_carve.hip): the one-wave walk hands rows to the carve and energy roles of the
+// same launch through a work list, so the 59 us per 4K seam in which 64 chasing waves had the chip to themselves leave the step.
+// A form exists where the energy update runs beside the carve (plan_carve_beside), the backtrack is the one-wave walk at delta_x
+// <= 2, the frame has at least three walk chunks of rows and at most what the walk's path buffer and the entry's fields hold, and
+// spinning kernels are allowed (the consumers wait for their entries).  Not on the step that compacts the frozen planes: that pass
+// reads this seam's log row between the backtrack and the carve.  The knob at 1 takes the form wherever it exists.  Automatic:
+// batches that have their stream to themselves, of at least BACKTRACK_BESIDE_MIN images.
+// Measured on one stream (profiles/backtrack_beside/README.md; 4K, 200 seams, parent / new): per launch k_vpath1 59.1 + k_carve_u 451.0 us
+// -> k_carve_v 460.5 us (the walk role itself: 100 us inside the launch); 64 images, three alternating runs of 20 steps: 200.89 202.78
+// 204.49 -> 193.85 195.43 197.60 ms per step (+3.8 % at the medians, every new run below every parent run).  Mseams*px/s in the order
+// parent, new, new, parent: 8 images 177.4 k 180.1 k 178.2 k 177.4 k, 16: 302.3 328.2 323.8 304.6, 32: 406.2 437.6 437.5 407.0,
+// 48: 492.5 527.3 528.0 492.7 -- every size run gains (8 by the least), so the threshold is the smallest size run, which is also where
+// the energy update beside the carve starts; 5 .. 7 were not run.  Sub-batches on sibling streams are left out as they are there.
+constexpr int BACKTRACK_BESIDE_MIN = 8;
+static inline bool plan_backtrack_beside(const PlanKnobs &k, const PlanBatch &b, int delta, int h, bool energy_beside, int backtrack, bool catchup)
+{
+    if (k.backtrack_beside == 0 || !energy_beside || backtrack != LQRHIP_CENSUS_VPATH1 || delta < 1 || delta > 2 || !b.spin || catchup) return false;
+    if (h < BB_MIN_ROWS || h > BB_MAX_ROWS || b.images > BB_MAX_IMAGES) return false;
+    return k.backtrack_beside > 0 || (!b.shared && b.group() >= (size_t) BACKTRACK_BESIDE_MIN);
+}
+
 // One seam of a lock-step batch: the frame is w wide before it; `lag` seams separate the frozen planes from the frame after it
 static inline StepPlan plan_seam_step(const PlanKnobs &k, const PlanDevice &d, const PlanBatch &b, int delta, bool use_rig, int w, int h, bool full_rebuild, int lag)
 {
@@ -278,6 +302,7 @@ static inline StepPlan plan_seam_step(const PlanKnobs &k, const PlanDevice &d, c
     s.carve = delta <= 2 && b.group() <= (size_t) k.carve_fused && wnew > 1 && !b.value ? LQRHIP_CENSUS_CARVE_E : LQRHIP_CENSUS_CARVE;
     s.energy_beside = s.carve == LQRHIP_CENSUS_CARVE && plan_carve_beside(k, b, delta, wnew);
     s.catchup = lag > frozen_lag(b.images);
+    s.backtrack_beside = plan_backtrack_beside(k, b, delta, h, s.energy_beside, s.backtrack, s.catchup);
     s.eu_nt = eu_samples(delta);
     if (wnew <= 1) return s;
     if (full_rebuild) {

@@ -147,6 +147,8 @@ struct LqrHipBatch {
     DevBuf<unsigned long long> exch;        // k_dp_tile_p: halo granules per image and tile + finished-tile counters
     int exch_ntiles = 0, exch_n = 0, exch_px = 0;      // geometry the exchange area was last laid out for
     int tile_epoch = 0;                     // launches of k_dp_tile_p on this batch (part of the granule tags)
+    DevBuf<unsigned long long> wlist;       // k_carve_v: the work list its walk role fills (two tail words, then the entries: lqr_beside.h)
+    unsigned wlist_launches = 0;            // launches of k_carve_v on this batch (their tags)
     bool dirty = true;
     int shared_n = 1;                       // ... how many batches of the group there are (lqrhip_batch_set_shared)
     bool shared = false;                    // other batches of the same group run concurrently on their own streams:
@@ -1102,6 +1104,14 @@ extern "C" unsigned long long lqrhip_carve_beside_launches(int reset)
     if (reset) g_carve_beside_launches = 0;
     return v;
 }
+extern "C" void lqrhip_set_backtrack_beside(int mode) { g_knobs.backtrack_beside = mode < 0 ? -1 : mode ? 1 : 0; }
+static unsigned long long g_backtrack_beside_launches;      // k_carve_v launches (counted under LQRHIP_CENSUS_VPATH1, _CARVE and as carve-beside launches as well)
+extern "C" unsigned long long lqrhip_backtrack_beside_launches(int reset)
+{
+    const unsigned long long v = g_backtrack_beside_launches;
+    if (reset) g_backtrack_beside_launches = 0;
+    return v;
+}
 extern "C" void lqrhip_set_update_mode(int mode) { g_knobs.update_mode = mode; }
 extern "C" void lqrhip_set_dp_persistent_px(int px) { g_knobs.dpp_px = (px == 2 || px == 3 || px == 4) ? px : 0; }
 // (0 sends every full DP to k_dp_tile and every incremental update to a band kernel)
@@ -1398,7 +1408,7 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
                 hipLaunchKernelGGL(k_vp_maps<delta>, dim3((w + 255) / 256, nchunks, n), dim3(256), 0, b->stream, b->d_desc, w, h, stride);
                 hipLaunchKernelGGL(k_vp_solve<delta>, dim3(n), dim3(VPATH_THREADS), (size_t) (nchunks + 2) * sizeof(int), b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit);
             })) return no_form("k_vp_maps");
-    } else {
+    } else if (!s.backtrack_beside) {            // (beside: the walk is a role of the carve's launch below)
         ProfScope ps("vpath", b->stream, 0);
         CENSUS(s.backtrack);
         // the one-wave walk: unrolled for the listed delta_x, the loop over candidates beyond (and for delta_x 0)
@@ -1418,6 +1428,35 @@ static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h,
         if (!with_listed(K_CARVE_E_FORMS, nrg_index(p->nrg_func), [&](auto nrg) {
                 hipLaunchKernelGGL((k_carve_e<nrg>), dim3((h + 3) / 4, n), dim3(256), 0, b->stream, b->d_desc, k, w, h, stride, move_dp, log_index, epoch);
             })) return no_form("k_carve_e");
+    } else if (s.backtrack_beside) {
+        // k_carve_v: the walks' workgroups first, then one consumer per entry of the work list the walks fill -- the carve's row-quads and
+        // the energy update's blocks, in the order they become ready (k_carve.hip).  "vpath" and "emap_update" have no launch on this path.
+        // (No catch-up here: the plan keeps the step that compacts the frozen planes on the separate launches)
+        const int epoch = c0->frozen_epoch;
+        const size_t need = (size_t) BB_LIST_HEAD + (size_t) bb_entries((int) n, h);
+        if (b->wlist.size() < need) {
+            bool grew = false;
+            HIPCK(hipStreamSynchronize(b->stream));     // (the list in use goes back to the pool)
+            if ((rc = b->wlist.ensure(need, "&b->wlist", &grew))) return rc;
+            HIPCK(hipMemsetAsync(b->wlist, 0, need * sizeof(unsigned long long), b->stream));        // no tag, both tails at 0
+        }
+        unsigned long long *moved = lqr_moved_bytes_dev();
+        if (!moved) { g_err = "k_carve_v: no address for the moved-bytes counter"; return LQRHIP_EHIP; }
+        const unsigned tag = bb_tag(b->wlist_launches++);
+        ProfScope ps("carve", b->stream, 4.0 * (double) w * h * n);
+        CENSUS(LQRHIP_CENSUS_VPATH1);
+        CENSUS(LQRHIP_CENSUS_CARVE);
+        g_carve_beside_launches++;
+        g_backtrack_beside_launches++;
+        const unsigned grid = n + (unsigned) bb_entries((int) n, h);
+        bool launched = false;
+        with_listed(K_CARVE_U_FORMS, nrg_index(p->nrg_func), [&](auto nrg) {
+            launched = with_listed(K_CARVE_V_DELTAS, p->delta_x, [&](auto delta) {
+                hipLaunchKernelGGL((k_carve_v<nrg, delta>), dim3(grid), dim3(256), 0, b->stream, b->d_desc, k, w, h, stride, leftright_pick, move_dp, log_index, epoch,
+                                   (int) n, moved_unit, tag, b->wlist.get(), moved, g_dev_err);
+            });
+        });
+        if (!launched) return no_form("k_carve_v");
     } else if (s.energy_beside) {
         // k_carve_u: the energy update's workgroups first, then the carve's, in one 1-D grid (k_carve.hip).  The same algorithmic bytes as
         // k_carve's; "emap_update" has no launch on this path
@@ -1848,6 +1887,17 @@ extern "C" int lqrhip_read_vmap(LqrHipCarver *c, int w0, int h0, int w, int leve
     return 0;
 }
 
+// Test hook: what the backtrack published for the last seam -- the origin every kernel uses, the origin before that seam, the side it moved
+extern "C" int lqrhip_read_seam_flags(LqrHipCarver *c, int *org, int *org_prev, int *side)
+{
+    int rc = batch_sync_of(c);
+    if (rc) return rc;
+    if (!c->wk.flags) return LQRHIP_EARG;
+    int32_t fl[FLAG_COUNT];
+    HIPCK(hipMemcpy(fl, c->wk.flags, sizeof fl, hipMemcpyDeviceToHost));
+    *org = fl[FLAG_ORG]; *org_prev = fl[FLAG_ORG_PREV]; *side = fl[FLAG_SIDE];
+    return 0;
+}
 extern "C" int lqrhip_read_working(LqrHipCarver *c, int w, int h, float *en, float *m, int *least_dx)
 {
     int rc = batch_sync_of(c);

@@ -127,6 +127,7 @@ struct _LqrCarver {
     /* debug snapshot */
     float *dbg_en, *dbg_m;
     int *dbg_least, dbg_w, dbg_h;
+    int dbg_org, dbg_org_prev, dbg_side;        /* the snapshot's seam flags (lqrhip_read_seam_flags) */
 };
 
 /* bytes per channel of each LqrColDepth */
@@ -773,6 +774,7 @@ static LqrRetVal take_debug_snapshot(LqrCarver *r)
     r->dbg_least = (int *) malloc(n * sizeof(int));
     if (!r->dbg_en || !r->dbg_m || !r->dbg_least) return LQR_NOMEM;
     HIP_CATCH(lqrhip_read_working(r->dev, r->geo.w, r->geo.h, r->dbg_en, r->dbg_m, r->dbg_least));
+    HIP_CATCH(lqrhip_read_seam_flags(r->dev, &r->dbg_org, &r->dbg_org_prev, &r->dbg_side));
     return LQR_OK;
 }
 
@@ -1369,6 +1371,13 @@ LqrRetVal lqrx_carver_debug_maps(LqrCarver *r, gfloat *en, gfloat *m, gint *leas
     if (!r->active || !r->wk_valid) return LQR_ERROR;
     HIP_CATCH(lqrhip_read_working(r->dev, r->geo.w, r->geo.h, en, m, least_dx));
     return LQR_OK;
+}
+int lqrhip_debug_seam_flags(const void *carver, int *org, int *org_prev, int *side)
+{
+    const LqrCarver *r = (const LqrCarver *) carver;
+    if (!r || !r->dbg_m) return LQRHIP_EARG;
+    *org = r->dbg_org; *org_prev = r->dbg_org_prev; *side = r->dbg_side;
+    return 0;
 }
 gint lqrx_carver_debug_width(LqrCarver *r) { return r->dbg_w; }
 gint lqrx_carver_debug_height(LqrCarver *r) { return r->dbg_h; }

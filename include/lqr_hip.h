@@ -275,6 +275,12 @@ void lqrhip_pool_trim(void);
 int lqrhip_read_vmap(LqrHipCarver *c, int w0, int h0, int w, int level, int depth, int *out);
 /* test hooks behind lqrx_carver_get_energy / lqrx_carver_debug_maps */
 int lqrhip_read_working(LqrHipCarver *c, int w, int h, float *en, float *m, int *least_dx);
+/* Test hook: the flags the backtrack published for the last seam: the origin of the carved planes, the origin before that seam, and
+ * the side of it the carve moved (0: the right part one to the left; 1: the left part one to the right, the origin advances) */
+int lqrhip_read_seam_flags(LqrHipCarver *c, int *org, int *org_prev, int *side);
+/* ... and as lqrx_set_debug(1) recorded them with the snapshot of the planes after a session's last seam (include/lqr.h).  `carver` is
+ * the LqrCarver (host/lqr_carver.c implements this one); 0, or LQRHIP_EARG where there is no snapshot */
+int lqrhip_debug_seam_flags(const void *carver, int *org, int *org_prev, int *side);
 
 /* kernel-time accounting for bench.py: accumulated HIP-event time (ms) and
  * launch count of the carve kernel (the roofline kernel) since the last reset */
@@ -299,6 +305,14 @@ void lqrhip_set_carve_fused(int max_images);
  * lqrhip_carve_beside_launches returns how many of them were combined launches since the last reset */
 void lqrhip_set_carve_beside(int mode);
 unsigned long long lqrhip_carve_beside_launches(int reset);
+/* Test hook: the backtrack as a role of that launch too (k_carve_v: the one-wave walk hands rows to the carve and the energy update
+ * of the same launch as it finds them; delta_x 1 and 2, frames of 37 to 4096 rows, where the energy update runs beside the carve and
+ * spinning kernels are allowed; never on the step that compacts the frozen planes): -1 = automatic (groups that have their stream to
+ * themselves, from the size lqr_plan.h names), 0 = never (k_vpath1, then k_carve_u), 1 = wherever a form exists.  Such a launch is
+ * counted under LQRHIP_CENSUS_VPATH1 and LQRHIP_CENSUS_CARVE and as a carve-beside launch; lqrhip_backtrack_beside_launches returns how
+ * many there were since the last reset.  Same seams, planes, flags and moved bytes either way */
+void lqrhip_set_backtrack_beside(int mode);
+unsigned long long lqrhip_backtrack_beside_launches(int reset);
 /* E7 form: -1 = the parallel two-kernel backtrack (k_vp_maps / k_vp_solve) for groups of up to par_max images (default 3; 0 keeps the
  * current value) of 1000 rows and more, the one-wave walk k_vpath1 otherwise; 0 = k_vpath1 always; 1 = the parallel form
  * always (delta_x 1 .. 4) */
