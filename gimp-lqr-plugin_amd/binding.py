@@ -245,6 +245,37 @@ def bind_vmap(api):
     return api
 
 
+# include/lqr_control.h: lqr_carver_cancel, the five small carver-control calls and the two extensions.  LqrDataTok is a union of one
+# word (a pointer, a gint, a pointer) passed by value: the C ABI passes it as one integer register, and ctypes, which does not pass
+# unions by value, passes it as the pointer-sized integer it is
+(LQR_GF_NORM, LQR_GF_NORM_BIAS, LQR_GF_SUMABS, LQR_GF_XABS, LQR_GF_YABS, LQR_GF_NULL) = range(6)
+DATA_TOK = C.c_void_p
+CARVER_FUNC = C.CFUNCTYPE(C.c_int, C.c_void_p, DATA_TOK)
+CONTROL_SYMBOLS = {
+    "lqr_carver_cancel": (_I, [_P]),
+    "lqr_carver_set_use_cache": (None, [_P, _I]),
+    "lqr_carver_set_no_dump_vmaps": (None, [_P]),
+    "lqr_carver_list_foreach": (_I, [_P, CARVER_FUNC, DATA_TOK]),
+    "lqr_carver_list_foreach_recursive": (_I, [_P, CARVER_FUNC, DATA_TOK]),
+    "lqr_carver_set_gradient_function": (None, [_P, _I]),
+    "lqrx_carver_cancelled": (_I, [_P]),
+    "lqrx_carver_cancel_clear": (_I, [_P]),
+}
+
+
+def bind_control(api):
+    """add CONTROL_SYMBOLS to a bound Api; a genuine liblqr-1 has none of the lqrx_ ones"""
+    if not getattr(api, "has_control", False):
+        for name, (res, args) in CONTROL_SYMBOLS.items():
+            if name.startswith("lqrx_") and not api.has_ext:
+                continue
+            fn = getattr(api.lib, api.prefix + name)      # AttributeError = missing export
+            fn.restype, fn.argtypes = res, args
+            setattr(api, name, fn)
+        api.has_control = True
+    return api
+
+
 def _vmap_new(api, m):
     """a LqrVMap around a malloc'd copy of m["data"] (h x w int32, image orientation), which the map owns"""
     data = np.ascontiguousarray(m["data"], dtype=np.int32)
@@ -298,6 +329,11 @@ def engine_energy_api():
 def engine_vmap_api():
     """the engine with the colour-depth and seam-map loading surfaces bound"""
     return bind_vmap(bind_coldepth(engine_api()))
+
+
+def engine_control_api():
+    """the engine with the carver-control surface bound"""
+    return bind_control(engine_api())
 
 
 def engine_coldepth_api():
@@ -648,8 +684,8 @@ class Carver:
         prog = a.lqr_progress_new()
         ev = self.events
         cb_i = PROGRESS_INIT(lambda m: (ev.append(("init", m.decode())), 1)[1])
-        cb_u = PROGRESS_UPDATE(lambda f: (ev.append(("update", f)), 1)[1])
-        cb_e = PROGRESS_END(lambda m: (ev.append(("end", m.decode() if m else "")), 1)[1])
+        cb_u = PROGRESS_UPDATE(lambda f: (ev.append(("update", f)), self._on_event("update"), 1)[2])
+        cb_e = PROGRESS_END(lambda m: (ev.append(("end", m.decode() if m else "")), self._on_event("end"), 1)[2])
         self._cbs += [cb_i, cb_u, cb_e]
         a.lqr_progress_set_init(prog, cb_i)
         a.lqr_progress_set_update(prog, cb_u)
@@ -657,6 +693,63 @@ class Carver:
         a.lqr_progress_set_init_width_message(prog, b"Resizing width...")
         a.lqr_progress_set_init_height_message(prog, b"Resizing height...")
         a.lqr_carver_set_progress(self.p, prog)
+
+    # -- carver control (include/lqr_control.h)
+    def cancel(self):
+        """lqr_carver_cancel; the LqrRetVal.  The one call another thread may make while this carver is inside a call"""
+        return bind_control(self.api).lqr_carver_cancel(self.p)
+
+    def cancelled(self):
+        return bind_control(self.api).lqrx_carver_cancelled(self.p)
+
+    def cancel_clear(self):
+        return bind_control(self.api).lqrx_carver_cancel_clear(self.p)
+
+    def cancel_at_update(self, n, target=None, via=None, event="update"):
+        """the recorder's n-th update callback from now on (0: disarmed; event="end": its n-th end callback) calls lqr_carver_cancel on
+        `target` (this carver by default); via: a callable that makes the call in its place (a test's second thread) and returns its
+        LqrRetVal"""
+        self._hook = dict(at=int(n), seen=0, target=target or self, via=via, event=event, fired=False, ret=0) if n else None
+
+    def cancel_result(self):
+        """(whether the armed call was made, what it returned)"""
+        h = getattr(self, "_hook", None)
+        return (h["fired"], h["ret"]) if h else (False, 0)
+
+    def _on_event(self, event):
+        h = getattr(self, "_hook", None)
+        if h and not h["fired"] and h["event"] == event:
+            h["seen"] += 1
+            if h["seen"] == h["at"]:
+                h["ret"] = h["via"](h["target"]) if h["via"] else h["target"].cancel()
+                h["fired"] = True
+
+    def set_use_cache(self, on):
+        bind_control(self.api).lqr_carver_set_use_cache(self.p, int(on))
+
+    def set_dump_vmaps(self):
+        self.api.lqr_carver_set_dump_vmaps(self.p)
+
+    def set_no_dump_vmaps(self):
+        bind_control(self.api).lqr_carver_set_no_dump_vmaps(self.p)
+
+    def set_gradient_function(self, gf):
+        bind_control(self.api).lqr_carver_set_gradient_function(self.p, int(gf))
+
+    def list_foreach(self, recursive=False, stop_at=0, stop_ret=0, token=0):
+        """lqr_carver_list_foreach (_recursive) over the attached carvers with a callback that returns stop_ret at its stop_at-th call
+        (0: never): (LqrRetVal, [index of each visited carver in self.aux], [the tokens the callback saw])"""
+        a = bind_control(self.api)
+        seen = []
+
+        def cb(carver, tok):
+            seen.append((carver, tok or 0))
+            return stop_ret if stop_at and len(seen) == stop_at else LQR_OK
+        fn = CARVER_FUNC(cb)
+        f = a.lqr_carver_list_foreach_recursive if recursive else a.lqr_carver_list_foreach
+        ret = f(a.lqr_carver_list_start(self.p), fn, token)
+        ps = [x.p for x in self.aux]
+        return ret, [ps.index(c) for c, _ in seen], [t for _, t in seen]
 
     def attach(self, img):
         """attach_aux_carver, render.c:881-900"""

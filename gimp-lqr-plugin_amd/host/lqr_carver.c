@@ -30,9 +30,11 @@
 #include "../../include/lqr_masks.h"
 #include "../../include/lqr_energy.h"
 #include "../../include/lqr_vmap.h"
+#include "../../include/lqr_control.h"
 #include "../../include/lqr_hip.h"
 #include "lqr_mask_queue.h"
 #include "lqr_sched.h"
+#include "lqr_state.h"
 
 #define MAXI(a, b) ((a) > (b) ? (a) : (b))
 #define MINI(a, b) ((a) < (b) ? (a) : (b))
@@ -106,6 +108,7 @@ struct _LqrCarver {
     float enl_step;
     int resize_order;
     int dump_vmaps;
+    LqrState state;             /* liblqr's carver state, the one word lqr_carver_cancel touches (lqr_state.h); a root's: attached carvers read their root's */
     LqrVMapList *flushed_vs;
     LqrProgress *progress;
     int session_update_step, session_rescale_total, session_rescale_current;
@@ -277,6 +280,7 @@ static LqrCarver *carver_new(void *buffer, int width, int height, int channels, 
     if (!r->progress) { lqrhip_carver_destroy(r->dev); free(r); return NULL; }
     lqr_maskq_init(&r->mq[0], 0);
     lqr_maskq_init(&r->mq[1], 0);
+    lqr_state_init(&r->state);
     return r;
 }
 
@@ -423,6 +427,57 @@ LqrRetVal lqr_carver_set_enl_step(LqrCarver *r, gfloat s)
 gfloat lqr_carver_get_enl_step(LqrCarver *r) { return r->enl_step; }
 void lqr_carver_set_dump_vmaps(LqrCarver *r) { r->dump_vmaps = 1; }
 
+/* ======================= carver control (lqr_control.h) ================== */
+/* The one call a second thread may make: it touches the root's state word and nothing else.  On an attached carver: LQR_ERROR, as in
+ * liblqr (tests/golden/control/, cancel_aux_idle and cancel_aux_in_resize). */
+LqrRetVal lqr_carver_cancel(LqrCarver *r)
+{
+    if (!r || r->root) return LQR_ERROR;
+    (void) lqr_state_cancel(&r->state);
+    return LQR_OK;
+}
+gint lqrx_carver_cancelled(LqrCarver *r) { return r ? lqr_state_check(lqr_state_word(&r->state, r->root ? &r->root->state : NULL)) : 0; }
+LqrRetVal lqrx_carver_cancel_clear(LqrCarver *r)
+{
+    if (!r || r->root) return LQR_ERROR;
+    return lqr_state_clear(&r->state) ? LQR_OK : LQR_ERROR;
+}
+/* (the read plane is the cache: lqr_control.h) */
+void lqr_carver_set_use_cache(LqrCarver *r, gboolean use_cache) { (void) r; (void) use_cache; }
+void lqr_carver_set_no_dump_vmaps(LqrCarver *r) { r->dump_vmaps = 0; }
+LqrRetVal lqr_carver_list_foreach(LqrCarverList *list, LqrCarverFunc func, LqrDataTok data)
+{
+    for (; list; list = list->next) LQR_CATCH(func(list->current, data));
+    return LQR_OK;
+}
+/* (attached carvers lie one level deep here: nothing further to visit) */
+LqrRetVal lqr_carver_list_foreach_recursive(LqrCarverList *list, LqrCarverFunc func, LqrDataTok data) { return lqr_carver_list_foreach(list, func, data); }
+void lqr_carver_set_gradient_function(LqrCarver *r, LqrGradFuncType gf_ind)
+{
+    static const LqrEnergyFuncBuiltinType builtin_of[6] = {LQR_EF_GRAD_NORM, LQR_EF_NULL, LQR_EF_GRAD_SUMABS, LQR_EF_GRAD_XABS, LQR_EF_NULL, LQR_EF_NULL};
+    if ((int) gf_ind >= LQR_GF_NORM && (int) gf_ind <= LQR_GF_NULL) (void) lqr_carver_set_energy_function_builtin(r, builtin_of[gf_ind]);
+}
+
+/* A call that works on the device enters the busy state on every root it was given and leaves it on every way out; a carver that is
+ * marked cancelled refuses the call (LQR_USRCANCEL, as liblqr's LQR_CATCH_CANC), one that is inside another call too (LQR_ERROR) */
+static LqrRetVal roots_enter(LqrCarver **rs, int n, int busy)
+{
+    int i;
+    for (i = 0; i < n; i++) {
+        const int rc = lqr_state_enter(&rs[i]->state, busy);
+        if (rc != LQR_STATE_ENTERED) {
+            while (i--) lqr_state_leave(&rs[i]->state);
+            return rc == LQR_STATE_IS_CANCELLED ? LQR_USRCANCEL : LQR_ERROR;
+        }
+    }
+    return LQR_OK;
+}
+static void roots_leave(LqrCarver **rs, int n)
+{
+    int i;
+    for (i = 0; i < n; i++) lqr_state_leave(&rs[i]->state);
+}
+
 /* ======================= getters ========================================= */
 gint lqr_carver_get_width(LqrCarver *r) { return r->geo.transposed ? r->geo.h : r->geo.w; }
 gint lqr_carver_get_height(LqrCarver *r) { return r->geo.transposed ? r->geo.w : r->geo.h; }
@@ -532,6 +587,24 @@ static void group_close(Group *g)
         }                                                         \
     }
 
+/* the check points of lqr_carver_cancel: one relaxed load per root */
+static int group_cancelled(const Group *g)
+{
+    int i;
+    for (i = 0; i < g->n; i++)
+        if (lqr_state_check(&g->r[i]->state)) return 1;
+    return 0;
+}
+#define CANCEL_POINT(g) do { if (group_cancelled(g)) return LQR_USRCANCEL; } while (0)
+/* ... and before a pass, which also names what the carvers are busy with (liblqr's LqrCarverState) */
+static LqrRetVal group_phase(Group *g, int busy)
+{
+    int i;
+    CANCEL_POINT(g);
+    for (i = 0; i < g->n; i++) (void) lqr_state_phase(&g->r[i]->state, busy);
+    return LQR_OK;
+}
+
 static void dp_params(const LqrCarver *r, LqrHipDpParams *p)
 {
     memset(p, 0, sizeof *p);
@@ -576,6 +649,7 @@ static LqrRetVal group_flatten(Group *g)
     LqrCarver *r0 = g->r[0];
     int i;
     if (!lqr_geom_is_flat(&r0->geo)) {
+        LQR_CATCH(group_phase(g, LQR_STATE_FLATTENING));
         HIP_ALL(g, lqrhip_flatten(B, r0->geo.w0, r0->geo.h0, r0->geo.w, r0->geo.level));     /* every sub-batch staged ... */
         HIP_ALL(g, lqrhip_planes_commit(B));                                                 /* ... before any adopts its flat layout */
     } else if (r0->wk_valid)       /* a flat carver is its own flattening */
@@ -593,6 +667,7 @@ static LqrRetVal group_transpose(Group *g)
     LqrCarver *r0 = g->r[0];
     int i, x;
     if (lqr_geom_flatten_before_transpose(&r0->geo)) LQR_CATCH(group_flatten(g));
+    LQR_CATCH(group_phase(g, LQR_STATE_TRANSPOSING));
     HIP_ALL(g, lqrhip_transpose(B, r0->geo.w0, r0->geo.h0));
     HIP_ALL(g, lqrhip_planes_commit(B));
     FOR_TREE(g, i, r, {
@@ -611,10 +686,12 @@ LqrRetVal lqr_carver_flatten(LqrCarver *r)
     Group g;
     LqrRetVal ret;
     if (r->root) return LQR_ERROR;
-    LQR_CATCH(mask_queue_flush(r));
-    LQR_CATCH(group_open(&g, &r, 1));
-    ret = group_flatten(&g);
-    group_close(&g);
+    LQR_CATCH(roots_enter(&r, 1, LQR_STATE_FLATTENING));
+    if ((ret = mask_queue_flush(r)) == LQR_OK && (ret = group_open(&g, &r, 1)) == LQR_OK) {
+        ret = group_flatten(&g);
+        group_close(&g);
+    }
+    roots_leave(&r, 1);
     return ret;
 }
 
@@ -798,7 +875,9 @@ static LqrRetVal group_build_vsmap(Group *g, const LqrSession *s, int *reported)
                 r0->progress->update(seam.fraction);
                 *reported = l;
             }
+            CANCEL_POINT(g);        /* a cancel from the callback, or during it: nothing is queued here */
         }
+        CANCEL_POINT(g);
         if (seam.full)
             for (i = 0; i < g->n; i++) g->r[i]->leftright ^= 1;
         HIP_ALL(g, lqrhip_seam_step(B, &p, seam.w_before, r0->geo.h, l - s->max_level, lr_pick, seam.full, r0->leftright));
@@ -810,11 +889,13 @@ static LqrRetVal group_build_vsmap(Group *g, const LqrSession *s, int *reported)
 
     /* the seam loop is over: nothing of it is committed to the base layout before its kernels have all ended without a device-side
      * failure and the seam log has passed its self-check */
+    /* (the last check point of lqr_carver_cancel in a session: from here on the session commits and inflates to its end) */
     T_BEGIN(T_TAIL);
     HIP_ALL(g, lqrhip_session_check(B, r0->geo.h, s->wc0, s->n_seams, r0->delta_x));
     HIP_ALL(g, lqrhip_batch_sync(B));
     HIP_ALL(g, lqrhip_vs_commit(B, r0->geo.w0, r0->geo.h0, s->wc0, s->n_seams, s->first_level, s->finish));
     /* inflate (E14): every seam of this session is doubled in the base layout */
+    for (i = 0; i < g->n; i++) (void) lqr_state_phase(&g->r[i]->state, LQR_STATE_INFLATING);
     HIP_ALL(g, lqrhip_inflate(B, r0->geo.w0, r0->geo.h0, s->depth - 1, s->max_level));      /* every sub-batch staged and checked ... */
     HIP_ALL(g, lqrhip_planes_commit(B));                                                    /* ... before any adopts its inflated layout */
     T_END(T_TAIL);
@@ -831,6 +912,7 @@ static LqrRetVal session_run(Group *g, const LqrSession *s, int redo, int *repor
     LqrCarver *r0 = g->r[0];
     LqrHipDpParams p;
     int i;
+    LQR_CATCH(group_phase(g, LQR_STATE_RESIZING));
     for (i = 0; i < g->n; i++) set_width_one(g->r[i], s->wc0);    /* the carved frame */
     dp_params(r0, &p);
     if (!r0->wk_valid || redo) {
@@ -865,10 +947,13 @@ static LqrRetVal group_build_maps(Group *g, int depth)
     ret = session_run(g, &s, 0, &reported);
     for (k = 0; k < 2 && ret != LQR_OK; k++) {
         const int fault = (ret == LQR_ERROR && g_last_rc == LQRHIP_EFAULT);
+        /* a cancelled session (lqr_control.h) is a failed one that is not carved again: nothing more is enqueued, what was runs out,
+         * nothing of it was committed (the last check point lies before the self-check), the bookkeeping goes back */
+        const int cancelled = (ret == LQR_USRCANCEL);
         /* the carver as it was before the session: the base layout (levels of this session removed if they were committed),
          * the bookkeeping; the working planes are gone */
         /* (also after an allocation failure: the staging of the inflate pass comes after the commit of the session's levels) */
-        if (fault || g_last_rc == LQRHIP_ENOMEM)
+        if (fault || cancelled || g_last_rc == LQRHIP_ENOMEM)
             for (i = 0; i < g->nb; i++) (void) lqrhip_session_rollback(g->b[i], r0->geo.w0, r0->geo.h0, s.first_level, s.finish);
         for (i = 0; i < g->n; i++) {
             LqrCarver *c = g->r[i];
@@ -935,17 +1020,27 @@ static int same_config(const LqrCarver *a, const LqrCarver *b);
  * carver changes: the arguments and sizes here, the map's contents on the device (lqrhip_vmap_stage).  Then: flatten if the carvers
  * were resized since their last load, transpose if the map lies the other way, and the inflate pass of the whole tree with the map as
  * every carver's levels, staged on every sub-batch before any commits.  The bookkeeping is group_build_vsmap's after its inflate. */
+static LqrRetVal group_vmap_load_entered(LqrCarver **rs, int n, const gint *map, int on_device, int width, int height, int depth, int orientation);
 static LqrRetVal group_vmap_load(LqrCarver **rs, int n, const gint *map, int on_device, int width, int height, int depth, int orientation)
 {
-    Group g;
-    LqrHipVMap *staged = NULL;
-    LqrRetVal ret = LQR_OK;
-    int i, rc;
+    LqrRetVal ret;
+    int i;
     if (n < 1 || !rs || !map || (orientation != 0 && orientation != 1)) return LQR_ERROR;
     for (i = 0; i < n; i++)
         if (!rs[i] || rs[i]->root || rs[i]->active) return LQR_ERROR;
     for (i = 1; i < n; i++)
         if (!same_config(rs[0], rs[i])) return LQR_ERROR;
+    LQR_CATCH(roots_enter(rs, n, LQR_STATE_RESIZING));
+    ret = group_vmap_load_entered(rs, n, map, on_device, width, height, depth, orientation);
+    roots_leave(rs, n);
+    return ret;
+}
+static LqrRetVal group_vmap_load_entered(LqrCarver **rs, int n, const gint *map, int on_device, int width, int height, int depth, int orientation)
+{
+    Group g;
+    LqrHipVMap *staged = NULL;
+    LqrRetVal ret = LQR_OK;
+    int i, rc;
     for (i = 0; i < n; i++) LQR_CATCH(mask_queue_flush(rs[i]));
     if (lqr_carver_get_width(rs[0]) != width || lqr_carver_get_height(rs[0]) != height) {
         fprintf(stderr, "liblqr-hip: lqr_vmap_load refused: a %d x %d map on a carver that is %d x %d now\n", width, height,
@@ -1015,6 +1110,7 @@ static LqrRetVal group_resize_dir(Group *g, int w1, int want_transposed)
     const gchar *end_msg = want_transposed ? r->progress->end_height_message : r->progress->end_width_message;
 
     lqr_walk_begin(&walk, &r->geo, r->enl_step, w1, want_transposed);
+    if (walk.total) CANCEL_POINT(g);        /* (a direction with nothing to carve is no check point: a cancel that came after the last session's check ends in LQR_OK) */
     for (i = 0; i < g->n; i++) {
         LqrCarver *c = g->r[i];
         c->session_rescale_total = walk.total;
@@ -1024,6 +1120,7 @@ static LqrRetVal group_resize_dir(Group *g, int w1, int want_transposed)
     if (walk.total && r->progress->init) r->progress->init(init_msg);
 
     while (lqr_walk_next(&walk, &s)) {
+        CANCEL_POINT(g);
         if (s.transpose) LQR_CATCH(group_transpose(g));
         LQR_CATCH(group_build_maps(g, s.depth));
         for (i = 0; i < g->n; i++) {
@@ -1073,14 +1170,24 @@ static int inactive_refused(const LqrCarver *r, int w1, int want_transposed)
     return !r->active && lqr_walk_needs_maps(&r->geo, r->enl_step, w1, want_transposed);
 }
 
+static LqrRetVal group_resize_entered(LqrCarver **rs, int n, int w1, int h1);
 static LqrRetVal group_resize(LqrCarver **rs, int n, int w1, int h1)
 {
-    Group g;
-    LqrRetVal ret = LQR_OK;
+    LqrRetVal ret;
     int i;
     if (w1 < 1 || h1 < 1) return LQR_ERROR;
     for (i = 0; i < n; i++)
         if (rs[i]->root || !rs[i]->progress) return LQR_ERROR;
+    LQR_CATCH(roots_enter(rs, n, LQR_STATE_RESIZING));
+    ret = group_resize_entered(rs, n, w1, h1);
+    roots_leave(rs, n);
+    return ret;
+}
+static LqrRetVal group_resize_entered(LqrCarver **rs, int n, int w1, int h1)
+{
+    Group g;
+    LqrRetVal ret = LQR_OK;
+    int i;
     for (i = 0; i < n; i++) LQR_CATCH(mask_queue_flush(rs[i]));
     for (i = 0; i < n; i++)
         if (frame_refused(rs[i], w1, 0) || frame_refused(rs[i], h1, 1)) {
@@ -1136,6 +1243,7 @@ LqrRetVal lqrx_carver_resize_batch(LqrCarver **carvers, gint n, gint w1, gint h1
                 LqrRetVal first = LQR_OK;
                 for (i = 0; i < n; i += lim) {
                     const LqrRetVal r = group_resize(carvers + i, n - i < lim ? n - i : lim, w1, h1);
+                    if (r == LQR_USRCANCEL) return r;       /* ... but none is started after a cancelled one (lqr_control.h) */
                     if (first == LQR_OK) first = r;
                 }
                 return first;
@@ -1316,12 +1424,21 @@ gint lqrx_guess_new_size(const guchar *mask, gint channels, gint width, gint hei
  * its energy is built, and the output stage writes it in image orientation.  form 0: the values as they are, 1: normalised, 2: pixels
  * of depth / image_type; -1: the working plane as it lies, in the carver's frame and without a transposition (the test hook).  A
  * failure leaves the carver in one of the states this sequence passes through. */
+static LqrRetVal energy_run_entered(LqrCarver *r, void *buffer, int on_device, int orientation, int form, int depth, int image_type);
 static LqrRetVal energy_run(LqrCarver *r, void *buffer, int on_device, int orientation, int form, int depth, int image_type)
+{
+    LqrRetVal ret;
+    if (r->root) return LQR_ERROR;          /* (lqr_energy.h: an attached carver cannot be re-laid alone) */
+    LQR_CATCH(roots_enter(&r, 1, LQR_STATE_RESIZING));
+    ret = energy_run_entered(r, buffer, on_device, orientation, form, depth, image_type);
+    roots_leave(&r, 1);
+    return ret;
+}
+static LqrRetVal energy_run_entered(LqrCarver *r, void *buffer, int on_device, int orientation, int form, int depth, int image_type)
 {
     Group g;
     LqrHipDpParams p;
     LqrRetVal ret = LQR_OK;
-    if (r->root) return LQR_ERROR;          /* (lqr_energy.h: an attached carver cannot be re-laid alone) */
     LQR_CATCH(mask_queue_flush(r));
     LQR_CATCH(group_open(&g, &r, 1));
     if (r->geo.w != r->geo.w_start - r->geo.max_level + 1) ret = group_flatten(&g);

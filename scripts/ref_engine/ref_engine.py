@@ -21,7 +21,7 @@ EXE_IN_ZIP = "lib/gimp/2.0/plug-ins/gimp-lqr-plugin.exe"
 SCRATCH = os.environ.get("REF_ENGINE_SCRATCH", "/tmp/ref_engine")
 
 (OP_WRITE, OP_READ, OP_ALLOC, OP_FREE, OP_CALL, OP_INFO, OP_SETCW, OP_EVENTS, OP_HEAPCHECK, OP_SCANALL, OP_POISON,
- OP_PROGRET, OP_QUIT, OP_WRAP) = range(1, 15)
+ OP_PROGRET, OP_QUIT, OP_WRAP, OP_HOOK, OP_HOOKRET, OP_FOREACH, OP_FOREACHLOG) = range(1, 19)
 
 LQR_ERROR, LQR_OK, LQR_NOMEM, LQR_USRCANCEL = 0, 1, 2, 3
 
@@ -237,6 +237,29 @@ class Runner:
     def set_progress_return(self, v):
         self._cmd(OP_PROGRET, v)
         self._read(4)
+
+    def hook_at_update(self, n, name, arg):
+        """at the n-th update event from now the runner calls `name`(arg) from inside the progress callback (n = 0: disarmed)"""
+        self._cmd(OP_HOOK, n, self.pe.symbols[name] if n else 0, arg)
+        self._read(4)
+
+    def hook_result(self):
+        """(whether the armed call was made, what it returned)"""
+        self._cmd(OP_HOOKRET)
+        fired, ret = struct.unpack("<II", self._read(8))
+        return bool(fired), ret
+
+    def foreach_callback(self, stop_at=0, stop_ret=0):
+        """the address of the runner's LqrCarverFunc, its log emptied; it returns stop_ret at its stop_at-th call (0: never) and LQR_OK otherwise"""
+        self._cmd(OP_FOREACH, stop_at, stop_ret)
+        return struct.unpack("<I", self._read(4))[0]
+
+    def foreach_log(self):
+        """[(carver, token)] of the calls made to the runner's LqrCarverFunc since it was armed"""
+        self._cmd(OP_FOREACHLOG)
+        n = struct.unpack("<I", self._read(4))[0]
+        raw = struct.unpack("<32I", self._read(128))
+        return [(raw[i], raw[16 + i]) for i in range(min(n, 16))]
 
     def call(self, name_or_addr, *args, fp=False):
         """cdecl call.  ints/pointers -> one word; ('f', x) -> float word; ('d', x) -> two words"""
@@ -724,6 +747,38 @@ class RefCarver:
             out.append(self._vmap_to_dict(r.call("lqr_vmap_list_current", lst)))
             lst = r.call("lqr_vmap_list_next", lst)
         return out
+
+    # -- carver control (include/lqr_control.h), as binding.Carver's
+    def cancel(self):
+        return self.r.call("lqr_carver_cancel", self.p)
+
+    def cancel_at_update(self, n, target=None):
+        """lqr_carver_cancel(target or this carver) from inside the n-th update callback from now on (0: disarmed)"""
+        self.r.hook_at_update(int(n), "lqr_carver_cancel", (target or self).p)
+
+    def cancel_result(self):
+        return self.r.hook_result()
+
+    def set_use_cache(self, on):
+        self.r.call("lqr_carver_set_use_cache", self.p, int(on))
+
+    def set_no_dump_vmaps(self):
+        self.r.call("lqr_carver_set_no_dump_vmaps", self.p)
+
+    def set_dump_vmaps(self):
+        self.r.call("lqr_carver_set_dump_vmaps", self.p)
+
+    def set_gradient_function(self, gf):
+        self.r.call("lqr_carver_set_gradient_function", self.p, int(gf))
+
+    def list_foreach(self, recursive=False, stop_at=0, stop_ret=0, token=0):
+        """(LqrRetVal, [index of each visited carver in self.aux], [tokens seen])"""
+        r = self.r
+        cb = r.foreach_callback(stop_at, stop_ret)
+        ret = r.call("lqr_carver_list_foreach_recursive" if recursive else "lqr_carver_list_foreach", r.call("lqr_carver_list_start", self.p), cb, token)
+        log = r.foreach_log()
+        ps = [a.p for a in self.aux]
+        return ret, [ps.index(c) for c, _ in log], [t for _, t in log]
 
     def destroy(self):
         if self.p:

@@ -196,7 +196,29 @@ static void ev_push(u32 kind, double v, const char *m)
 }
 static int prog_ret = 1;       /* LQR_OK */
 static int cb_init(const char *m) { ev_push(1, 0, m); return prog_ret; }
-static int cb_update(double p) { ev_push(2, p, 0); return prog_ret; }
+/* one call from inside a resize (OP_HOOK): at the n-th update event after arming, the function at hook_fn is called with hook_arg
+   (lqr_carver_cancel with a carver: what a caller's progress callback, or its other thread, does).  A plain cdecl call on the
+   engine's own stack, the x87 state untouched (the function is integer code). */
+static u32 hook_at, hook_fn, hook_arg, hook_seen, hook_fired, hook_ret;
+static int cb_update(double p)
+{
+    ev_push(2, p, 0);
+    if (hook_at && ++hook_seen == hook_at) {
+        hook_ret = ((u32 (*)(u32)) hook_fn)(hook_arg);
+        hook_fired = 1;
+    }
+    return prog_ret;
+}
+/* a LqrCarverFunc for lqr_carver_list_foreach: logs the carvers and the token it is given, and returns fe_stop_ret at the fe_stop-th
+   call (OP_FOREACH arms it and gives its address, OP_FOREACHLOG reads the log) */
+#define FE_MAX 16
+static u32 fe_carver[FE_MAX], fe_tok[FE_MAX], fe_n, fe_stop, fe_stop_ret;
+static int cb_foreach(u32 carver, u32 tok)
+{
+    if (fe_n < FE_MAX) { fe_carver[fe_n] = carver; fe_tok[fe_n] = tok; }
+    fe_n++;
+    return (fe_stop && fe_n == fe_stop) ? (int) fe_stop_ret : 1;
+}
 static int cb_end(const char *m) { ev_push(3, 0, m); return prog_ret; }
 
 /* ---------------- cdecl call with an explicit stack image ---------------- */
@@ -247,7 +269,7 @@ WRAP_STUB(8) WRAP_STUB(9) WRAP_STUB(10) WRAP_STUB(11) WRAP_STUB(12) WRAP_STUB(13
 
 /* ---------------- protocol ---------------- */
 enum { OP_WRITE = 1, OP_READ, OP_ALLOC, OP_FREE, OP_CALL, OP_INFO, OP_SETCW, OP_EVENTS, OP_HEAPCHECK, OP_SCANALL, OP_POISON,
-       OP_PROGRET, OP_QUIT, OP_WRAP };
+       OP_PROGRET, OP_QUIT, OP_WRAP, OP_HOOK, OP_HOOKRET, OP_FOREACH, OP_FOREACHLOG };
 #define IMAGE_BASE 0x400000u
 #define IMAGE_SIZE 0x100000u
 
@@ -318,6 +340,14 @@ void _start_c(void)
             a = (u32) stubs[hdr[1]];
             wr(&a, 4);
         } break;
+        case OP_HOOK: {       /* hdr[1] n-th update event from now (0: disarm), hdr[2] function, hdr[3] its one argument */
+            u32 ok = 1;
+            hook_at = hdr[1]; hook_fn = hdr[2]; hook_arg = hdr[3]; hook_seen = 0; hook_fired = 0; hook_ret = 0;
+            wr(&ok, 4);
+        } break;
+        case OP_HOOKRET: { u32 r[2]; r[0] = hook_fired; r[1] = hook_ret; wr(r, 8); } break;
+        case OP_FOREACH: { u32 a = (u32) cb_foreach; fe_n = 0; fe_stop = hdr[1]; fe_stop_ret = hdr[2]; wr(&a, 4); } break;
+        case OP_FOREACHLOG: { u32 n = fe_n; wr(&n, 4); wr(fe_carver, sizeof fe_carver); wr(fe_tok, sizeof fe_tok); } break;
         case OP_QUIT: die(0);
         default: die(85);
         }
