@@ -276,6 +276,25 @@ def bind_control(api):
     return api
 
 
+# include/lqr_sizes.h: a carver read at many sizes in one pass over its pixels and map
+SIZES_SYMBOLS = {
+    "lqrx_carver_size_range": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "lqrx_carver_read_sizes_device": (_I, [_P, C.POINTER(_I), _I, C.POINTER(_P)]),
+    "lqrx_carver_read_sizes": (_I, [_P, C.POINTER(_I), _I, C.POINTER(_P)]),
+}
+
+
+def bind_sizes(api):
+    """add SIZES_SYMBOLS to a bound Api (the engine: a genuine liblqr-1 has none of them); returns it"""
+    if not getattr(api, "has_sizes", False):
+        for name, (res, args) in SIZES_SYMBOLS.items():
+            fn = getattr(api.lib, api.prefix + name)      # AttributeError = missing export
+            fn.restype, fn.argtypes = res, args
+            setattr(api, name, fn)
+        api.has_sizes = True
+    return api
+
+
 def _vmap_new(api, m):
     """a LqrVMap around a malloc'd copy of m["data"] (h x w int32, image orientation), which the map owns"""
     data = np.ascontiguousarray(m["data"], dtype=np.int32)
@@ -329,6 +348,11 @@ def engine_energy_api():
 def engine_vmap_api():
     """the engine with the colour-depth and seam-map loading surfaces bound"""
     return bind_vmap(bind_coldepth(engine_api()))
+
+
+def engine_sizes_api():
+    """the engine with the colour-depth and many-sizes surfaces bound"""
+    return bind_sizes(bind_coldepth(engine_api()))
 
 
 def engine_control_api():
@@ -828,6 +852,44 @@ class Carver:
         assert tensor.is_cuda and tensor.is_contiguous() and tensor.dim() == 2 and tensor.dtype == torch.int32
         torch.cuda.current_stream().synchronize()          # the engine reads the buffer on a stream of its own
         return bind_vmap(self.api).lqrx_vmap_load_device(self.p, tensor.data_ptr(), tensor.shape[1], tensor.shape[0], int(depth), int(orientation))
+
+    # -- many sizes in one pass (include/lqr_sizes.h)
+    def size_range(self):
+        """lqrx_carver_size_range: (direction, smallest size, largest size)"""
+        lo, hi = C.c_int(0), C.c_int(0)
+        d = bind_sizes(self.api).lqrx_carver_size_range(self.p, C.byref(lo), C.byref(hi))
+        return d, lo.value, hi.value
+
+    def _sizes_shape(self, size):
+        """the image at `size` in the direction of the map: (rows, columns, channels)"""
+        a = self.api
+        if a.lqr_carver_get_orientation(self.p):
+            return int(size), a.lqr_carver_get_width(self.p), self.ch
+        return a.lqr_carver_get_height(self.p), int(size), self.ch
+
+    def read_sizes(self, sizes):
+        """lqrx_carver_read_sizes: a list of numpy arrays (rows x columns x channels of the carver's dtype), one per size"""
+        dt, _ = self._px()
+        outs = [np.zeros(self._sizes_shape(s), dt) for s in sizes]
+        arr = (C.c_int * len(outs))(*[int(s) for s in sizes])
+        ptrs = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+        ret = bind_sizes(self.api).lqrx_carver_read_sizes(self.p, arr, len(outs), ptrs)
+        if ret != LQR_OK:
+            raise MemoryError("lqrx_carver_read_sizes") if ret == LQR_NOMEM else ValueError("lqrx_carver_read_sizes returned %d" % ret)
+        return outs
+
+    def read_sizes_device(self, sizes, tensors):
+        """lqrx_carver_read_sizes_device into torch tensors on the device, one per size: each contiguous, of the carver's dtype (any
+        dtype of the same item size) and of at least rows x columns x channels elements; returns the LqrRetVal"""
+        dt, _ = self._px()
+        assert len(sizes) == len(tensors)
+        for s, t in zip(sizes, tensors):
+            rows, cols, ch = self._sizes_shape(s)
+            assert t.is_cuda and t.is_contiguous() and t.element_size() == dt.itemsize and t.numel() >= rows * cols * ch
+        torch.cuda.current_stream().synchronize()          # the engine writes the buffers on a stream of its own
+        arr = (C.c_int * len(sizes))(*[int(s) for s in sizes])
+        ptrs = (C.c_void_p * len(sizes))(*[t.data_ptr() for t in tensors])
+        return bind_sizes(self.api).lqrx_carver_read_sizes_device(self.p, arr, len(sizes), ptrs)
 
     def vmap_internal_dump(self):
         return bind_vmap(self.api).lqr_vmap_internal_dump(self.p)

@@ -12,6 +12,7 @@
 //   k_oneoff.hip     E8(vs)/E11/E12/E14, auto-size  k_vs_commit, k_inflate, k_vmap_check(_t), k_compact(_jobs), k_transpose(_px), k_mask_line_max
 //   k_masks.hip      E2 (lqr_masks.h) k_mask_add_f (float / double masks, host or device), k_mask_scatter (queued _xy calls), k_plane_transpose
 //   k_energy_out.hip energy read-outs (lqr_energy.h) k_energy_range (squash, min / max per workgroup), k_energy_out (normalise, expand to pixels, image orientation)
+//   k_sizes.hip      many sizes in one pass (lqr_sizes.h) k_compact_sizes (up to 64 levels ranked from one load of a row), k_transpose_sizes (a width per job)
 //   lqr_shim.hip     the lqrhip_* C ABI of include/lqr_hip.h: allocation cache, batches, the per-seam launch sequence
 //   lqr_plan.h       which form of each stage that sequence runs (plain C++17, no HIP: also compiled alone by tests/test_plan.py)
 //   lqr_beside.h     k_carve_v's side bound, work-list entries and their readiness (plain C++17, no HIP: also compiled alone by tests/test_backtrack_beside.py)
@@ -527,6 +528,15 @@ struct InflateDev {
     float *nbias, *nrig;
     int ch;                 // bytes per pixel
     int depth;              // LqrColDepth (read by k_inflate<true> only: how new pixels are averaged)
+};
+// a job of the many-sizes read-out (k_sizes.hip): one size of one carver.  k_compact_sizes writes the pixels visible at `level`, `width`
+// of them per frame row, to `out`; k_transpose_sizes turns the plane `src` (width x h, frame orientation) into `out` (h x width)
+#define SZ_MAX_JOBS 64      // jobs per launch
+#define SZ_CHUNK 1024       // columns of a frame row a workgroup of k_compact_sizes holds at a time: 256 lanes x 4
+struct SizeJob {
+    uint8_t *out;
+    const uint8_t *src;     // k_transpose_sizes only
+    int level, width;
 };
 // How a carver that reads through the value plane (lqr_pixel.h) forms the value its energy reads: liblqr's image type
 // (lqr_imagetype.h) reduced to the arithmetic it selects, the alpha and black channel indices (-1: none), brightness or luma

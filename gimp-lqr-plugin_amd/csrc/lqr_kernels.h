@@ -100,6 +100,13 @@ __global__ void k_transpose(const InflateDev *jobs, int w, int h);
 __global__ void k_transpose_px(const InflateDev *jobs, int w, int h);
 __global__ __launch_bounds__(256) void k_mask_line_max(const uint8_t *mask, int channels, int width, int a0, int b0, int line_len, int direction, int *out);
 
+// k_sizes.hip (a carver read at many sizes in one pass, include/lqr_sizes.h).  X(DEEP): base-layout pixels wider than 4 bytes;
+// X(WIDE) of the transposition: the same split (jobs' pixels move through an LDS tile of dwords, or pixel by pixel)
+#define K_COMPACT_SIZES_FORMS(X) X(false) X(true)
+#define K_TRANSPOSE_SIZES_FORMS(X) X(false) X(true)
+template <bool DEEP> __global__ __launch_bounds__(256) void k_compact_sizes(const uint8_t *rgb, const int32_t *vs, const SizeJob *jobs, int n_jobs, int w0, int bytes);
+template <bool WIDE> __global__ __launch_bounds__(256) void k_transpose_sizes(const SizeJob *jobs, int h, int bytes);
+
 // k_masks.hip (computed masks, include/lqr_masks.h: T = float or double)
 template <class T> __global__ __launch_bounds__(256) void k_mask_add_f(float *plane, int w0, const T *mask, int mw, int x0, int y0, int x1, int y1, int nx, int ny,
                                                                        int transposed, int is_rig, int bias_factor);

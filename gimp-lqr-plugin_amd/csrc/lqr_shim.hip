@@ -1835,6 +1835,82 @@ extern "C" int lqrhip_read_visible_device(LqrHipCarver *c, int w0, int h0, int w
     return 0;
 }
 
+// lqr_sizes.h: many sizes from one pass.  The sizes are served in chunks of at most SZ_MAX_JOBS, one k_compact_sizes launch each.  Only a
+// device caller of a carver that is not transposed gets the compaction's stores directly; otherwise a size passes through scratch
+// planes -- one in frame orientation in front of k_transpose_sizes, one in front of the copy to the host -- and a chunk ends where
+// its planes would pass SZ_SCRATCH_MAX.  The job table of the whole call and one scratch block (the largest chunk's, reused: the
+// chunks follow each other on one stream) are taken before the first launch.
+static const size_t SZ_SCRATCH_MAX = (size_t) 512 << 20;
+extern "C" int lqrhip_read_sizes(LqrHipCarver *c, int w0, int h0, int transposed, const int *levels, int n, void *const *outs, int on_device)
+{
+    int rc = batch_sync_of(c);
+    if (rc) return rc;
+    if (n < 1 || !levels || !outs || w0 < 1 || h0 < 1) return LQRHIP_EARG;
+    for (int k = 0; k < n; k++)
+        if (levels[k] < 1 || levels[k] > w0 || !outs[k]) return LQRHIP_EARG;
+    const size_t bytes = px_bytes(c);
+    const int planes = (on_device ? 0 : 1) + (transposed ? 1 : 0);          // scratch planes a size passes through
+    auto width_of = [&](int k) { return w0 - levels[k] + 1; };
+    auto plane_bytes = [&](int k) { return ((size_t) width_of(k) * h0 * bytes + 255) & ~(size_t) 255; };
+    struct Chunk { int first, count; };
+    std::vector<Chunk> chunks;
+    size_t scratch_bytes = 0;
+    for (int k = 0; k < n;) {
+        size_t used = 0;
+        int m = 0;
+        while (k + m < n && m < SZ_MAX_JOBS && (m == 0 || used + planes * plane_bytes(k + m) <= SZ_SCRATCH_MAX)) used += planes * plane_bytes(k + m), m++;
+        chunks.push_back(Chunk{k, m});
+        scratch_bytes = std::max(scratch_bytes, used);
+        k += m;
+    }
+    std::vector<SizeJob> jobs(2 * (size_t) n);                               // (outlives the Scratch, which waits for the copy that reads it)
+    std::vector<const uint8_t *> result(n);                                  // where the host copy finds image k
+    Scratch tmp(g_stream0);
+    SizeJob *d_jobs = tmp.get<SizeJob>(2 * (size_t) n, "&d_jobs", rc);      // [0, n) the compactions, [n, 2 n) the transpositions
+    if (rc) return rc;
+    uint8_t *scratch = nullptr;
+    if (planes) {
+        scratch = tmp.get<uint8_t>(scratch_bytes, "&scratch", rc);
+        if (rc) return rc;
+    }
+    for (const Chunk &ch : chunks) {
+        size_t at = 0;
+        for (int k = ch.first; k < ch.first + ch.count; k++) {
+            uint8_t *frame = (uint8_t *) outs[k], *image = (uint8_t *) outs[k];
+            if (planes) { frame = scratch + at; at += plane_bytes(k); }
+            if (transposed && !on_device) { image = scratch + at; at += plane_bytes(k); }
+            jobs[k] = SizeJob{frame, nullptr, levels[k], width_of(k)};
+            jobs[n + k] = SizeJob{image, frame, levels[k], width_of(k)};
+            result[k] = transposed ? image : frame;
+        }
+    }
+    HIPCK(hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(SizeJob), hipMemcpyHostToDevice, g_stream0));
+    for (const Chunk &ch : chunks) {
+#define LAUNCH_CS(DEEP) hipLaunchKernelGGL(k_compact_sizes<DEEP>, dim3(h0), dim3(256), 0, g_stream0, (const uint8_t *) c->rgb0.get(), (const int32_t *) vs_of(c), \
+                                           (const SizeJob *) (d_jobs + ch.first), ch.count, w0, (int) bytes)
+        if (bytes > 4) LAUNCH_CS(true); else LAUNCH_CS(false);
+#undef LAUNCH_CS
+        CENSUS(LQRHIP_CENSUS_COMPACT_SIZES);
+        HIPCK(hipGetLastError());
+        if (transposed) {
+            int wmax = 0;
+            for (int k = ch.first; k < ch.first + ch.count; k++) wmax = std::max(wmax, width_of(k));
+            const dim3 grid((wmax + 31) / 32, (h0 + 31) / 32, (unsigned) ch.count);
+#define LAUNCH_TS(WIDE) hipLaunchKernelGGL(k_transpose_sizes<WIDE>, grid, dim3(256), 0, g_stream0, (const SizeJob *) (d_jobs + n + ch.first), h0, (int) bytes)
+            if (bytes > 4) LAUNCH_TS(true); else LAUNCH_TS(false);
+#undef LAUNCH_TS
+            CENSUS(LQRHIP_CENSUS_TRANSPOSE_SIZES);
+            HIPCK(hipGetLastError());
+        }
+        if (!on_device)
+            for (int k = ch.first; k < ch.first + ch.count; k++)
+                if ((rc = d2h_staged(outs[k], result[k], (size_t) width_of(k) * h0 * bytes))) return rc;
+    }
+    HIPCK(hipStreamSynchronize(g_stream0));
+    tmp.done();
+    return 0;
+}
+
 extern "C" int lqrhip_mask_line_max(const unsigned char *mask, int channels, int width, int height, int a0, int b0, int n_lines,
                                     int line_len, int direction)
 {

@@ -31,6 +31,7 @@
 #include "../../include/lqr_energy.h"
 #include "../../include/lqr_vmap.h"
 #include "../../include/lqr_control.h"
+#include "../../include/lqr_sizes.h"
 #include "../../include/lqr_hip.h"
 #include "lqr_mask_queue.h"
 #include "lqr_sched.h"
@@ -1351,6 +1352,43 @@ LqrRetVal lqrx_carver_read_image_device(LqrCarver *r, void *device_ptr)
     HIP_CATCH(lqrhip_read_visible_device(r->dev, r->geo.w0, r->geo.h0, r->geo.w, r->geo.level, device_ptr));
     return LQR_OK;
 }
+
+/* ======================= many sizes in one pass (lqr_sizes.h) ============= */
+/* (an attached carver follows its root's walk: the root's enlargement step) */
+static void size_range(const LqrCarver *r, int *lo, int *hi)
+{
+    lqr_geom_size_range(&r->geo, (r->root ? r->root : r)->enl_step, lo, hi);
+}
+
+gint lqrx_carver_size_range(LqrCarver *r, gint *min_size, gint *max_size)
+{
+    int lo, hi;
+    if (!r) return -1;
+    size_range(r, &lo, &hi);
+    if (min_size) *min_size = lo;
+    if (max_size) *max_size = hi;
+    return r->geo.transposed ? 1 : 0;
+}
+
+/* a pure read: the geometry, the read-out cache and the state word are neither consulted nor changed */
+static LqrRetVal read_sizes(LqrCarver *r, const gint *sizes, gint n, void *const *out, int on_device)
+{
+    int lo, hi, k, rc;
+    int *levels;
+    if (!r || !sizes || !out || n < 1) return LQR_ERROR;
+    size_range(r, &lo, &hi);
+    for (k = 0; k < n; k++)
+        if (!out[k] || sizes[k] < lo || sizes[k] > hi) return LQR_ERROR;
+    levels = (int *) malloc((size_t) n * sizeof *levels);
+    if (!levels) return LQR_NOMEM;
+    for (k = 0; k < n; k++) levels[k] = r->geo.w0 - sizes[k] + 1;
+    rc = lqrhip_read_sizes(r->dev, r->geo.w0, r->geo.h0, r->geo.transposed, levels, n, out, on_device);
+    free(levels);
+    return hip_ret(rc);
+}
+
+LqrRetVal lqrx_carver_read_sizes_device(LqrCarver *r, const gint *sizes, gint n, void *const *device_out) { return read_sizes(r, sizes, n, device_out, 1); }
+LqrRetVal lqrx_carver_read_sizes(LqrCarver *r, const gint *sizes, gint n, void *const *host_out) { return read_sizes(r, sizes, n, host_out, 0); }
 
 /* ======================= seam-map colour ramp (I5) ======================== */
 LqrRetVal lqrx_vmap_to_rgba(LqrVMap *v, const gdouble col_start[3], const gdouble col_end[3], guchar *out_rgba)

@@ -143,6 +143,12 @@ int lqr_walk_needs_maps(const LqrGeom *g, float enl_step, int w1, int want_trans
     return 0;
 }
 
+void lqr_geom_size_range(const LqrGeom *g, float enl_step, int *lo, int *hi)
+{
+    *lo = g->w_start - (g->max_level - 1);
+    *hi = g->w_start + MINI(g->max_level - 1, lqr_sched_delta_max(enl_step, g->w_start));
+}
+
 /* ======================= one session ===================================== */
 void lqr_session_begin(LqrSession *s, int max_level, int depth, int wc0, int lr_switch_frequency, int rescale_current, int rescale_total,
                        int update_step)

@@ -65,6 +65,12 @@ int lqr_walk_frame_refused(const LqrGeom *g, float enl_step, int w1, int want_tr
 /* a carver that cannot build maps: some step would need a transposition, a depth beyond max_level, or a second step */
 int lqr_walk_needs_maps(const LqrGeom *g, float enl_step, int w1, int want_transposed);
 
+/* the sizes of the current direction that lqr_walk_needs_maps refuses nothing of, as a closed form: one step, no session, no
+ * transposition, no second step -- [w_start - (max_level - 1), w_start + min(max_level - 1, delta_max)].  (The walk also lets the
+ * current width pass, whatever it is, because there is nothing to do: it lies inside the interval unless the enlargement step was
+ * lowered after the carver was enlarged.) */
+void lqr_geom_size_range(const LqrGeom *g, float enl_step, int *lo, int *hi);
+
 /* ---- one session (one visibility-map build) ---- */
 typedef struct LqrSession {
     int max_level, depth;       /* seams l = max_level .. depth - 1 */

@@ -257,6 +257,12 @@ int lqrhip_mask_line_max(const unsigned char *mask, int channels, int width, int
                          int direction);
 /* same, but into a caller-provided device buffer (no host round trip) */
 int lqrhip_read_visible_device(LqrHipCarver *c, int w0, int h0, int w, int level, void *device_out);
+/* lqr_sizes.h: the pixels visible at each of n levels (image k is w0 - levels[k] + 1 wide in the carver's frame), every image in
+ * IMAGE orientation (transposed: the carver lies transposed, its frame rows are image columns), to outs[k] in device memory
+ * (on_device; any multiple of the sample size) or in host memory.  One pass over the base layout per 64 sizes (and per 512 MiB of
+ * scratch planes where the images do not go straight to the caller's device memory): LQRHIP_CENSUS_COMPACT_SIZES counts them.
+ * Everything is allocated before anything is launched: LQRHIP_ENOMEM has written nothing.  Returns with the outputs written. */
+int lqrhip_read_sizes(LqrHipCarver *c, int w0, int h0, int transposed, const int *levels, int n, void *const *outs, int on_device);
 int lqrhip_device_sync(void);
 /* free / total device memory in bytes (hipMemGetInfo) and the bytes the shim's allocation cache holds */
 int lqrhip_mem_info(unsigned long long *free_bytes, unsigned long long *total_bytes, unsigned long long *cached_bytes);
@@ -364,6 +370,8 @@ enum {
     LQRHIP_CENSUS_SWEEP_UPDATE = 26,    /* ... and the launches behind a band kernel (E9) */
     LQRHIP_CENSUS_LDS_ATTR_SWEEP = 27,  /* k_dp_sweep launches with more than 64 KB of dynamic LDS (hipFuncSetAttribute first) */
     LQRHIP_CENSUS_LDS_ATTR_COMMIT = 28, /* k_vs_commit launches with more than 64 KB of dynamic LDS */
+    LQRHIP_CENSUS_COMPACT_SIZES = 29,   /* lqrhip_read_sizes: k_compact_sizes, one launch per chunk of sizes */
+    LQRHIP_CENSUS_TRANSPOSE_SIZES = 30, /*     k_transpose_sizes, likewise (a carver that lies transposed) */
     LQRHIP_CENSUS_SLOTS = 32
 };
 int lqrhip_launch_census(unsigned long long *out, int n, int reset);
