@@ -295,6 +295,33 @@ def bind_sizes(api):
     return api
 
 
+# include_ext/lqr_forward.h: forward-energy seam maps built on the device (into device memory, as a caller-owned LqrVMap, for a batch),
+# loaded in place, and the resize made of the two.  The engine's own: a genuine liblqr-1 has none of them
+FORWARD_SYMBOLS = {
+    "lqrx_carver_forward_map_device": (_I, [_P, _I, _I, _P]),
+    "lqrx_carver_forward_map": (_P, [_P, _I, _I]),
+    "lqrx_carver_forward_maps_device": (_I, [C.POINTER(_P), _I, _I, _I, C.POINTER(_P)]),
+    "lqrx_carver_load_forward": (_I, [_P, _I, _I]),
+    "lqrx_carver_resize_forward": (_I, [_P, _I, _I]),
+}
+
+
+def bind_forward(api):
+    """add FORWARD_SYMBOLS (and VMAP_SYMBOLS) and the build's test hooks to a bound Api (the engine); returns it"""
+    bind_vmap(api)
+    if not getattr(api, "has_forward", False):
+        for name, (res, args) in FORWARD_SYMBOLS.items():
+            fn = getattr(api.lib, api.prefix + name)      # AttributeError = missing export
+            fn.restype, fn.argtypes = res, args
+            setattr(api, name, fn)
+        api.lqrhip_forward_launches = api.lib.lqrhip_forward_launches
+        api.lqrhip_forward_launches.restype, api.lqrhip_forward_launches.argtypes = C.c_ulonglong, [_I]
+        api.lqrhip_read_forward_intensity = api.lib.lqrhip_read_forward_intensity
+        api.lqrhip_read_forward_intensity.restype, api.lqrhip_read_forward_intensity.argtypes = _I, [_P, _I, _P]
+        api.has_forward = True
+    return api
+
+
 def _vmap_new(api, m):
     """a LqrVMap around a malloc'd copy of m["data"] (h x w int32, image orientation), which the map owns"""
     data = np.ascontiguousarray(m["data"], dtype=np.int32)
@@ -353,6 +380,11 @@ def engine_vmap_api():
 def engine_sizes_api():
     """the engine with the colour-depth and many-sizes surfaces bound"""
     return bind_sizes(bind_coldepth(engine_api()))
+
+
+def engine_forward_api():
+    """the engine with the colour-depth, seam-map loading and forward-energy surfaces bound"""
+    return bind_forward(bind_coldepth(engine_api()))
 
 
 def engine_control_api():
@@ -853,6 +885,44 @@ class Carver:
         torch.cuda.current_stream().synchronize()          # the engine reads the buffer on a stream of its own
         return bind_vmap(self.api).lqrx_vmap_load_device(self.p, tensor.data_ptr(), tensor.shape[1], tensor.shape[0], int(depth), int(orientation))
 
+
+    # -- forward-energy seam maps (include_ext/lqr_forward.h)
+    def _forward_line(self, orientation):
+        a = self.api
+        return a.lqr_carver_get_height(self.p) if orientation else a.lqr_carver_get_width(self.p)
+
+    def forward_map(self, depth, orientation):
+        """lqrx_carver_forward_map: the dict vmap_dump returns, or None where the call returned NULL"""
+        a = bind_forward(self.api)
+        v = a.lqrx_carver_forward_map(self.p, int(depth), int(orientation))
+        if not v:
+            return None
+        d = self._vmap_to_dict(v)
+        a.lqr_vmap_destroy(v)
+        return d
+
+    def forward_map_device(self, tensor, depth, orientation):
+        """lqrx_carver_forward_map_device into a contiguous h x w int32 torch tensor on the device; the LqrRetVal"""
+        assert tensor.is_cuda and tensor.is_contiguous() and tensor.dtype == torch.int32
+        assert tensor.numel() >= self.api.lqr_carver_get_width(self.p) * self.api.lqr_carver_get_height(self.p)
+        torch.cuda.current_stream().synchronize()          # the engine writes the buffer on a stream of its own
+        return bind_forward(self.api).lqrx_carver_forward_map_device(self.p, int(depth), int(orientation), tensor.data_ptr())
+
+    def load_forward(self, depth, orientation):
+        return bind_forward(self.api).lqrx_carver_load_forward(self.p, int(depth), int(orientation))
+
+    def resize_forward(self, w1, h1):
+        return bind_forward(self.api).lqrx_carver_resize_forward(self.p, int(w1), int(h1))
+
+    def forward_intensity(self, orientation):
+        """test hook: the I plane a forward build forms for this (flat) carver, lines x line length float32 in the carving frame"""
+        a = bind_forward(self.api)
+        w, h = a.lqr_carver_get_width(self.p), a.lqr_carver_get_height(self.p)
+        out = np.zeros((w, h) if orientation else (h, w), np.float32)
+        ret = a.lqrhip_read_forward_intensity(self.p, int(orientation), out.ctypes.data)
+        assert ret == 0, ret
+        return out
+
     # -- many sizes in one pass (include/lqr_sizes.h)
     def size_range(self):
         """lqrx_carver_size_range: (direction, smallest size, largest size)"""
@@ -972,3 +1042,14 @@ def vmap_load_batch(carvers, m):
 def resize_batch(api, carvers, w1, h1):
     arr = (C.c_void_p * len(carvers))(*[c.p for c in carvers])
     return api.lqrx_carver_resize_batch(arr, len(carvers), int(w1), int(h1))
+
+
+def forward_maps_device(carvers, tensors, depth, orientation):
+    """lqrx_carver_forward_maps_device: one contiguous int32 torch tensor on the device per carver; the LqrRetVal"""
+    a = bind_forward(carvers[0].api)
+    for t in tensors:
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32
+    torch.cuda.current_stream().synchronize()
+    arr = (C.c_void_p * len(carvers))(*[c.p for c in carvers])
+    ptrs = (C.c_void_p * len(carvers))(*[t.data_ptr() for t in tensors])
+    return a.lqrx_carver_forward_maps_device(arr, len(carvers), int(depth), int(orientation), ptrs)

@@ -13,6 +13,7 @@
 //   k_masks.hip      E2 (lqr_masks.h) k_mask_add_f (float / double masks, host or device), k_mask_scatter (queued _xy calls), k_plane_transpose
 //   k_energy_out.hip energy read-outs (lqr_energy.h) k_energy_range (squash, min / max per workgroup), k_energy_out (normalise, expand to pixels, image orientation)
 //   k_sizes.hip      many sizes in one pass (lqr_sizes.h) k_compact_sizes (up to 64 levels ranked from one load of a row), k_transpose_sizes (a width per job)
+//   k_forward.hip    forward-energy seam maps (include_ext/lqr_forward.h) k_fwd_init (I, P, positions from the base layouts), k_fwd_seam (sweep, pick, walk: one workgroup per image), k_fwd_remove
 //   lqr_shim.hip     the lqrhip_* C ABI of include/lqr_hip.h: allocation cache, batches, the per-seam launch sequence
 //   lqr_plan.h       which form of each stage that sequence runs (plain C++17, no HIP: also compiled alone by tests/test_plan.py)
 //   lqr_beside.h     k_carve_v's side bound, work-list entries and their readiness (plain C++17, no HIP: also compiled alone by tests/test_backtrack_beside.py)
@@ -559,3 +560,22 @@ struct DeepRead {
 #define EO_CHUNK 1024
 #define EO_MAX_PARTIALS 512
 #define EO_TILE 64
+// forward-energy seam maps (k_forward.hip, include_ext/lqr_forward.h).  One workgroup of FWD_THREADS per image sweeps the rows of a frame, a
+// thread taking the pixels tid + k * FWD_THREADS, k < PXT (PXT = 1 .. FWD_MAX_PXT: lines of up to FWD_THREADS * PXT pixels); the walk
+// stages the choices of FWD_WALK_ROWS rows around the seam in LDS at a time; the removal moves FWD_REMOVE_PX pixels per thread and round
+#define FWD_THREADS 1024
+#define FWD_MAX_PXT 16
+#define FWD_WALK_ROWS 64
+#define FWD_REMOVE_THREADS 256
+#define FWD_REMOVE_PX 4
+// one image of a forward build: where its pixels and bias lie (the carver's base layout) and the builder's planes, H lines of L
+struct FwdJob {
+    const uint8_t *rgb0;
+    const float *bias0;     // null: no bias plane, P is 0 and `p` is null too
+    float *in;              // I: the value the energy reads, as a float, current frame
+    float *p;               // P: bias / w_start, current frame
+    uint16_t *pos;          // where each pixel of the current frame stood on its line at the start
+    int8_t *choice;         // the parent each pixel of the last sweep chose: -1, 0, 1
+    int32_t *seam;          // the last seam: a column per line
+    int32_t *map;           // the result, image orientation
+};

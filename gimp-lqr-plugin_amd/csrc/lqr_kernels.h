@@ -107,6 +107,14 @@ __global__ __launch_bounds__(256) void k_mask_line_max(const uint8_t *mask, int 
 template <bool DEEP> __global__ __launch_bounds__(256) void k_compact_sizes(const uint8_t *rgb, const int32_t *vs, const SizeJob *jobs, int n_jobs, int w0, int bytes);
 template <bool WIDE> __global__ __launch_bounds__(256) void k_transpose_sizes(const SizeJob *jobs, int h, int bytes);
 
+// k_forward.hip (forward-energy seam maps, include_ext/lqr_forward.h).  X(DEPTH) of the one-off pass: LqrColDepth; X(PXT) of the seam kernel:
+// pixels per thread.  One workgroup per image in k_fwd_seam (grid n), one per line and image in k_fwd_remove (grid H x n)
+#define K_FWD_INIT_FORMS(X) X(0) X(1) X(2) X(3)
+#define K_FWD_SEAM_FORMS(X) X(1) X(2) X(4) X(8) X(16)
+template <int DEPTH> __global__ __launch_bounds__(256) void k_fwd_init(const FwdJob *jobs, int L, int H, int fw0, int strided, DeepRead rd, int w_start, int orientation);
+template <int PXT> __global__ __launch_bounds__(FWD_THREADS) void k_fwd_seam(const FwdJob *jobs, int wc, int L, int H);
+__global__ __launch_bounds__(FWD_REMOVE_THREADS) void k_fwd_remove(const FwdJob *jobs, int wc, int L, int H, int level, int orientation);
+
 // k_masks.hip (computed masks, include/lqr_masks.h: T = float or double)
 template <class T> __global__ __launch_bounds__(256) void k_mask_add_f(float *plane, int w0, const T *mask, int mw, int x0, int y0, int x1, int y1, int nx, int ny,
                                                                        int transposed, int is_rig, int bias_factor);

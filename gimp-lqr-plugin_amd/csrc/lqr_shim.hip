@@ -10,6 +10,7 @@
 #include "lqr_own.h"
 #include "lqr_pool.h"
 #include "lqr_stage.h"
+#include <atomic>
 #include <memory>
 #include <dirent.h>
 
@@ -1907,6 +1908,165 @@ extern "C" int lqrhip_read_sizes(LqrHipCarver *c, int w0, int h0, int transposed
                 if ((rc = d2h_staged(outs[k], result[k], (size_t) width_of(k) * h0 * bytes))) return rc;
     }
     HIPCK(hipStreamSynchronize(g_stream0));
+    tmp.done();
+    return 0;
+}
+
+// ---- include_ext/lqr_forward.h: forward-energy seam maps (kernels in k_forward.hip) ---------------------------------------------------------
+// A build owns its planes -- per image I, P (with a bias plane), the positions, the choices, the seam, and the map unless the caller
+// gave one -- and the job table, all taken in lqrhip_forward_begin before anything is launched.  It runs on g_stream0; the two events
+// are the ends of the last two slices.
+struct __attribute__((visibility("hidden"))) LqrHipForward {
+    struct Planes {
+        DevBuf<float> in, p;
+        DevBuf<uint16_t> pos;
+        DevBuf<int8_t> choice;
+        DevBuf<int32_t> seam, map;
+    };
+    std::vector<Planes> img;
+    std::vector<FwdJob> jobs;               // (read by the copy to d_jobs)
+    DevBuf<FwdJob> d_jobs;
+    hipEvent_t slice_end[2] = {nullptr, nullptr};
+    int slices = 0, next_seam = 0;
+    int n = 0, L = 0, H = 0, depth = 0, orientation = 0, pxt = 0;
+    size_t lds = 0;
+    ~LqrHipForward()
+    {
+        if (g_stream0) (void) hipStreamSynchronize(g_stream0);      // the planes go back to the pool when the members are destroyed
+        for (hipEvent_t e : slice_end)
+            if (e) (void) hipEventDestroy(e);
+        (void) hipGetLastError();
+    }
+};
+// (atomic, relaxed: a second thread may poll the hook while a build counts, lqr_hip.h)
+static std::atomic<unsigned long long> g_forward_launches{0};
+extern "C" unsigned long long lqrhip_forward_launches(int reset)
+{
+    return reset ? g_forward_launches.exchange(0, std::memory_order_relaxed) : g_forward_launches.load(std::memory_order_relaxed);
+}
+// the job of carver c: its base layout and the planes pl, the map `map`
+static FwdJob forward_job(const LqrHipCarver *c, const LqrHipForward::Planes &pl, int32_t *map)
+{
+    return FwdJob{c->rgb0, c->bias0, pl.in, pl.p, pl.pos, pl.choice, pl.seam, map};
+}
+// the one-off pass for n jobs of carvers that read like c0
+static int forward_launch_init(const LqrHipCarver *c0, const FwdJob *d_jobs, int n, int L, int H, int strided, int luma, int w_start, int orientation)
+{
+    DeepRead rd = deep_read(c0);
+    rd.luma = luma != 0;
+    const dim3 grid((L + 255) / 256, H, (unsigned) n);
+#define CASE(D) if (c0->depth == D) hipLaunchKernelGGL(k_fwd_init<D>, grid, dim3(256), 0, g_stream0, d_jobs, L, H, c0->w0, strided, rd, w_start, orientation); else
+    K_FWD_INIT_FORMS(CASE) return no_form("k_fwd_init");
+#undef CASE
+    g_forward_launches.fetch_add(1, std::memory_order_relaxed);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+extern "C" int lqrhip_forward_begin(LqrHipCarver *const *cs, int n, int depth, int orientation, int transposed, int luma, int w_start,
+                                    void *const *device_maps, LqrHipForward **out)
+{
+    if (out) *out = nullptr;
+    if (!cs || !out || n < 1 || n > LQRHIP_FORWARD_MAX_LINES || (orientation != 0 && orientation != 1) || w_start < 1) { g_err = "forward map: arguments"; return LQRHIP_EARG; }
+    const LqrHipCarver *c0 = cs[0];
+    for (int i = 0; i < n; i++) {
+        const LqrHipCarver *c = cs[i];
+        if (!c || c->root || c->w0 != c0->w0 || c->h0 != c0->h0 || c->ch != c0->ch || c->depth != c0->depth || c->mode != c0->mode ||
+            c->alpha != c0->alpha || c->black != c0->black || (device_maps && !device_maps[i])) {
+            g_err = "forward map: root carvers of one shape and pixel kind, a map for each";
+            return LQRHIP_EARG;
+        }
+    }
+    const int strided = (transposed != 0) != (orientation != 0);
+    const int L = strided ? c0->h0 : c0->w0, H = strided ? c0->w0 : c0->h0;
+    if (depth < 1 || depth >= L || L > FWD_THREADS * FWD_MAX_PXT || L > LQRHIP_MAX_FRAME_WIDTH || H > LQRHIP_FORWARD_MAX_LINES) {
+        g_err = "forward map: 0 < depth < line length <= " + std::to_string(LQRHIP_MAX_FRAME_WIDTH) + ", at most " + std::to_string(LQRHIP_FORWARD_MAX_LINES) + " lines";
+        return LQRHIP_EARG;
+    }
+    int rc;
+    for (int i = 0; i < n; i++)
+        if ((rc = batch_sync_of(cs[i]))) return rc;     // whatever still writes the base layouts
+    std::unique_ptr<LqrHipForward> f(new LqrHipForward());
+    f->n = n; f->L = L; f->H = H; f->depth = depth; f->orientation = orientation;
+    f->pxt = L <= FWD_THREADS ? 1 : L <= 2 * FWD_THREADS ? 2 : L <= 4 * FWD_THREADS ? 4 : L <= 8 * FWD_THREADS ? 8 : 16;
+    f->lds = (size_t) 2 * L * sizeof(float);
+    const size_t px = (size_t) L * H;
+    f->img.resize(n);
+    for (int i = 0; i < n; i++) {
+        LqrHipForward::Planes &pl = f->img[i];
+        if ((rc = pl.in.alloc(px, "&fwd_in")) || (cs[i]->bias0 && (rc = pl.p.alloc(px, "&fwd_p"))) || (rc = pl.pos.alloc(px, "&fwd_pos")) ||
+            (rc = pl.choice.alloc(px, "&fwd_choice")) || (rc = pl.seam.alloc((size_t) H, "&fwd_seam")) ||
+            (!device_maps && (rc = pl.map.alloc(px, "&fwd_map"))))
+            return rc;
+        f->jobs.push_back(forward_job(cs[i], pl, device_maps ? (int32_t *) device_maps[i] : pl.map.get()));
+    }
+    if ((rc = f->d_jobs.alloc((size_t) n, "&fwd_jobs"))) return rc;
+    for (hipEvent_t &e : f->slice_end) HIPCK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (lds_needs_attr(f->lds)) {
+#define CASE(P) if (f->pxt == P) HIPCK(hipFuncSetAttribute((const void *) k_fwd_seam<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) f->lds)); else
+        K_FWD_SEAM_FORMS(CASE) return no_form("k_fwd_seam");
+#undef CASE
+    }
+    // -- everything is allocated: the first launch
+    HIPCK(hipMemcpyAsync(f->d_jobs, f->jobs.data(), (size_t) n * sizeof(FwdJob), hipMemcpyHostToDevice, g_stream0));
+    if ((rc = forward_launch_init(c0, f->d_jobs, n, L, H, strided, luma, w_start, orientation))) return rc;
+    *out = f.release();
+    return 0;
+}
+extern "C" int lqrhip_forward_seams(LqrHipForward *f, int first_seam, int n_seams)
+{
+    if (!f || first_seam != f->next_seam || n_seams < 1 || first_seam + n_seams > f->depth) { g_err = "forward map: seams out of order or range"; return LQRHIP_EARG; }
+    for (int s = first_seam; s < first_seam + n_seams; s++) {
+        const int wc = f->L - s;
+#define CASE(P) if (f->pxt == P) hipLaunchKernelGGL(k_fwd_seam<P>, dim3((unsigned) f->n), dim3(FWD_THREADS), f->lds, g_stream0, (const FwdJob *) f->d_jobs.get(), wc, f->L, f->H); else
+        K_FWD_SEAM_FORMS(CASE) return no_form("k_fwd_seam");
+#undef CASE
+        hipLaunchKernelGGL(k_fwd_remove, dim3((unsigned) f->H, (unsigned) f->n), dim3(FWD_REMOVE_THREADS), 0, g_stream0, (const FwdJob *) f->d_jobs.get(), wc, f->L,
+                           f->H, s + 1, f->orientation);
+        g_forward_launches.fetch_add(2, std::memory_order_relaxed);
+        HIPCK(hipGetLastError());
+    }
+    f->next_seam = first_seam + n_seams;
+    HIPCK(hipEventRecord(f->slice_end[f->slices & 1], g_stream0));
+    if (f->slices > 0) HIPCK(hipEventSynchronize(f->slice_end[(f->slices - 1) & 1]));
+    f->slices++;
+    return 0;
+}
+extern "C" int lqrhip_forward_finish(LqrHipForward *f)
+{
+    if (!f || f->next_seam != f->depth) { g_err = "forward map: the build is not complete"; return LQRHIP_EARG; }
+    HIPCK(hipStreamSynchronize(g_stream0));
+    return check_dev_error();
+}
+extern "C" const int *lqrhip_forward_map(const LqrHipForward *f, int i)
+{
+    return (f && i >= 0 && i < f->n) ? (const int *) f->jobs[i].map : nullptr;
+}
+extern "C" int lqrhip_forward_read_map(LqrHipForward *f, int i, int *out)
+{
+    if (!f || i < 0 || i >= f->n || !out) return LQRHIP_EARG;
+    return d2h_staged(out, f->jobs[i].map, (size_t) f->L * f->H * sizeof(int32_t));
+}
+extern "C" void lqrhip_forward_release(LqrHipForward *f) { delete f; }
+extern "C" int lqrhip_forward_intensity(LqrHipCarver *c, int orientation, int transposed, int luma, float *out)
+{
+    if (!c || c->root || !out || (orientation != 0 && orientation != 1)) return LQRHIP_EARG;
+    int rc = batch_sync_of(c);
+    if (rc) return rc;
+    const int strided = (transposed != 0) != (orientation != 0);
+    const int L = strided ? c->h0 : c->w0, H = strided ? c->w0 : c->h0;
+    if (L > LQRHIP_MAX_FRAME_WIDTH || H > LQRHIP_FORWARD_MAX_LINES) return LQRHIP_EARG;
+    const size_t px = (size_t) L * H;
+    Scratch tmp(g_stream0);
+    float *in = tmp.get<float>(px, "&fwd_in", rc);
+    uint16_t *pos = rc ? nullptr : tmp.get<uint16_t>(px, "&fwd_pos", rc);
+    int32_t *map = rc ? nullptr : tmp.get<int32_t>(px, "&fwd_map", rc);
+    FwdJob *d_job = rc ? nullptr : tmp.get<FwdJob>(1, "&fwd_jobs", rc);
+    if (rc) return rc;
+    const FwdJob job{c->rgb0, nullptr, in, nullptr, pos, nullptr, nullptr, map};
+    HIPCK(hipMemcpyAsync(d_job, &job, sizeof job, hipMemcpyHostToDevice, g_stream0));
+    HIPCK(hipStreamSynchronize(g_stream0));                         // (`job` is on this frame)
+    if ((rc = forward_launch_init(c, d_job, 1, L, H, strided, luma, 1, orientation))) return rc;
+    if ((rc = d2h_staged(out, in, px * sizeof(float)))) return rc;
     tmp.done();
     return 0;
 }

@@ -32,6 +32,7 @@
 #include "../../include/lqr_vmap.h"
 #include "../../include/lqr_control.h"
 #include "../../include/lqr_sizes.h"
+#include "../../include_ext/lqr_forward.h"
 #include "../../include/lqr_hip.h"
 #include "lqr_mask_queue.h"
 #include "lqr_sched.h"
@@ -1097,6 +1098,175 @@ LqrRetVal lqrx_vmap_load_batch(LqrCarver **carvers, gint n, LqrVMap *vmap)
 {
     if (!vmap) return LQR_ERROR;
     return group_vmap_load(carvers, n, vmap->buffer, 0, vmap->width, vmap->height, vmap->depth, vmap->orientation);
+}
+
+/* ======================= forward-energy seam maps (lqr_forward.h) ========= */
+/* Only the up-front checks and the composition live here: the seams are found by k_forward.hip behind lqrhip_forward_*, the map is
+ * loaded by group_vmap_load_entered like any other. */
+#define FWD_SLICE_SEAMS 16      /* seams enqueued between two looks at the state word (lqr_carver_cancel) */
+
+/* what refuses a map call before any device work; *len: the line length L */
+static LqrRetVal forward_check(LqrCarver *const *rs, int n, int depth, int orientation, const char *who, int *len)
+{
+    int i, L, H;
+    const char *why = NULL;
+    if (!rs || n < 1 || (orientation != 0 && orientation != 1)) why = "NULL or bad arguments";
+    else if (n > LQRHIP_FORWARD_MAX_LINES) why = "more carvers than one build takes";
+    for (i = 0; !why && i < n; i++) {
+        if (!rs[i]) why = "NULL carver";
+        else if (rs[i]->root) why = "an attached carver follows its root";
+        else if (i && !same_config(rs[0], rs[i])) why = "the carvers are not of one configuration";
+    }
+    if (why) { fprintf(stderr, "liblqr-hip: %s refused: %s\n", who, why); return LQR_ERROR; }
+    L = orientation ? lqr_carver_get_height(rs[0]) : lqr_carver_get_width(rs[0]);
+    H = orientation ? lqr_carver_get_width(rs[0]) : lqr_carver_get_height(rs[0]);
+    if (depth < 1 || depth >= L || L > LQRHIP_MAX_FRAME_WIDTH || H > LQRHIP_FORWARD_MAX_LINES) {
+        fprintf(stderr, "liblqr-hip: %s refused: depth %d on %d lines of %d (0 < depth < line length <= %d, at most %d lines)\n", who, depth, H, L,
+                LQRHIP_MAX_FRAME_WIDTH, LQRHIP_FORWARD_MAX_LINES);
+        return LQR_ERROR;
+    }
+    *len = L;
+    return LQR_OK;
+}
+
+/* the slices of a build, a check point in front of each */
+static LqrRetVal forward_slices(LqrCarver *const *rs, int n, LqrHipForward *f, int depth)
+{
+    int first, i;
+    for (first = 0; first < depth; first += FWD_SLICE_SEAMS) {
+        for (i = 0; i < n; i++)
+            if (lqr_state_check(&rs[i]->state)) return LQR_USRCANCEL;
+        HIP_CATCH(lqrhip_forward_seams(f, first, MINI(FWD_SLICE_SEAMS, depth - first)));
+    }
+    for (i = 0; i < n; i++)
+        if (lqr_state_check(&rs[i]->state)) return LQR_USRCANCEL;
+    HIP_CATCH(lqrhip_forward_finish(f));
+    return LQR_OK;
+}
+
+/* Inside the call (roots_enter): flatten what is not flat, then the build.  device_maps NULL: the build keeps the maps.  On LQR_OK *out
+ * holds the finished build, which the caller releases; otherwise nothing is left */
+static LqrRetVal forward_build_entered(LqrCarver **rs, int n, int depth, int orientation, int L, gint *const *device_maps, LqrHipForward **out)
+{
+    LqrHipCarver **ds;
+    LqrHipForward *f = NULL;
+    LqrRetVal ret;
+    int i;
+    *out = NULL;
+    for (i = 0; i < n; i++) LQR_CATCH(mask_queue_flush(rs[i]));
+    if (!lqr_geom_is_flat(&rs[0]->geo)) {
+        Group g;
+        LQR_CATCH(group_open(&g, rs, n));
+        ret = group_flatten(&g);
+        if (ret != LQR_OK) { int k; for (k = 0; k < g.nb; k++) lqrhip_batch_abort(g.b[k]); }
+        group_close(&g);
+        LQR_CATCH(ret);
+    }
+    for (i = 0; i < n; i++)
+        if (lqr_state_check(&rs[i]->state)) return LQR_USRCANCEL;
+    ds = (LqrHipCarver **) malloc((size_t) n * sizeof *ds);
+    if (!ds) return LQR_NOMEM;
+    for (i = 0; i < n; i++) ds[i] = rs[i]->dev;
+    ret = hip_ret(lqrhip_forward_begin(ds, n, depth, orientation, rs[0]->geo.transposed,
+                                       rs[0]->nrg_func >= LQR_EF_LUMA_GRAD_NORM && rs[0]->nrg_func <= LQR_EF_LUMA_GRAD_XABS, L,
+                                       (void *const *) device_maps, &f));
+    free(ds);
+    if (ret == LQR_OK) ret = forward_slices(rs, n, f, depth);
+    if (ret != LQR_OK) { lqrhip_forward_release(f); return ret; }
+    *out = f;
+    return LQR_OK;
+}
+
+static LqrRetVal forward_maps(LqrCarver **rs, int n, int depth, int orientation, gint *const *device_maps, const char *who)
+{
+    LqrHipForward *f;
+    LqrRetVal ret;
+    int i, L;
+    LQR_CATCH(forward_check(rs, n, depth, orientation, who, &L));
+    for (i = 0; device_maps && i < n; i++)
+        if (!device_maps[i]) device_maps = NULL;
+    if (!device_maps) { fprintf(stderr, "liblqr-hip: %s refused: NULL map\n", who); return LQR_ERROR; }
+    LQR_CATCH(roots_enter(rs, n, LQR_STATE_RESIZING));
+    ret = forward_build_entered(rs, n, depth, orientation, L, device_maps, &f);
+    if (ret == LQR_OK) lqrhip_forward_release(f);
+    roots_leave(rs, n);
+    return ret;
+}
+LqrRetVal lqrx_carver_forward_map_device(LqrCarver *r, gint depth, gint orientation, gint *device_map)
+{
+    return forward_maps(&r, 1, depth, orientation, &device_map, "lqrx_carver_forward_map_device");
+}
+LqrRetVal lqrx_carver_forward_maps_device(LqrCarver **carvers, gint n, gint depth, gint orientation, gint *const *device_maps)
+{
+    return forward_maps(carvers, n, depth, orientation, device_maps, "lqrx_carver_forward_maps_device");
+}
+
+LqrVMap *lqrx_carver_forward_map(LqrCarver *r, gint depth, gint orientation)
+{
+    LqrHipForward *f;
+    LqrVMap *v = NULL;
+    gint *buffer;
+    int L, width, height;
+    if (forward_check(&r, 1, depth, orientation, "lqrx_carver_forward_map", &L) != LQR_OK) return NULL;
+    if (roots_enter(&r, 1, LQR_STATE_RESIZING) != LQR_OK) return NULL;
+    width = lqr_carver_get_width(r); height = lqr_carver_get_height(r);
+    buffer = (gint *) malloc((size_t) width * height * sizeof *buffer);
+    if (buffer && forward_build_entered(&r, 1, depth, orientation, L, NULL, &f) == LQR_OK) {
+        if (hip_ret(lqrhip_forward_read_map(f, 0, buffer)) == LQR_OK) v = lqr_vmap_new(buffer, width, height, depth, orientation);
+        lqrhip_forward_release(f);
+    }
+    if (!v) free(buffer);
+    roots_leave(&r, 1);
+    return v;
+}
+
+LqrRetVal lqrx_carver_load_forward(LqrCarver *r, gint depth, gint orientation)
+{
+    LqrHipForward *f;
+    LqrRetVal ret;
+    int L;
+    LQR_CATCH(forward_check(&r, 1, depth, orientation, "lqrx_carver_load_forward", &L));
+    LQR_CATCH(roots_enter(&r, 1, LQR_STATE_RESIZING));
+    ret = forward_build_entered(&r, 1, depth, orientation, L, NULL, &f);
+    if (ret == LQR_OK) {
+        /* (the map lies in the build's device memory until the load has committed) */
+        ret = group_vmap_load_entered(&r, 1, lqrhip_forward_map(f, 0), 1, lqr_carver_get_width(r), lqr_carver_get_height(r), depth, orientation);
+        lqrhip_forward_release(f);
+    }
+    roots_leave(&r, 1);
+    return ret;
+}
+
+LqrRetVal lqrx_carver_resize_forward(LqrCarver *r, gint w1, gint h1)
+{
+    int w, h, dir, k;
+    if (!r || r->root || w1 < 1 || h1 < 1) return LQR_ERROR;
+    w = lqr_carver_get_width(r); h = lqr_carver_get_height(r);
+    /* both directions are decided before either changes anything: no line has |change| seams, no frame is wider than the engine's */
+    /* (the second direction's lines are as many as the first leaves: max(., .) covers both orders) */
+    if (abs(w1 - w) >= w || abs(h1 - h) >= h || (w1 != w && w > LQRHIP_MAX_FRAME_WIDTH) || (h1 != h && h > LQRHIP_MAX_FRAME_WIDTH) ||
+        (w1 != w && MAXI(h, h1) > LQRHIP_FORWARD_MAX_LINES) || (h1 != h && MAXI(w, w1) > LQRHIP_FORWARD_MAX_LINES)) {
+        fprintf(stderr, "liblqr-hip: lqrx_carver_resize_forward refused: %d x %d to %d x %d (a change below the line length, lines of at most %d, "
+                "at most %d of them)\n", w, h, w1, h1, LQRHIP_MAX_FRAME_WIDTH, LQRHIP_FORWARD_MAX_LINES);
+        return LQR_ERROR;
+    }
+    for (k = 0; k < 2; k++) {
+        dir = (r->resize_order == LQR_RES_ORDER_HOR) ? k : 1 - k;       /* 0: the width */
+        w = lqr_carver_get_width(r); h = lqr_carver_get_height(r);
+        if ((dir ? h1 - h : w1 - w) == 0) continue;
+        LQR_CATCH(lqrx_carver_load_forward(r, abs(dir ? h1 - h : w1 - w), dir));
+        LQR_CATCH(lqr_carver_resize(r, dir ? w : w1, dir ? h1 : h));
+    }
+    return LQR_OK;
+}
+
+/* test hook (lqr_hip.h): the I plane a build would form for a flat carver, H lines of L floats in the frame of `orientation` */
+int lqrhip_read_forward_intensity(const void *carver, int orientation, float *out)
+{
+    const LqrCarver *r = (const LqrCarver *) carver;
+    if (!r || r->root || !out || !lqr_geom_is_flat(&r->geo)) return LQRHIP_EARG;
+    return lqrhip_forward_intensity(r->dev, orientation, r->geo.transposed,
+                                    r->nrg_func >= LQR_EF_LUMA_GRAD_NORM && r->nrg_func <= LQR_EF_LUMA_GRAD_XABS, out);
 }
 
 /* ======================= resize (E10) ==================================== */

@@ -263,6 +263,36 @@ int lqrhip_read_visible_device(LqrHipCarver *c, int w0, int h0, int w, int level
  * scratch planes where the images do not go straight to the caller's device memory): LQRHIP_CENSUS_COMPACT_SIZES counts them.
  * Everything is allocated before anything is launched: LQRHIP_ENOMEM has written nothing.  Returns with the outputs written. */
 int lqrhip_read_sizes(LqrHipCarver *c, int w0, int h0, int transposed, const int *levels, int n, void *const *outs, int on_device);
+/* lqr_forward.h: forward-energy seam maps of n FLAT root carvers of one shape and pixel kind (the host has flattened them), `depth` seams
+ * in the direction `orientation` (0: the width changes).  transposed: the carvers lie transposed (their base layout's rows are image
+ * columns); luma: the value read is luma; w_start: what the bias is divided by.  device_maps: n maps in device memory, width x height
+ * ints each, image orientation -- or NULL, and the build keeps maps of its own (lqrhip_forward_map, lqrhip_forward_read_map).
+ *   lqrhip_forward_begin    checks, allocates EVERYTHING the build needs and enqueues the one-off pass (k_fwd_init): LQRHIP_ENOMEM has
+ *                           launched nothing and given every block back
+ *   lqrhip_forward_seams    enqueues seams first_seam .. first_seam + n_seams - 1 (0-based, in order, every one once): two launches per
+ *                           seam whatever n is.  Returns once the slice BEFORE this one has completed, so that the host is never more
+ *                           than two slices ahead of the device and can stop between them
+ *   lqrhip_forward_finish   waits for the build; 0: the maps are complete
+ *   lqrhip_forward_release  waits for whatever is still queued and gives the build's blocks back (at any point, also instead of finish)
+ * The build runs on the shim's own stream; it reads the carvers' base layouts and changes nothing of theirs.
+ * A build takes at most LQRHIP_FORWARD_MAX_LINES lines per image and as many images (the launch grids' second dimension); the host
+ * refuses more up front.
+ * lqrhip_forward_launches: kernel launches of forward builds so far (test hook).  The counter is atomic: this one call MAY BE POLLED
+ * FROM ANOTHER THREAD while a build runs (a test's second thread times its lqr_carver_cancel by it).  lqrhip_forward_intensity: the I
+ * plane the one-off pass forms for one carver, H lines of L floats in the frame of the carving direction, to host memory (test hook). */
+#define LQRHIP_FORWARD_MAX_LINES 65535
+typedef struct LqrHipForward LqrHipForward;
+int lqrhip_forward_begin(LqrHipCarver *const *cs, int n, int depth, int orientation, int transposed, int luma, int w_start,
+                         void *const *device_maps, LqrHipForward **out);
+int lqrhip_forward_seams(LqrHipForward *f, int first_seam, int n_seams);
+int lqrhip_forward_finish(LqrHipForward *f);
+const int *lqrhip_forward_map(const LqrHipForward *f, int i);       /* image i's map, device memory (after finish) */
+int lqrhip_forward_read_map(LqrHipForward *f, int i, int *out);    /* ... copied to host memory */
+void lqrhip_forward_release(LqrHipForward *f);
+unsigned long long lqrhip_forward_launches(int reset);
+int lqrhip_forward_intensity(LqrHipCarver *c, int orientation, int transposed, int luma, float *out);
+/* (host/lqr_carver.c) the same for a LqrCarver, which must be flat: what tests/test_forward_gpu.py compares with the model's I */
+int lqrhip_read_forward_intensity(const void *carver, int orientation, float *out);
 int lqrhip_device_sync(void);
 /* free / total device memory in bytes (hipMemGetInfo) and the bytes the shim's allocation cache holds */
 int lqrhip_mem_info(unsigned long long *free_bytes, unsigned long long *total_bytes, unsigned long long *cached_bytes);
