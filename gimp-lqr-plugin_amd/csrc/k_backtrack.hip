@@ -190,7 +190,7 @@ __global__ __launch_bounds__(VPATH_THREADS) void k_vpath1(const DevCarver *cs, i
 template <int DELTA>
 __global__ __launch_bounds__(256) void k_vp_maps(const DevCarver *cs, int w, int h, int stride)
 {
-    constexpr int R = vp_chunk_rows(DELTA), RD = R * DELTA, WIN = 256 + 2 * RD, R4 = (R + 3) / 4;        // RD <= VP_REACH
+    constexpr int R = vp_chunk_rows(DELTA), RD = R * DELTA, WIN = 256 + 2 * RD, R4 = vp_quads(R);       // RD <= VP_REACH
     __shared__ __attribute__((aligned(4))) int8_t s_rows[R][WIN + 8];
     const GCarver c = gview(cs[blockIdx.z]);
     const int chunk = blockIdx.y, ytop = h - 1 - chunk * R, nrows = min(R, ytop);      // steps at rows ytop, ytop - 1, .. ytop - nrows + 1 (row 0 has none)
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256) void k_vp_maps(const DevCarver *cs, int w, int
     const int x = X0 + tid;
     if (x >= w) return;
     int p = x - base;
-    gu32 *path = (gu32 *) c.vp_path + (size_t) chunk * R4 * stride + x;
+    gu32 *path = (gu32 *) c.vp_path + vp_path_chunk(chunk, R4, stride) + x;
 #pragma unroll
     for (int r4 = 0; r4 < R4; r4++) {
         uint32_t pk = 0u;
@@ -227,15 +227,15 @@ __global__ __launch_bounds__(256) void k_vp_maps(const DevCarver *cs, int w, int
             pk |= (uint32_t) (uint8_t) (int8_t) (p + base - x) << (8 * k);          // the displacement BEFORE step r: the seam's column on row ytop - r
             if (r < nrows) { const int d = s_rows[r < R ? r : 0][p]; p += (d == LEAST_INVALID) ? 0 : d; }
         }
-        path[(size_t) r4 * stride] = pk;
+        path[vp_path_quad(r4, stride)] = pk;
     }
-    c.vp_map[(size_t) chunk * stride + x] = (int8_t) (p + base - x);
+    c.vp_map[vp_map_row(chunk, stride) + x] = (int8_t) (p + base - x);
 }
 
 template <int DELTA>
 __global__ __launch_bounds__(VPATH_THREADS) void k_vp_solve(const DevCarver *cs, int w, int h, int stride, int lr, int log_index, int moved_unit)
 {
-    constexpr int R = vp_chunk_rows(DELTA), RD = R * DELTA, S = VP_STAGE, R4 = (R + 3) / 4;
+    constexpr int R = vp_chunk_rows(DELTA), RD = R * DELTA, S = VP_STAGE, R4 = vp_quads(R);
     constexpr int CP = (2 * RD * S + 4 + 15 + 16) & ~15;       // LDS pitch of a stage's rows: the cone [x - RD S, x + RD S] from a base rounded down to 4, in 16-byte units
     const GCarver c = gview(cs[blockIdx.x]);
     const int org = c.flags[FLAG_ORG];           // read before wave 0 publishes the next one
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(VPATH_THREADS) void k_vp_solve(const DevCarver *cs,
             const int i = tid + k * VPATH_THREADS, j = i / W16, d = i - j * W16, col = base + 16 * d;
             v[k] = (u32x4) {0u, 0u, 0u, 0u};
             if (i >= ns * W16 || col + 15 < x - RD * (j + 1) || col > x + RD * (j + 1)) continue;
-            const gi8 *src = c.vp_map + (size_t) (c0 + j) * stride + col;
+            const gi8 *src = c.vp_map + vp_map_row(c0 + j, stride) + col;        // (col may be negative: added to the pointer, not to the size_t)
             if (col >= 0 && col + 15 < stride) v[k] = *(const GLOBAL_AS u32x4 *) src;
             else {
                 uint32_t q4[4] = {0u, 0u, 0u, 0u};
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(VPATH_THREADS) void k_vp_solve(const DevCarver *cs,
         if (y == 0) v = s_xs[nchunks];
         else {
             const int s = h - 1 - y, chunk = s / R, r = s - chunk * R, xs = s_xs[chunk];
-            v = xs + (int) ((const gi8 *) c.vp_path)[(((size_t) chunk * R4 + (r >> 2)) * stride + xs) * 4 + (r & 3)];
+            v = xs + (int) ((const gi8 *) c.vp_path)[vp_path_step(chunk, R4, r, stride, xs)];
         }
         seam[y] = v; logp[y] = v; acc += v;
     }

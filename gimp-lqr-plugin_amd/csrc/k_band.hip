@@ -20,7 +20,7 @@ __global__ __launch_bounds__(NTH) void k_dp_sweep(const DevCarver *cs, DpK p, in
 {
     const GCarver c = gview(cs[blockIdx.x]);
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int wpad = (w + 3) & ~3;
+    const int wpad = sweep_wpad(w);
     float *prev = sm, *cur = sm + wpad;
     const int tid = threadIdx.x;
     int y0 = 0;
@@ -556,7 +556,7 @@ __device__ __forceinline__ void band_update_tw_body(const DevCarver &dc, const D
     GCarver c = gview(dc);
     c.en = uni_ptr(c.en); c.m = uni_ptr(c.m); c.least = uni_ptr(c.least);       // (scalar bases for the row loop: lqr_common.h)
     extern __shared__ int s_tw[];                          // [2h]: per row, per batch-starting-at-row touch ranges
-    int *s_touch = s_tw, *s_touchR = s_tw + h;
+    int *s_touch = s_tw, *s_touchR = s_tw + band_tw_touchR_off(h);
     // m of the last finished row over [B-R, B+WIN+R), double-buffered by batch parity: a slot reads its halo
     // (the neighbours' own columns) at the start of a batch, and a neighbour that is a whole batch faster
     // must not have overwritten them yet

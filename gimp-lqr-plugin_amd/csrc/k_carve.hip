@@ -413,7 +413,9 @@ __global__ __launch_bounds__(256) void k_carve_e(const DevCarver *cs, DpK p, int
 template <int NRG>
 __global__ __launch_bounds__(256) void k_carve_u(const DevCarver *cs, DpK p, int w, int h, int stride, int move_dp, int k, int epoch, int n)
 {
-    const int eblk = (h + EU_ROWS - 1) / EU_ROWS, ne = n * eblk;
+    // (cu_grid / cu_block in lqr_geom.h state this map and the test checks it there; here it stays in the kernel's own text: through the
+    // function the instruction stream differs)
+    const int eblk = bb_energy_entries(h), ne = n * eblk;
     if ((int) blockIdx.x < ne) {
         const int img = blockIdx.x / eblk, blk = blockIdx.x - img * eblk;
         PixRead<false> rd;
@@ -423,7 +425,7 @@ __global__ __launch_bounds__(256) void k_carve_u(const DevCarver *cs, DpK p, int
         emap_update_block<NRG, 12, false, true>(c, rd, p, w - 1, h, stride, k, epoch, blk, threadIdx.x);
         return;
     }
-    const int rblk = (h + 3) / 4, cb = blockIdx.x - ne, img = cb / rblk, rb = cb - img * rblk;
+    const int rblk = bb_carve_entries(h), cb = blockIdx.x - ne, img = cb / rblk, rb = cb - img * rblk;
     const GCarver c = gview_phys(cs[img]);
     const int org = c.flags[FLAG_ORG_PREV], side = c.flags[FLAG_SIDE];      // published by k_vpath* for this seam
     if (rb == 0 && threadIdx.x == 0) c.flags[FLAG_OVF_ROW] = h;

@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void k_frozen_catchup(const DevCarver *cs, int
     const GCarver c = gview(cs[blockIdx.y]);
     extern __shared__ int smc[];
     int *xs = smc;                                  // [to - from]
-    uint8_t *rem = (uint8_t *) (smc + (to - from));  // [w_from]
+    uint8_t *rem = (uint8_t *) (smc + fc_rem_off(from, to));  // [w_from]
     __shared__ int s_wave[4];
     const int y = blockIdx.x, tid = threadIdx.x, n = to - from;
     for (int i = tid; i < n; i += 256) xs[i] = c.seam_log[(size_t) (from + i) * h + y];

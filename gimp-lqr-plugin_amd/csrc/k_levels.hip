@@ -86,7 +86,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_band_levels(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long long *exch, int epoch, int *dev_err, int P, int n_img)
 {
     static_assert(DELTA >= 1 && DELTA <= LQR_FAST_MAX_DELTA && (DELTA <= 4 || RIG) && (RIG || !RIGM), "delta_x 1 .. 10 (5 .. 10: the rigidity form, with a zero table if there is none); a rigidity mask only matters with rigidity");
-    constexpr int PX = 2, HALO = 32, OWN = 64, HL = 16, R = lv_rows(DELTA, RIGM), TILE = 128;
+    constexpr int PX = 2, HALO = 32, OWN = LV_OWN, HL = 16, R = lv_rows(DELTA, RIGM), TILE = 128;
     static_assert(R * DELTA <= HALO, "a level's errors stay inside the halo");
     typedef LaneVec<2>::F FV;
     typedef LaneVec<2>::L LV;
@@ -103,19 +103,21 @@ void k_band_levels(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long
     // only, the protocol is placement-independent): the P slots of an image are the workgroups b = xcd + 8 (P g + slot), image = 8 g +
     // xcd -- all on one XCD, whose L2 then serves the level hand-overs' reads a little sooner (handoff-1to1: cross-XCD +0.1 - 0.3 us)
     const int dbg = __builtin_amdgcn_readfirstlane(g_lv_dbg);
+    // (lv_grid / lv_block in lqr_geom.h state this map and the test checks it there; here it stays in the kernel's own text: through the
+    // function the instruction stream differs)
     const int b_xcd = (int) blockIdx.x & 7, b_k = (int) blockIdx.x >> 3;
     // (debug switch 8: consecutive workgroups = the slots of one image, i.e. on DIFFERENT XCDs -- the placement the near copies do
     // not serve; the tests run it to show that nothing but speed depends on where the slots sit)
     const int slot = (dbg & 8) ? (int) blockIdx.x % P : b_k % P, image = (dbg & 8) ? (int) blockIdx.x / P : (b_k / P) * 8 + b_xcd;
     if (image >= n_img) return;
     const int nblk = (h + R - 1) / R;
-    const int ntiles = (w + OWN - 1) / OWN;
+    const int ntiles = lv_tiles(w);
     GCarver c = gview(cs[image]);
     if constexpr (RIG && DELTA == 1 && !RIGM) { c.en = uni_ptr(c.en); c.m = uni_ptr(c.m); c.least = uni_ptr(c.least); }      // (see LEAN below)
-    const size_t near_off = (size_t) 4 * LV_PMAX + (size_t) 2 * ntiles * OWN;      // the near copies (see the header)
-    gu64 *ex_img = (gu64 *) exch + (size_t) image * 2 * near_off;
+    const size_t near_off = lv_near_off(ntiles);      // the near copies (see the header)
+    gu64 *ex_img = (gu64 *) exch + exch_image_off(image, near_off);
     gu64 *flagw = ex_img;                                    // [2 parities][LV_PMAX slots][2 tiles]
-    gu64 *gran = ex_img + 4 * LV_PMAX;                       // [2 parities][ntiles][OWN]
+    gu64 *gran = ex_img + LV_FLAG_WORDS;                      // [2 parities][ntiles][OWN]
     const float INF = __int_as_float(0x7f800000);
     const float rig_l = p.rigmap[0], rig_r = p.rigmap[2];
     float rg[2 * DELTA + 1];

@@ -14,7 +14,7 @@ __global__ __launch_bounds__(256) void k_vs_commit(const DevCarver *cs, int w0, 
     const GCarver c = gview(cs[blockIdx.y]);
     extern __shared__ int smi[];
     int *xs = smi;                      // [n_seams]
-    int *lvl = smi + n_seams;           // [wc0]
+    int *lvl = smi + vsc_lvl_off(n_seams);          // [wc0]
     __shared__ int s_wave[4];
     const int y = blockIdx.x, tid = threadIdx.x;
     for (int k = tid; k < n_seams; k += 256) xs[k] = c.seam_log[(size_t) k * h0 + y];

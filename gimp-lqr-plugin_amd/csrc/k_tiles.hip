@@ -165,10 +165,10 @@ __global__ __launch_bounds__(64 * DPP_W) void k_dp_tile_p(DevCarver *cs, DpK p, 
     // neighbour is of its own class polls the near copy three times out of four, the write-through copy the fourth; the others
     // poll the write-through copy only.  The protocol rests on the write-through copies alone.
     typedef GLOBAL_AS unsigned long long gu64;
-    const size_t near_off = (size_t) ntiles * EX_TILE + 8;
-    gu64 *ex_img = (gu64 *) exch + (size_t) blockIdx.y * 2 * near_off;
+    const size_t near_off = dpp_near_off(ntiles, PXC);
+    gu64 *ex_img = (gu64 *) exch + exch_image_off(blockIdx.y, near_off);
     const bool near_l = !(dbg & 3) && cls_k > 0, near_r = !(dbg & 3) && cls_k + 1 < cls_n;      // the left / right neighbour is on this XCD
-    gi32 *done_ctr = (gi32 *) (ex_img + (size_t) ntiles * EX_TILE);
+    gi32 *done_ctr = (gi32 *) (ex_img + dpp_ctr_off(ntiles, PXC));
     const int lane = threadIdx.x & 63;
     const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const float INF = __int_as_float(0x7f800000);

@@ -88,7 +88,6 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 __global__ __launch_bounds__(256) void k_vs_commit(const DevCarver *cs, int w0, int h0, int wc0, int n_seams, int first_level, int finish);
 template <bool DEEP> __global__ __launch_bounds__(256) void k_inflate(const InflateDev *jobs, int w0, int w1, int l, int max_level, int *dev_err);
 __global__ __launch_bounds__(256) void k_vmap_check(const int32_t *map, int len, int depth, int *dev_err);
-#define VT_LINES 32     // lines of the carver's frame (columns of the map) per workgroup of k_vmap_check_t
 __global__ __launch_bounds__(256) void k_vmap_check_t(const int32_t *map, int32_t *out, int width, int height, int depth, int *dev_err);
 __global__ __launch_bounds__(256) void k_seam_check(const DevCarver *cs, int h, int wc0, int n_seams, int delta, int *dev_err);
 __global__ __launch_bounds__(256) void k_vs_rollback(const DevCarver *cs, size_t n, int first_level, int finish_level);

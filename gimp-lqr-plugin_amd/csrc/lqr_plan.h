@@ -8,30 +8,22 @@
 #include <stddef.h>
 #include "../../include/lqr_hip.h"
 #include "lqr_beside.h"         // the backtrack beside the carve: its side bound, its entries and their limits
+#include "lqr_geom.h"           // each launch's sizes and grid maps, and the tiles' geometry (dpp_halo, dpp_own, LV_PMAX, tiles_of)
 
 #define DP_THREADS 1024
-// ---- geometry of the persistent tiled kernels (k_tiles.hip), needed by their launchers too
-// PX pixels per lane (4, or 2 when the device has room for twice the tiles: half the instructions per wave and row):
-// a tile is 64 * PX columns of which the 16 outer lanes on each side are halo
-// `px` below is a geometry code: 2 / 4 = pixels per lane with 16 halo lanes per side; 3 (round 6) = 2 pixels per lane with 24 halo lanes per
-// side -- 32 own columns + 48-column halos, blocks of 48 rows: the hand-over through memory (a third of a 32-row level) is paid 45
-// times per 4K sweep instead of 68, for twice the tiles; used while every tile still has a compute unit to itself (single images)
-constexpr int dppx_px(int px) { return px == 3 ? 2 : px; }
-constexpr int dppx_hl(int px) { return px == 3 ? 24 : 16; }
-constexpr int dpp_halo(int px) { return dppx_hl(px) * dppx_px(px); }              // halo columns on each side = rows per block
-constexpr int dpp_own(int px) { return 64 * dppx_px(px) - 2 * dpp_halo(px); }     // columns a tile owns
-constexpr int dpp_ex_tile(int px) { return px == 3 ? 2 * dpp_own(3) : 2 * 2 * dpp_halo(px); }       // granules a tile publishes: [block parity][side: 0 to the left, 1 to the right][column]; px 3: [block parity][own column]
+// ---- geometry of the persistent tiled kernels (k_tiles.hip) that the choices depend on; the tiles themselves are lqr_geom.h's
 constexpr int dpp_rb(int px, int delta) { return delta >= 5 ? dpp_halo(2) / delta : delta >= 3 ? 8 : dpp_halo(px) / delta; }      // rows per block (delta_x 5 .. 10: 6, 5, 4, 4, 3, 3)
 constexpr int DPP_R = 16;                       // rows per batch
 constexpr int DPP_W = 2;                        // waves taking turns
 static_assert(dpp_halo(2) % (2 * DPP_R) == 0 && dpp_halo(4) % (2 * DPP_R) == 0, "a block (halo / delta_x rows, delta_x <= 2) is a whole number of batches");
 constexpr int DPP_BLK_BITS = 12;                // bits of the block index in a granule's tag
+static_assert(DPP_EPOCH_BITS + DPP_BLK_BITS == 31, "a granule's tag: epoch above block index, the sign bit free");
 #define DPT_ROWS 32
 #define DPT_OWN 192
-// k_band_levels (k_levels.hip): slots per image at most, tiles per image at most (one 64-bit mask: rows up to 4096 px)
-constexpr int LV_PMAX = 16;
+// k_band_levels (k_levels.hip): tiles per image at most (one 64-bit mask: rows up to 4096 px)
 constexpr int LV_MAX_TILES = 64;
 constexpr int LV_MAX_LEVELS = 1020;       // levels per image at most (10 bits of the tags hold level + 1; 4K rows at delta_x 10: 720 levels of 3 rows)
+static_assert(LV_MAX_LEVELS + 1 < (1 << LV_LEVEL_BITS), "level + 1 fits its field of the tags");
 constexpr int lv_rows(int delta, bool rigm = false) { return delta == 1 ? (rigm ? 16 : 32) : delta == 2 ? 16 : delta <= 4 ? 8 : 32 / delta; }      // rows per level: halo (32 columns) / delta_x (a rigidity mask: 16, for the registers)
 constexpr int LQR_FAST_MAX_DELTA = 10;    // delta_x up to which the tiled kernels have instantiations (the plug-in's UI: src/interface.c:47, MAX_DELTA_X 10)
 // parallel backtrack (k_backtrack.hip, k_vp_*): a chunk is VP_REACH / delta_x rows, so that a path moves at most VP_REACH columns
@@ -48,8 +40,6 @@ constexpr int eu_samples(int delta_x) { return delta_x <= 2 ? 12 : delta_x <= 8 
 #define FROZEN_LAG_MAX 128
 #endif
 constexpr int frozen_lag(int images) { return images <= 4 ? FROZEN_LAG_MAX / 4 : FROZEN_LAG_MAX; }
-// dynamic LDS beyond this needs hipFuncSetAttribute before the launch (k_dp_sweep past 8192 columns, k_vs_commit)
-constexpr bool lds_needs_attr(size_t bytes) { return bytes > 64 * 1024; }
 constexpr int LV_AUTO_MIN = 7;            // slots per image the automatic choice of k_band_levels needs (6 and fewer put second tiles on a slot in 9 % of the tile-levels)
 
 // ---- what the choice is made from -----------------------------------------------------------------------------------------------
@@ -114,7 +104,6 @@ struct StepPlan {
 };
 
 static inline int plan_limit(const PlanKnobs &k, int bound) { return k.dpp_limit >= 0 ? std::min(k.dpp_limit, bound) : bound; }     // a residency bound under the cap
-constexpr int tiles_of(int w, int own) { return (w + own - 1) / own; }
 
 // Streams a lock-step group of n carvers is split over.  Automatic: 4 for the groups that run k_band_update_tw (49 images and more), 2
 // for the groups of 32 to 48 that run k_band_levels (round 5, one box, Mseams*px/s with 2 / 4 streams: 32 images 360 / 352 k, 48
@@ -165,7 +154,7 @@ static inline DpPlan plan_sweep(const PlanKnobs &k, int w, bool update)
     p.threads = (update && k.sweep_threads == 256 && w <= 16 * 256) ? 256 : DP_THREADS;
     for (p.px = 1; p.px <= 16 && p.px * p.threads < w;) p.px *= 2;
     if (p.px > 16) p.px = 0;
-    p.lds = (size_t) 2 * ((w + 3) & ~3) * sizeof(float);
+    p.lds = sweep_lds(w);
     return p;
 }
 
@@ -325,11 +314,11 @@ static inline StepPlan plan_seam_step(const PlanKnobs &k, const PlanDevice &d, c
     else if (tiled) {
         s.dp = plan_persistent(plan_persistent_px(k, d, b, wnew, general, delta, b.images), general, b.images);
         return s;
-    } else if (plain && (size_t) h * sizeof(int) <= 60 * 1024) {       // (the fast band kernels keep a row's seam positions in LDS)
+    } else if (plain && band_mw_fits(h)) {       // (the fast band kernels keep a row's seam positions in LDS)
         // the trapezoid-wave band kernel takes rows up to ~4200 px (wider rows: the changes outgrow its 896-column window too often, and
         // an 8-slot build spills registers); beyond that, and in update mode 2, k_band_update_mw: 8 waves, 16 for rows wider than 4200 px
         // (8K: dirty regions up to ~900 px)
-        s.band = mode != 2 && wnew <= 4200 && (size_t) 2 * h * sizeof(int) <= 64 * 1024 ? LQRHIP_CENSUS_BAND_TW : wnew > 4200 ? LQRHIP_CENSUS_BAND_MW16 : LQRHIP_CENSUS_BAND_MW8;
+        s.band = mode != 2 && wnew <= 4200 && band_tw_fits(h) ? LQRHIP_CENSUS_BAND_TW : wnew > 4200 ? LQRHIP_CENSUS_BAND_MW16 : LQRHIP_CENSUS_BAND_MW8;
     } else s.band = LQRHIP_CENSUS_BAND_GENERIC;
     s.dp = plan_sweep(k, wnew, true);
     return s;

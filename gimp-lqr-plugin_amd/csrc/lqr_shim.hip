@@ -558,18 +558,18 @@ extern "C" int lqrhip_carver_attach(LqrHipCarver *root, LqrHipCarver *aux)
 // (re)allocate the working planes for a w x h carved frame
 static int ensure_working(LqrHipCarver *c, int w, int h)
 {
-    int stride = ((w + 16) + 63) & ~63;
+    int stride = plane_stride(w);
     bool need_bias = c->bias0 != nullptr, need_rig = c->rig0 != nullptr;
     const int deep = reads_value(c) ? 1 : 0;
     WorkingPlanes &k = c->wk;
     if (k.pix && c->stride == stride && c->wk_h == h && (!!k.bias == need_bias) && (!!k.rig == need_rig) && c->pix_deep == deep) return 0;
     free_working(c);
     c->stride = 0; c->wk_h = 0;
-    size_t n = (size_t) stride * (h + 1) + 1024;
+    size_t n = plane_elems(stride, h);
     const size_t npix = deep ? 2 * n : n;              // a value plane holds a double per pixel
     int rc;
     if ((rc = k.pix.alloc(npix, "&c->pix")) || (rc = k.en.alloc(n, "&c->en")) || (rc = k.m.alloc(n, "&c->m")) || (rc = k.least.alloc(n, "&c->least")) ||
-        (rc = k.seam_x.alloc((size_t) h + 8, "&c->seam_x")) || (rc = k.flags.alloc((size_t) FLAG_WORDS, "&c->flags")) ||
+        (rc = k.seam_x.alloc(seam_x_elems(h), "&c->seam_x")) || (rc = k.flags.alloc((size_t) FLAG_WORDS, "&c->flags")) ||
         (need_bias && (rc = k.bias.alloc(n, "&c->bias"))) || (need_rig && (rc = k.rig.alloc(n, "&c->rig")))) {
         free_working(c);            // never leave a half-allocated set behind: a retry must not pass the early-out above
         return rc;
@@ -590,7 +590,7 @@ static int ensure_working(LqrHipCarver *c, int w, int h)
 static int ensure_log(LqrHipCarver *c, int n_seams, int h)
 {
     if (c->wk.seam_log && c->log_cap >= n_seams && c->log_h == h) return 0;
-    int rc = c->wk.seam_log.alloc((size_t) n_seams * h, "&c->seam_log");      // (a log of another shape is replaced, also by a smaller one)
+    int rc = c->wk.seam_log.alloc(seam_log_elems(n_seams, h), "&c->seam_log");      // (a log of another shape is replaced, also by a smaller one)
     if (rc) return rc;
     c->log_cap = n_seams; c->log_h = h;
     if (c->batch) c->batch->dirty = true;
@@ -620,20 +620,6 @@ extern "C" int lqrhip_mask_plane_ensure(LqrHipCarver *c, int is_rigmask)
     return 0;
 }
 
-// Where a width x height mask laid at (x_off, y_off) over the image (transposed: over the carver's transposed frame) falls: (x0, y0) what
-// of the offset is negative, (x1, y1) the first pixel it covers, nx x ny how many.  The far edge is computed in long long, so that a mask
-// near INT_MAX wide cannot wrap; for arguments where plain int arithmetic does not overflow the values are those it gives.
-struct MaskClip { int x0, y0, x1, y1, nx, ny; };
-static MaskClip mask_clip(const LqrHipCarver *c, int width, int height, int x_off, int y_off, int transposed)
-{
-    const int wt = transposed ? c->h0 : c->w0, ht = transposed ? c->w0 : c->h0;
-    const int x0 = x_off < 0 ? x_off : 0, y0 = y_off < 0 ? y_off : 0;
-    const int x1 = x_off > 0 ? x_off : 0, y1 = y_off > 0 ? y_off : 0;
-    const long long xe = (long long) width + x_off, ye = (long long) height + y_off;
-    const int x2 = wt < xe ? wt : (int) xe, y2 = ht < ye ? ht : (int) ye;
-    return MaskClip{x0, y0, x1, y1, x2 - x1, y2 - y1};
-}
-
 extern "C" int lqrhip_mask_add(LqrHipCarver *c, const unsigned char *mask, int channels, int width, int height, int x_off,
                                int y_off, int transposed, int is_rigmask, int bias_factor)
 {
@@ -641,13 +627,13 @@ extern "C" int lqrhip_mask_add(LqrHipCarver *c, const unsigned char *mask, int c
     if (rc) return rc;
     if ((rc = lqrhip_mask_plane_ensure(c, is_rigmask))) return rc;
     float *plane = is_rigmask ? c->rig0 : c->bias0;
-    const MaskClip k = mask_clip(c, width, height, x_off, y_off, transposed);
+    const MaskClip k = mask_clip(c->w0, c->h0, width, height, x_off, y_off, transposed);
     if (k.nx <= 0 || k.ny <= 0) return 0;
     const size_t mbytes = (size_t) width * height * channels;
     Scratch tmp(g_stream0);
     uint8_t *dmask = tmp.get<uint8_t>(mbytes, "&dmask", rc);
     if (rc || (rc = h2d_staged(dmask, mask, mbytes))) return rc;
-    dim3 grid((k.nx + 255) / 256, k.ny);
+    dim3 grid(tiles_of(k.nx, 256), k.ny);
     hipLaunchKernelGGL(k_mask_add, grid, dim3(256), 0, g_stream0, plane, c->w0, dmask, channels, width, k.x0, k.y0, k.x1, k.y1, k.nx, k.ny,
                        transposed, is_rigmask, bias_factor);
     HIPCK(hipGetLastError());
@@ -664,7 +650,7 @@ extern "C" int lqrhip_mask_add_f(LqrHipCarver *c, const void *mask, int depth, i
     if (rc) return rc;
     if ((rc = lqrhip_mask_plane_ensure(c, is_rigmask))) return rc;
     float *plane = is_rigmask ? c->rig0 : c->bias0;
-    const MaskClip k = mask_clip(c, width, height, x_off, y_off, transposed);
+    const MaskClip k = mask_clip(c->w0, c->h0, width, height, x_off, y_off, transposed);
     if (k.nx <= 0 || k.ny <= 0) return 0;
     const size_t mbytes = (size_t) width * height * (depth == 2 ? sizeof(float) : sizeof(double));
     Scratch tmp(g_stream0);
@@ -674,7 +660,7 @@ extern "C" int lqrhip_mask_add_f(LqrHipCarver *c, const void *mask, int depth, i
         if (rc || (rc = h2d_staged(staged, mask, mbytes))) return rc;
         src = staged;
     }
-    dim3 grid((k.nx + 255) / 256, k.ny);
+    dim3 grid(tiles_of(k.nx, 256), k.ny);
     if (depth == 2)
         hipLaunchKernelGGL(k_mask_add_f<float>, grid, dim3(256), 0, g_stream0, plane, c->w0, (const float *) src, width, k.x0, k.y0, k.x1, k.y1, k.nx, k.ny,
                            transposed, is_rigmask, bias_factor);
@@ -707,7 +693,7 @@ extern "C" int lqrhip_mask_scatter(LqrHipCarver *c, int is_rigmask, const int *i
     for (int b = 0; b < buckets; b++) {
         const size_t nb = start[b + 1] - start[b];
         if (!nb) continue;
-        hipLaunchKernelGGL(k_mask_scatter, dim3((unsigned) ((nb + 255) / 256)), dim3(256), 0, g_stream0, plane, dindex + start[b], dvalue + start[b],
+        hipLaunchKernelGGL(k_mask_scatter, dim3((unsigned) blocks_of(nb, 256)), dim3(256), 0, g_stream0, plane, dindex + start[b], dvalue + start[b],
                            nb, is_rigmask);
         HIPCK(hipGetLastError());
         g_mask_flushes++;
@@ -741,7 +727,7 @@ extern "C" int lqrhip_read_mask_plane(LqrHipCarver *c, int is_rigmask, int trans
     Scratch tmp(g_stream0);
     float *t = tmp.get<float>(n, "&t", rc);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_plane_transpose, dim3((c->w0 + 15) / 16, (c->h0 + 15) / 16), dim3(256), 0, g_stream0, plane, t, c->w0, c->h0);
+    hipLaunchKernelGGL(k_plane_transpose, dim3(tiles_of(c->w0, 16), tiles_of(c->h0, 16)), dim3(256), 0, g_stream0, plane, t, c->w0, c->h0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { g_err = std::string("k_plane_transpose: ") + hipGetErrorString(e); return LQRHIP_EHIP; }
     if ((rc = d2h_staged(out, t, n * sizeof(float)))) return rc;
@@ -986,7 +972,7 @@ extern "C" int lqrhip_wk_init(LqrHipBatch *b, int from_visible)
     LqrHipCarver *c0 = b->cs[0];
     int w = c0->w0, h = c0->h0, rc;
     if ((rc = wk_init_prepare(b))) return rc;
-    const dim3 grid((c0->stride + 255) / 256, h, (unsigned) b->cs.size()), grid_v(h, (unsigned) b->cs.size());
+    const dim3 grid(tiles_of(c0->stride, 256), h, (unsigned) b->cs.size()), grid_v(h, (unsigned) b->cs.size());
 #define LAUNCH_WK(FORM, arg) do { if (from_visible) hipLaunchKernelGGL(k_wk_init_visible<FORM>, grid_v, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, arg); \
                                   else hipLaunchKernelGGL(k_wk_init<FORM>, grid, dim3(256), 0, b->stream, b->d_desc, w, h, c0->stride, arg); } while (0)
     if (!reads_value(c0)) LAUNCH_WK(PixPacked, c0->ch);
@@ -1005,7 +991,7 @@ extern "C" int lqrhip_emap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w,
     if ((rc = pay_catchup(b))) return rc;           // the energy reads pix / bias in the carved frame
     if ((rc = batch_upload(b))) return rc;
     LqrHipCarver *c0 = b->cs[0];
-    dim3 grid((w + 255) / 256, h, (unsigned) b->cs.size());
+    dim3 grid(tiles_of(w, 256), h, (unsigned) b->cs.size());
     DpK k = make_dpk(p, c0->ch);
     const bool value = reads_value(c0);
     const int nrg = plane_nrg(value, nrg_index(p->nrg_func));
@@ -1025,7 +1011,7 @@ extern "C" int lqrhip_wk_init_emap(LqrHipBatch *b, const LqrHipDpParams *p, int 
     int rc;
     if (reads_value(c0) || w != c0->w0 || h != c0->h0) return (rc = lqrhip_wk_init(b, 0)) ? rc : lqrhip_emap_build(b, p, w, h);
     if ((rc = wk_init_prepare(b))) return rc;
-    const dim3 grid((tiles_of(c0->stride, 4) + 255) / 256, h, (unsigned) b->cs.size());
+    const dim3 grid(tiles_of(tiles_of(c0->stride, 4), 256), h, (unsigned) b->cs.size());
     DpK k = make_dpk(p, c0->ch);
     const int nrg = nrg_index(p->nrg_func);
 #define CASE(N) if (nrg == N) hipLaunchKernelGGL(k_wk_init_emap<N>, grid, dim3(256), 0, b->stream, b->d_desc, k, w, h, c0->stride); else
@@ -1081,7 +1067,7 @@ extern "C" int lqrhip_energy_out(LqrHipBatch *b, int w, int h, int transposed, i
 static int launch_dp_tiled(LqrHipBatch *b, const DpK &k, int w, int h, int lr)
 {
     LqrHipCarver *c0 = b->cs[0];
-    const dim3 grid((w + DPT_OWN - 1) / DPT_OWN, (unsigned) b->cs.size());
+    const dim3 grid(tiles_of(w, DPT_OWN), (unsigned) b->cs.size());
     for (int y0 = 0; y0 < h; y0 += DPT_ROWS) {
         CENSUS(LQRHIP_CENSUS_DP_TILE);
 #define CASE(LRV, RIGV) if ((lr != 0) == LRV && (k.use_rig != 0) == RIGV) hipLaunchKernelGGL((k_dp_tile<LRV, RIGV>), grid, dim3(64), 0, b->stream, b->d_desc, k, w, h, c0->stride, y0); else
@@ -1132,13 +1118,30 @@ extern "C" int lqrhip_general_batch_limit_delta(int w, int delta)
 }
 extern "C" int lqrhip_general_batch_limit(int w) { return lqrhip_general_batch_limit_delta(w, 2); }
 
-// Grow and (re)lay a batch's exchange area for a spinning kernel: `need_elems` words for `ntiles` tiles of each of `n` images, in the
-// layout `layout` (k_dp_tile_p: its px code; k_band_levels: 103, that kernel's own layout and tags).  Tags and finished-tile
-// counters start at 0; afterwards nothing is ever cleared: tags carry the launch epoch, the last tile re-arms the counter
-static int exch_ensure(LqrHipBatch *b, size_t need_elems, int ntiles, int n, int layout)
+// Grow a pair of buffers that every carver of the batch owns one of: ready(c) says that carver c has its pair, make(c) allocates it.  The stream
+// is drained once, before the first pair is made (what is in use goes back to the pool); if any was made, the descriptors are uploaded again
+template <class Ready, class Make> static int grow_pairs(LqrHipBatch *b, Ready ready, Make make)
 {
     int rc;
     bool grew = false;
+    for (auto *c : b->cs) {
+        if (ready(c)) continue;
+        if (!grew) { HIPCK(hipStreamSynchronize(b->stream)); grew = true; }
+        if ((rc = make(c))) return rc;
+    }
+    if (!grew) return 0;
+    b->dirty = true;
+    return batch_upload(b);
+}
+
+// Grow and (re)lay a batch's exchange area for a spinning kernel: `near_off` words and their near copies for `ntiles` tiles of each of
+// `n` images, in the layout `layout` (lqr_geom.h: exch_layout_dpp, EXCH_LAYOUT_LEVELS).  Tags and finished-tile
+// counters start at 0; afterwards nothing is ever cleared: tags carry the launch epoch, the last tile re-arms the counter
+static int exch_ensure(LqrHipBatch *b, size_t near_off, int ntiles, int n, int layout)
+{
+    int rc;
+    bool grew = false;
+    const size_t need_elems = exch_words(near_off, (size_t) n);
     if (b->exch.size() < need_elems) HIPCK(hipStreamSynchronize(b->stream));     // (the area in use goes back to the pool)
     if ((rc = b->exch.ensure(need_elems, "&b->exch", &grew))) return rc;
     if (grew) b->exch_ntiles = 0;
@@ -1164,39 +1167,31 @@ static int launch_dp_persistent(LqrHipBatch *b, const DpK &k, const DpPlan &dp, 
     LqrHipCarver *c0 = b->cs[0];
     const size_t n = (size_t) count;
     const int px = dp.px;
-    const bool general = dp.general;
     if (!px || (UPDATE && n != b->cs.size())) return LQRHIP_EARG;
-    const int ntiles = (w + dpp_own(px) - 1) / dpp_own(px);
+    const int ntiles = dpp_tiles(w, px);
     int rc;
-    const size_t need_elems = 2 * ((size_t) ntiles * dpp_ex_tile(px) + 8) * n;      // (granules + finished-tile counter, and the near copies: k_tiles.hip)
-    if ((rc = exch_ensure(b, need_elems, ntiles, (int) n, px))) return rc;
-    if (UPDATE) {
-        // second planes, allocated on first use -- per carver: a batch may mix carvers that already went
-        // through a tiled update on their own with fresh ones
-        bool grew = false;
-        for (auto *c : b->cs) {
-            if (c->wk.m2 && c->wk.least2) continue;
-            if (!grew) { HIPCK(hipStreamSynchronize(b->stream)); grew = true; }
-            const size_t pe = (size_t) c->stride * (c->wk_h + 1) + 1024;
-            // m2 and least2 are made here and dropped in free_working, both times as a pair; the carver gets the zeroed pair or
-            // nothing, so that a plane that was never zeroed cannot pass for an old one
-            DevBuf<float> m2;
-            DevBuf<int8_t> least2;
-            if ((rc = m2.alloc(pe, "&c->m2")) || (rc = least2.alloc(pe, "&c->least2"))) return rc;
-            // like the first planes (ensure_working): nothing in them depends on what the block held before
-            hipError_t e = hipMemsetAsync(m2, 0, pe * sizeof(float), b->stream);
-            if (e == hipSuccess) e = hipMemsetAsync(least2, 0, pe, b->stream);
-            if (e != hipSuccess) { lqr_stream_wait(b->stream); HIPCK(e); }
-            c->wk.m2 = std::move(m2); c->wk.least2 = std::move(least2);
-        }
-        if (grew) {
-            b->dirty = true;
-            if ((rc = batch_upload(b))) return rc;
-        }
-    }
-    const int epoch = 1 + ((b->tile_epoch++) % ((1 << (31 - DPP_BLK_BITS)) - 2));          // never 0; above the block index in the 32-bit tag
+    if ((rc = exch_ensure(b, dpp_near_off(ntiles, px), ntiles, (int) n, exch_layout_dpp(px)))) return rc;
+    // the second planes, allocated on first use -- per carver: a batch may mix carvers that already went through a tiled update on their
+    // own with fresh ones
+    auto make_second = [&](LqrHipCarver *c) -> int {
+        const size_t pe = plane_elems(c->stride, c->wk_h);
+        // m2 and least2 are made here and dropped in free_working, both times as a pair; the carver gets the zeroed pair or
+        // nothing, so that a plane that was never zeroed cannot pass for an old one
+        DevBuf<float> m2;
+        DevBuf<int8_t> least2;
+        int err;
+        if ((err = m2.alloc(pe, "&c->m2")) || (err = least2.alloc(pe, "&c->least2"))) return err;
+        // like the first planes (ensure_working): nothing in them depends on what the block held before
+        hipError_t e = hipMemsetAsync(m2, 0, pe * sizeof(float), b->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(least2, 0, pe, b->stream);
+        if (e != hipSuccess) { lqr_stream_wait(b->stream); HIPCK(e); }
+        c->wk.m2 = std::move(m2); c->wk.least2 = std::move(least2);
+        return 0;
+    };
+    if (UPDATE && (rc = grow_pairs(b, [](LqrHipCarver *c) { return c->wk.m2 && c->wk.least2; }, make_second))) return rc;
+    const int epoch = dpp_epoch(b->tile_epoch++);
     const dim3 grid(ntiles, (unsigned) n);
-    CENSUS(general ? LQRHIP_CENSUS_TILE_P_GENERAL : px == 3 ? LQRHIP_CENSUS_TILE_P_G3 : px == 2 ? LQRHIP_CENSUS_TILE_P_G2 : LQRHIP_CENSUS_TILE_P_G4);
+    CENSUS(dp.general ? LQRHIP_CENSUS_TILE_P_GENERAL : px == 3 ? LQRHIP_CENSUS_TILE_P_G3 : px == 2 ? LQRHIP_CENSUS_TILE_P_G2 : LQRHIP_CENSUS_TILE_P_G4);
     // px code 3 is 2 px per lane with the 24-halo-lane geometry; the general forms exist for 2 px per lane only (plan_persistent_px)
     const DpForm f = dp_form(k, lr, rigm);
     const int px_lane = px == 4 ? 4 : 2, hln = px == 3 ? 24 : 16;
@@ -1262,20 +1257,19 @@ extern "C" int lqrhip_mmap_build(LqrHipBatch *b, const LqrHipDpParams *p, int w,
     return launch_dp<false>(b, make_dpk(p, b->cs[0]->ch), plan_full_dp(g_knobs, g_dev, pb, w, p->delta_x, use_rig), pb.rigm(use_rig), w, h, leftright);
 }
 
-// remove seams [epoch, to) from the frozen planes of every carver of the batch
-static int frozen_catchup(LqrHipBatch *b, int to, int w_at_to, int h)
+// remove seams [frozen_epoch, to) from the frozen planes of carvers [first, first + count) of the batch, which are at the same epoch;
+// the frame is w_at_to wide after seam to - 1
+static int frozen_catchup(LqrHipBatch *b, size_t first, size_t count, int to, int w_at_to, int h)
 {
-    LqrHipCarver *c0 = b->cs[0];
+    LqrHipCarver *c0 = b->cs[first];
     const int from = c0->frozen_epoch;
     if (to <= from) return 0;
-    const int w_from = w_at_to + (to - from);
-    size_t lds = (size_t) (to - from) * sizeof(int) + (size_t) w_from + 16;
+    const int w_from = fc_w_from(from, to, w_at_to);
     with_form(c0, [&](auto value) {
-        hipLaunchKernelGGL(k_frozen_catchup<value>, dim3(h, (unsigned) b->cs.size()), dim3(256), lds, b->stream, b->d_desc, from, to, w_from, h,
-                           c0->stride);
+        hipLaunchKernelGGL(k_frozen_catchup<value>, dim3(h, (unsigned) count), dim3(256), fc_lds(from, to, w_from), b->stream, b->d_desc + first, from, to, w_from, h, c0->stride);
     });
     HIPCK(hipGetLastError());
-    for (auto *c : b->cs) c->frozen_epoch = to;
+    for (size_t i = first; i < first + count; i++) b->cs[i]->frozen_epoch = to;
     return 0;
 }
 
@@ -1294,23 +1288,11 @@ static int pay_catchup(LqrHipBatch *b)
     if (!any) return 0;
     int rc;
     if ((rc = batch_upload(b))) return rc;
-    if (alike) {
-        if ((rc = frozen_catchup(b, c0->owed_to, c0->owed_w, c0->owed_h))) return rc;
-    } else {
-        // carvers that ended their last sessions in different batches (alone: a lag of 32; in a group: of 128) owe different ranges, and
-        // the kernel takes one range per launch: one launch per owing carver, each through its own descriptor of the table
-        for (size_t i = 0; i < b->cs.size(); i++) {
-            LqrHipCarver *c = b->cs[i];
-            if (c->owed_to <= c->frozen_epoch) continue;
-            const int from = c->frozen_epoch, w_from = c->owed_w + (c->owed_to - from);
-            const size_t lds = (size_t) (c->owed_to - from) * sizeof(int) + (size_t) w_from + 16;
-            with_form(c, [&](auto value) {
-                hipLaunchKernelGGL(k_frozen_catchup<value>, dim3(c->owed_h, 1), dim3(256), lds, b->stream, b->d_desc + i, from, c->owed_to, w_from, c->owed_h, c->stride);
-            });
-            HIPCK(hipGetLastError());
-            drop_catchup(c);
-        }
-    }
+    // carvers that ended their last sessions in different batches (alone: a lag of 32; in a group: of 128) owe different ranges, and
+    // the kernel takes one range per launch: then one launch per owing carver, each through its own descriptor of the table
+    const size_t per = alike ? b->cs.size() : 1;
+    for (size_t i = 0; i < b->cs.size(); i += per)
+        if ((rc = frozen_catchup(b, i, per, b->cs[i]->owed_to, b->cs[i]->owed_w, b->cs[i]->owed_h))) return rc;
     for (auto *c : b->cs) drop_catchup(c);              // paid: the planes are in the carved frame, the log restarts at 0
     return 0;
 }
@@ -1319,12 +1301,10 @@ static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr
 {
     LqrHipCarver *c0 = b->cs[0];
     const size_t n = b->cs.size();
-    int rc;
-    const int ntiles = (w + 63) / 64;
-    const size_t need_elems = 2 * ((size_t) 4 * LV_PMAX + (size_t) 2 * ntiles * 64) * n;    // (two copies of each word: k_levels.hip, near_off)
-    if ((rc = exch_ensure(b, need_elems, ntiles, (int) n, 103))) return rc;
-    const int epoch = 1 + ((b->tile_epoch++) % ((1 << 22) - 2));           // never 0; 22 bits above the 10 bits of level + 1
-    const dim3 grid((unsigned) (8 * ((n + 7) / 8) * P));          // the slots of an image on one XCD (k_levels.hip)
+    const int ntiles = lv_tiles(w);
+    if (int rc = exch_ensure(b, lv_near_off(ntiles), ntiles, (int) n, EXCH_LAYOUT_LEVELS)) return rc;
+    const int epoch = lv_epoch(b->tile_epoch++);
+    const dim3 grid(lv_grid(n, P));
     CENSUS(LQRHIP_CENSUS_BAND_LEVELS);
     const DpForm f = dp_form(k, lr, rigm);
 #define CASE(LR, RIG, DELTA, RIGM) if (f.lr == LR && f.rig == RIG && f.delta == DELTA && f.rigm == RIGM) \
@@ -1334,12 +1314,199 @@ static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr
     HIPCK(hipGetLastError());
     return 0;
 }
+static void inject_after_step(LqrHipBatch *b, int h, int log_index);
+static void inject_after_commit(LqrHipBatch *b, int w0, int h0, int first_level);
+// ---- one seam step, stage by stage: each launcher runs one case of the step's plan (lqr_plan.h) over the step's values; sizes are lqr_geom.h's
+struct StepVals {
+    DpK k;
+    int w, h, stride, log_index;    // the frame on entry; the seam's row of the log
+    int lr_pick, lr_next;           // the side a tie goes to: in this seam's pick, in the DP for the next
+    int move_dp;                    // the carve moves m and the back pointers too: an update follows, not a full DP
+    int moved_unit;                 // bytes the carve moves per pixel of the side it moves (seam_step_impl)
+    int epoch;                      // the frozen planes are in the frame before this seam of the log (catchup_within_lag moves it on)
+    bool value, rigm;               // PlanBatch::value, PlanBatch::rigm(use_rigidity)
+    unsigned n;                     // carvers
+};
+// the frozen planes lag too far: compact them up to this seam (needs the seam log only)
+static int catchup_within_lag(LqrHipBatch *b, const StepPlan &s, StepVals &v)
+{
+    const int rc = s.catchup ? frozen_catchup(b, 0, b->cs.size(), v.log_index + 1, v.w - 1, v.h) : 0;
+    v.epoch = b->cs[0]->frozen_epoch;
+    return rc;
+}
+// the backtrack: the parallel pair, or the one-wave walk (beside the carve: the walk is a role of the carve's launch)
+static int launch_backtrack(LqrHipBatch *b, const StepPlan &s, const StepVals &v)
+{
+    const int w = v.w, h = v.h, stride = v.stride, n = (int) v.n;
+    if (s.backtrack == LQRHIP_CENSUS_VP_PARALLEL) {
+        // the maps and paths, per carver, for this step's chunks (vp_path's size depends on delta_x: each answers for its own)
+        const size_t need = vp_map_bytes(s.vp_chunks, stride), need_path = vp_path_bytes(s.vp_chunks, stride, s.vp_rows);
+        if (int rc = grow_pairs(b, [&](LqrHipCarver *c) { return c->wk.vp_map.size() >= need && c->wk.vp_path.size() >= need_path; }, [&](LqrHipCarver *c) {
+                c->wk.vp_map.reset(); c->wk.vp_path.reset();
+                const int rc = c->wk.vp_map.alloc(need, "&c->vp_map");
+                return rc ? rc : c->wk.vp_path.alloc(need_path, "&c->vp_path");
+            })) return rc;
+        ProfScope ps("vpath", b->stream, 0);
+        CENSUS(LQRHIP_CENSUS_VP_PARALLEL);
+        if (!with_listed(K_VP_FORMS, v.k.delta, [&](auto delta) {
+                hipLaunchKernelGGL(k_vp_maps<delta>, dim3(vp_col_blocks(w), s.vp_chunks, n), dim3(256), 0, b->stream, b->d_desc, w, h, stride);
+                hipLaunchKernelGGL(k_vp_solve<delta>, dim3(n), dim3(VPATH_THREADS), vp_solve_lds(s.vp_chunks), b->stream, b->d_desc, w, h, stride, v.lr_pick, v.log_index, v.moved_unit);
+            })) return no_form("k_vp_maps");
+    } else if (!s.backtrack_beside) {
+        ProfScope ps("vpath", b->stream, 0);
+        CENSUS(s.backtrack);
+        // the one-wave walk: unrolled for the listed delta_x, the loop over candidates beyond (and for delta_x 0)
+        if (!with_listed(K_VPATH1_FORMS, v.k.delta, [&](auto delta) {
+                hipLaunchKernelGGL(k_vpath1<delta>, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, v.lr_pick, v.log_index, v.moved_unit);
+            }))
+            hipLaunchKernelGGL(k_vpath, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, v.lr_pick, v.k.delta, v.log_index, v.moved_unit);
+    }
+    return 0;
+}
+// the carve: with the energy update fused in, with the walk and the energy update beside it, with the energy update beside it, or plain.
+// Algorithmic bytes of one carve launch: read + write of one 4-byte plane over the half of each row right of the seam
+// = 8 B * w*h/2 per image, whichever form
+static int launch_carve(LqrHipBatch *b, const StepPlan &s, StepVals &v)
+{
+    int rc;
+    const int w = v.w, h = v.h, stride = v.stride, n = (int) v.n;
+    const double bytes = 4.0 * (double) w * h * n;
+    if (s.carve == LQRHIP_CENSUS_CARVE_E) {
+        if ((rc = catchup_within_lag(b, s, v))) return rc;      // (before the carve)
+        ProfScope ps("carve", b->stream, bytes);
+        CENSUS(LQRHIP_CENSUS_CARVE_E);
+        if (!with_listed(K_CARVE_E_FORMS, nrg_index(v.k.nrg), [&](auto nrg) {
+                hipLaunchKernelGGL((k_carve_e<nrg>), dim3(bb_carve_entries(h), n), dim3(256), 0, b->stream, b->d_desc, v.k, w, h, stride, v.move_dp, v.log_index, v.epoch);
+            })) return no_form("k_carve_e");
+    } else if (s.backtrack_beside) {
+        // k_carve_v: the walks' workgroups first, then one consumer per entry of the work list the walks fill -- the carve's row-quads and
+        // the energy update's blocks, in the order they become ready (k_carve.hip).  "vpath" and "emap_update" have no launch on this path.
+        // (No catch-up here: the plan keeps the step that compacts the frozen planes on the separate launches)
+        const size_t need = cv_list_words(n, h);
+        if (b->wlist.size() < need) {
+            bool grew = false;
+            HIPCK(hipStreamSynchronize(b->stream));     // (the list in use goes back to the pool)
+            if ((rc = b->wlist.ensure(need, "&b->wlist", &grew))) return rc;
+            HIPCK(hipMemsetAsync(b->wlist, 0, need * sizeof(unsigned long long), b->stream));        // no tag, both tails at 0
+        }
+        unsigned long long *moved = lqr_moved_bytes_dev();
+        if (!moved) { g_err = "k_carve_v: no address for the moved-bytes counter"; return LQRHIP_EHIP; }
+        const unsigned tag = bb_tag(b->wlist_launches++);
+        ProfScope ps("carve", b->stream, bytes);
+        CENSUS(LQRHIP_CENSUS_VPATH1);
+        CENSUS(LQRHIP_CENSUS_CARVE);
+        g_carve_beside_launches++;
+        g_backtrack_beside_launches++;
+        bool launched = false;
+        with_listed(K_CARVE_U_FORMS, nrg_index(v.k.nrg), [&](auto nrg) {
+            launched = with_listed(K_CARVE_V_DELTAS, v.k.delta, [&](auto delta) {
+                hipLaunchKernelGGL((k_carve_v<nrg, delta>), dim3(cv_grid(n, h)), dim3(256), 0, b->stream, b->d_desc, v.k, w, h, stride, v.lr_pick, v.move_dp, v.log_index, v.epoch,
+                                   (int) n, v.moved_unit, tag, b->wlist.get(), moved, g_dev_err);
+            });
+        });
+        if (!launched) return no_form("k_carve_v");
+    } else if (s.energy_beside) {
+        // k_carve_u: the energy update's workgroups first, then the carve's, in one 1-D grid (k_carve.hip); "emap_update" has no launch on this path
+        if ((rc = catchup_within_lag(b, s, v))) return rc;      // (before the carve)
+        ProfScope ps("carve", b->stream, bytes);
+        CENSUS(LQRHIP_CENSUS_CARVE);
+        g_carve_beside_launches++;
+        if (!with_listed(K_CARVE_U_FORMS, nrg_index(v.k.nrg), [&](auto nrg) {
+                hipLaunchKernelGGL((k_carve_u<nrg>), dim3(cu_grid(n, h)), dim3(256), 0, b->stream, b->d_desc, v.k, w, h, stride, v.move_dp, v.log_index, v.epoch, (int) n);
+            })) return no_form("k_carve_u");
+    } else {
+        ProfScope ps("carve", b->stream, bytes);
+        // (a grid of a half, a quarter, an eighth of the rows, the kernel striding over the rest, measured at 64 x 4K in round 5: 508 / 504 / 490 k
+        // against 488 - 501 k: inside the run-to-run spread; not adopted)
+        CENSUS(LQRHIP_CENSUS_CARVE);
+        hipLaunchKernelGGL(k_carve, dim3(bb_carve_entries(h), n), dim3(256), 0, b->stream, b->d_desc, w, h, stride, v.k.delta, v.move_dp);
+    }
+    return 0;
+}
+// the energy update, where the carve's launch has not taken it
+static int launch_energy(LqrHipBatch *b, const StepPlan &s, StepVals &v)
+{
+    if (s.carve == LQRHIP_CENSUS_CARVE_E || s.energy_beside) return 0;
+    ProfScope ps("emap_update", b->stream, 0);
+    if (int rc = catchup_within_lag(b, s, v)) return rc;
+    const int h = v.h, stride = v.stride, wnew = v.w - 1, log_index = v.log_index, epoch = v.epoch, n = (int) v.n;
+    const DpK &k = v.k;
+    const bool value = v.value;
+    const int nrg = plane_nrg(value, nrg_index(k.nrg)), nt = s.eu_nt;
+#define CASE_NT(NT, N, V) if (nrg == N && value == V && nt == NT) hipLaunchKernelGGL((k_emap_update<N, NT, V>), dim3(bb_energy_entries(h), n), dim3(64), 0, b->stream, b->d_desc, k, wnew, h, stride, log_index, epoch); else
+#define CASE(N, V) K_EMAP_UPDATE_NT_FORMS(CASE_NT, N, V)
+    K_EMAP_FORMS(CASE) return no_form("k_emap_update");
+#undef CASE
+#undef CASE_NT
+    return 0;
+}
+// the band stage: the kernel that updates the band the seam changed, and the sweep that takes the rows it hands over
+static int launch_band(LqrHipBatch *b, const StepPlan &s, const StepVals &v)
+{
+    const int h = v.h, stride = v.stride, wnew = v.w - 1, leftright_next = v.lr_next, n = (int) v.n;
+    const DpK &k = v.k;
+    if (s.band == LQRHIP_CENSUS_BAND_LEVELS) {
+        ProfScope ps("band_levels", b->stream, 0);
+        if (int rc = launch_band_levels(b, k, wnew, h, leftright_next, s.levels_P, v.rigm)) return rc;
+    } else if (s.band == LQRHIP_CENSUS_BAND_TW) {
+        ProfScope ps("band_update", b->stream, 0);
+        CENSUS(LQRHIP_CENSUS_BAND_TW);
+#define CASE(LRV, RIGV) if ((leftright_next != 0) == LRV && (k.use_rig != 0) == RIGV) hipLaunchKernelGGL((k_band_update_tw<4, LRV, RIGV>), dim3(n), dim3(128 * 4), band_tw_lds(h), b->stream, b->d_desc, k, wnew, h, stride, g_dev_err); else
+        K_LR_RIG_FORMS(CASE) return no_form("k_band_update_tw");
+#undef CASE
+        // (round 5: the kernel finishing the rows its window cannot hold itself, without the (almost always empty) k_dp_sweep<UPDATE>
+        // launch behind it, was built and measured on one box: 527.5 / 523.5 k against 531 / 528 k -- the launch's 22 us reappear in
+        // the kernels around it (k_vpath1 74 -> 92 us, k_carve 149 -> 162), the step is not the sum of a chain's kernels; removed)
+    } else if (s.band == LQRHIP_CENSUS_BAND_MW8 || s.band == LQRHIP_CENSUS_BAND_MW16) {
+        ProfScope ps("band_update", b->stream, 0);
+        const int nw = s.band == LQRHIP_CENSUS_BAND_MW16 ? 16 : 8;
+        CENSUS(nw == 16 ? LQRHIP_CENSUS_BAND_MW16 : LQRHIP_CENSUS_BAND_MW8);
+#define CASE_NW(NWV, LRV, RIGV) if (nw == NWV && (leftright_next != 0) == LRV && (k.use_rig != 0) == RIGV) hipLaunchKernelGGL((k_band_update_mw<2, NWV, 8, LRV, RIGV>), dim3(n), dim3(64 * NWV), band_mw_lds(h), b->stream, b->d_desc, k, wnew, h, stride); else
+#define CASE(LRV, RIGV) CASE_NW(8, LRV, RIGV) CASE_NW(16, LRV, RIGV)
+        K_LR_RIG_FORMS(CASE) return no_form("k_band_update_mw");
+#undef CASE
+#undef CASE_NW
+    } else {
+        ProfScope ps("band_update", b->stream, 0);
+        CENSUS(LQRHIP_CENSUS_BAND_GENERIC);
+        hipLaunchKernelGGL(k_band_update, dim3(n), dim3(64), 0, b->stream, b->d_desc, k, wnew, h, stride, leftright_next);
+    }
+    // rows the band kernel handed over (flags[FLAG_OVF_ROW] .. h): the keep rule over the full width
+    ProfScope ps("dp_update", b->stream, 0);
+    return launch_dp<true>(b, k, s.dp, v.rigm, wnew, h, leftright_next);
+}
+
 // One seam of a lock-step batch: k_vpath* (pick + backtrack, publishes the side to move) -> k_carve ->
 // k_emap_update -> one form of update_mmap (or the full DP after a side switch), all on the batch's stream.
 static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h, int log_index, int leftright_pick,
-                          int full_rebuild, int leftright_next);
-static void inject_after_step(LqrHipBatch *b, int h, int log_index);
-static void inject_after_commit(LqrHipBatch *b, int w0, int h0, int first_level);
+                          int full_rebuild, int leftright_next)
+{
+    int rc;
+    LqrHipCarver *c0 = b->cs[0];
+    for (auto *c : b->cs)
+        if (log_index >= c->log_cap || c->owed_to) return LQRHIP_EARG;     // (a carver that owes a catch-up never meets the new session's log)
+    if ((rc = batch_upload(b))) return rc;
+    // every choice of this step (lqr_plan.h): the launchers run one case of the plan each
+    const PlanBatch pb = plan_batch(b);
+    const StepPlan s = plan_seam_step(g_knobs, g_dev, pb, p->delta_x, p->use_rigidity != 0, w, h, full_rebuild != 0, log_index + 1 - c0->frozen_epoch);
+    const int wnew = w - 1, move_dp = (wnew > 1 && !full_rebuild) ? 1 : 0;
+    // bytes the carve moves per pixel of the side it moves, read + write: en 4 (+ m 4 + back pointer 1 unless a full DP follows,
+    // + the rigidity mask 4) -- k_vpath* knows how many pixels that is for the seam it finds and keeps the sum (lqrhip_moved_bytes)
+    const int moved_unit = 2 * (4 + (move_dp ? 5 : 0) + (pb.rigmask ? 4 : 0));
+    StepVals v{make_dpk(p, c0->ch), w, h, c0->stride, log_index, leftright_pick, leftright_next, move_dp, moved_unit, c0->frozen_epoch,
+               pb.value, pb.rigm(p->use_rigidity != 0), (unsigned) b->cs.size()};
+    if ((rc = launch_backtrack(b, s, v)) || (rc = launch_carve(b, s, v))) return rc;
+    if (s.dp.form < 0) { HIPCK(hipGetLastError()); return 0; }          // liblqr's finish_vsmap case: nothing left to update
+    if ((rc = launch_energy(b, s, v))) return rc;
+    if (s.full || s.band < 0) {         // the full DP after a side switch, or E9 as the tiled full-width update: that launch alone
+        ProfScope ps(s.full ? "dp_sweep" : "dp_update_tiled", b->stream, s.full ? 9.0 * wnew * h * v.n : 0);
+        rc = s.full ? launch_dp<false>(b, v.k, s.dp, v.rigm, wnew, h, leftright_next) : launch_dp<true>(b, v.k, s.dp, v.rigm, wnew, h, leftright_next);
+    } else rc = launch_band(b, s, v);
+    if (rc) return rc;
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
 // LQRHIP_DUMP=<prefix> (debugging aid): after every seam step the first image's seam, flags and DP planes go to
 // <prefix>_<call>.bin -- header {w, h, stride, log_index, FLAG_COUNT}, flags, seam_x[h], m[stride * h], least[stride * h]
 extern "C" int lqrhip_seam_step(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h, int log_index, int leftright_pick,
@@ -1371,171 +1538,6 @@ extern "C" int lqrhip_seam_step(LqrHipBatch *b, const LqrHipDpParams *p, int w, 
     return rc;
 }
 
-static int seam_step_impl(LqrHipBatch *b, const LqrHipDpParams *p, int w, int h, int log_index, int leftright_pick,
-                          int full_rebuild, int leftright_next)
-{
-    int rc;
-    LqrHipCarver *c0 = b->cs[0];
-    for (auto *c : b->cs)
-        if (log_index >= c->log_cap || c->owed_to) return LQRHIP_EARG;     // (a carver that owes a catch-up never meets the new session's log)
-    if ((rc = batch_upload(b))) return rc;
-    const unsigned n = (unsigned) b->cs.size();
-    DpK k = make_dpk(p, c0->ch);
-    const int stride = c0->stride;
-    const int wnew = w - 1;
-    const int move_dp = (wnew > 1 && !full_rebuild) ? 1 : 0;
-    // every choice of this step (lqr_plan.h): the launches below are one case of the plan each
-    const PlanBatch pb = plan_batch(b);
-    const StepPlan s = plan_seam_step(g_knobs, g_dev, pb, p->delta_x, p->use_rigidity != 0, w, h, full_rebuild != 0, log_index + 1 - c0->frozen_epoch);
-    const bool rigm = pb.rigm(p->use_rigidity != 0);
-    // bytes the carve moves per pixel of the side it moves, read + write: en 4 (+ m 4 + back pointer 1 unless a full DP follows,
-    // + the rigidity mask 4) -- k_vpath* knows how many pixels that is for the seam it finds and keeps the sum (lqrhip_moved_bytes)
-    const int moved_unit = 2 * (4 + (move_dp ? 5 : 0) + (pb.rigmask ? 4 : 0));
-    if (s.backtrack == LQRHIP_CENSUS_VP_PARALLEL) {
-        const int nchunks = s.vp_chunks, R4 = (s.vp_rows + 3) / 4;
-        const size_t need = (size_t) (nchunks + 1) * stride + 64, need_path = need * 4 * R4;      // (R4 depends on delta_x: each answers for its own size)
-        bool grew = false;
-        for (auto *c : b->cs) {
-            WorkingPlanes &wp = c->wk;
-            if (wp.vp_map.size() >= need && wp.vp_path.size() >= need_path) continue;
-            if (!grew) { HIPCK(hipStreamSynchronize(b->stream)); grew = true; }
-            wp.vp_map.reset(); wp.vp_path.reset();
-            if ((rc = wp.vp_map.alloc(need, "&c->vp_map")) || (rc = wp.vp_path.alloc(need_path, "&c->vp_path"))) return rc;
-        }
-        if (grew) { b->dirty = true; if ((rc = batch_upload(b))) return rc; }
-        ProfScope ps("vpath", b->stream, 0);
-        CENSUS(LQRHIP_CENSUS_VP_PARALLEL);
-        if (!with_listed(K_VP_FORMS, p->delta_x, [&](auto delta) {
-                hipLaunchKernelGGL(k_vp_maps<delta>, dim3((w + 255) / 256, nchunks, n), dim3(256), 0, b->stream, b->d_desc, w, h, stride);
-                hipLaunchKernelGGL(k_vp_solve<delta>, dim3(n), dim3(VPATH_THREADS), (size_t) (nchunks + 2) * sizeof(int), b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit);
-            })) return no_form("k_vp_maps");
-    } else if (!s.backtrack_beside) {            // (beside: the walk is a role of the carve's launch below)
-        ProfScope ps("vpath", b->stream, 0);
-        CENSUS(s.backtrack);
-        // the one-wave walk: unrolled for the listed delta_x, the loop over candidates beyond (and for delta_x 0)
-        if (!with_listed(K_VPATH1_FORMS, p->delta_x, [&](auto delta) {
-                hipLaunchKernelGGL(k_vpath1<delta>, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, leftright_pick, log_index, moved_unit);
-            }))
-            hipLaunchKernelGGL(k_vpath, dim3(n), dim3(VPATH_THREADS), 0, b->stream, b->d_desc, w, h, stride, leftright_pick, p->delta_x,
-                               log_index, moved_unit);
-    }
-    auto frozen_within_lag = [&]() -> int { return s.catchup ? frozen_catchup(b, log_index + 1, wnew, h) : 0; };
-    const bool fuse_e = s.carve == LQRHIP_CENSUS_CARVE_E;
-    if (fuse_e) {
-        if ((rc = frozen_within_lag())) return rc;      // (needs the seam log only: before the carve)
-        const int epoch = c0->frozen_epoch;
-        ProfScope ps("carve", b->stream, 4.0 * (double) w * h * n);
-        CENSUS(LQRHIP_CENSUS_CARVE_E);
-        if (!with_listed(K_CARVE_E_FORMS, nrg_index(p->nrg_func), [&](auto nrg) {
-                hipLaunchKernelGGL((k_carve_e<nrg>), dim3((h + 3) / 4, n), dim3(256), 0, b->stream, b->d_desc, k, w, h, stride, move_dp, log_index, epoch);
-            })) return no_form("k_carve_e");
-    } else if (s.backtrack_beside) {
-        // k_carve_v: the walks' workgroups first, then one consumer per entry of the work list the walks fill -- the carve's row-quads and
-        // the energy update's blocks, in the order they become ready (k_carve.hip).  "vpath" and "emap_update" have no launch on this path.
-        // (No catch-up here: the plan keeps the step that compacts the frozen planes on the separate launches)
-        const int epoch = c0->frozen_epoch;
-        const size_t need = (size_t) BB_LIST_HEAD + (size_t) bb_entries((int) n, h);
-        if (b->wlist.size() < need) {
-            bool grew = false;
-            HIPCK(hipStreamSynchronize(b->stream));     // (the list in use goes back to the pool)
-            if ((rc = b->wlist.ensure(need, "&b->wlist", &grew))) return rc;
-            HIPCK(hipMemsetAsync(b->wlist, 0, need * sizeof(unsigned long long), b->stream));        // no tag, both tails at 0
-        }
-        unsigned long long *moved = lqr_moved_bytes_dev();
-        if (!moved) { g_err = "k_carve_v: no address for the moved-bytes counter"; return LQRHIP_EHIP; }
-        const unsigned tag = bb_tag(b->wlist_launches++);
-        ProfScope ps("carve", b->stream, 4.0 * (double) w * h * n);
-        CENSUS(LQRHIP_CENSUS_VPATH1);
-        CENSUS(LQRHIP_CENSUS_CARVE);
-        g_carve_beside_launches++;
-        g_backtrack_beside_launches++;
-        const unsigned grid = n + (unsigned) bb_entries((int) n, h);
-        bool launched = false;
-        with_listed(K_CARVE_U_FORMS, nrg_index(p->nrg_func), [&](auto nrg) {
-            launched = with_listed(K_CARVE_V_DELTAS, p->delta_x, [&](auto delta) {
-                hipLaunchKernelGGL((k_carve_v<nrg, delta>), dim3(grid), dim3(256), 0, b->stream, b->d_desc, k, w, h, stride, leftright_pick, move_dp, log_index, epoch,
-                                   (int) n, moved_unit, tag, b->wlist.get(), moved, g_dev_err);
-            });
-        });
-        if (!launched) return no_form("k_carve_v");
-    } else if (s.energy_beside) {
-        // k_carve_u: the energy update's workgroups first, then the carve's, in one 1-D grid (k_carve.hip).  The same algorithmic bytes as
-        // k_carve's; "emap_update" has no launch on this path
-        if ((rc = frozen_within_lag())) return rc;      // (needs the seam log only: before the carve)
-        const int epoch = c0->frozen_epoch;
-        ProfScope ps("carve", b->stream, 4.0 * (double) w * h * n);
-        CENSUS(LQRHIP_CENSUS_CARVE);
-        g_carve_beside_launches++;
-        const unsigned grid = n * (unsigned) ((h + EU_ROWS - 1) / EU_ROWS) + n * (unsigned) ((h + 3) / 4);
-        if (!with_listed(K_CARVE_U_FORMS, nrg_index(p->nrg_func), [&](auto nrg) {
-                hipLaunchKernelGGL((k_carve_u<nrg>), dim3(grid), dim3(256), 0, b->stream, b->d_desc, k, w, h, stride, move_dp, log_index, epoch, (int) n);
-            })) return no_form("k_carve_u");
-    } else {
-        // algorithmic bytes of one carve launch: read + write of one 4-byte
-        // plane over the half of each row right of the seam = 8 B * w*h/2 per image
-        ProfScope ps("carve", b->stream, 4.0 * (double) w * h * n);
-        // (a grid of a half, a quarter, an eighth of the rows, the kernel striding over the rest, measured at 64 x 4K in round 5: 508 / 504 / 490 k
-        // against 488 - 501 k: inside the run-to-run spread; not adopted)
-        CENSUS(LQRHIP_CENSUS_CARVE);
-        hipLaunchKernelGGL(k_carve, dim3((h + 3) / 4, n), dim3(256), 0, b->stream, b->d_desc, w, h, stride, p->delta_x, move_dp);
-    }
-    if (s.dp.form < 0) {        // liblqr's finish_vsmap case: nothing left to update
-        HIPCK(hipGetLastError());
-        return 0;
-    }
-    if (!fuse_e && !s.energy_beside) {
-        ProfScope ps("emap_update", b->stream, 0);
-        if ((rc = frozen_within_lag())) return rc;
-        const int epoch = c0->frozen_epoch;
-        const bool value = pb.value;
-        const int nrg = plane_nrg(value, nrg_index(p->nrg_func)), nt = s.eu_nt;
-#define CASE_NT(NT, N, V) if (nrg == N && value == V && nt == NT) hipLaunchKernelGGL((k_emap_update<N, NT, V>), dim3((h + EU_ROWS - 1) / EU_ROWS, n), dim3(64), 0, b->stream, b->d_desc, k, wnew, h, stride, log_index, epoch); else
-#define CASE(N, V) K_EMAP_UPDATE_NT_FORMS(CASE_NT, N, V)
-        K_EMAP_FORMS(CASE) return no_form("k_emap_update");
-#undef CASE
-#undef CASE_NT
-    }
-    if (s.full || s.band < 0) {         // the full DP after a side switch, or E9 as the tiled full-width update: that launch alone
-        ProfScope ps(s.full ? "dp_sweep" : "dp_update_tiled", b->stream, s.full ? 9.0 * wnew * h * n : 0);
-        if ((rc = s.full ? launch_dp<false>(b, k, s.dp, rigm, wnew, h, leftright_next) : launch_dp<true>(b, k, s.dp, rigm, wnew, h, leftright_next))) return rc;
-        HIPCK(hipGetLastError());
-        return 0;
-    }
-    if (s.band == LQRHIP_CENSUS_BAND_LEVELS) {
-        ProfScope ps("band_levels", b->stream, 0);
-        if ((rc = launch_band_levels(b, k, wnew, h, leftright_next, s.levels_P, rigm))) return rc;
-    } else if (s.band == LQRHIP_CENSUS_BAND_TW) {
-        ProfScope ps("band_update", b->stream, 0);
-        CENSUS(LQRHIP_CENSUS_BAND_TW);
-#define CASE(LRV, RIGV) if ((leftright_next != 0) == LRV && (p->use_rigidity != 0) == RIGV) hipLaunchKernelGGL((k_band_update_tw<4, LRV, RIGV>), dim3(n), dim3(128 * 4), (size_t) 2 * h * sizeof(int), b->stream, b->d_desc, k, wnew, h, stride, g_dev_err); else
-        K_LR_RIG_FORMS(CASE) return no_form("k_band_update_tw");
-#undef CASE
-        // (round 5: the kernel finishing the rows its window cannot hold itself, without the (almost always empty) k_dp_sweep<UPDATE>
-        // launch behind it, was built and measured on one box: 527.5 / 523.5 k against 531 / 528 k -- the launch's 22 us reappear in
-        // the kernels around it (k_vpath1 74 -> 92 us, k_carve 149 -> 162), the step is not the sum of a chain's kernels; removed)
-    } else if (s.band == LQRHIP_CENSUS_BAND_MW8 || s.band == LQRHIP_CENSUS_BAND_MW16) {
-        ProfScope ps("band_update", b->stream, 0);
-        const int nw = s.band == LQRHIP_CENSUS_BAND_MW16 ? 16 : 8;
-        CENSUS(nw == 16 ? LQRHIP_CENSUS_BAND_MW16 : LQRHIP_CENSUS_BAND_MW8);
-#define CASE_NW(NWV, LRV, RIGV) if (nw == NWV && (leftright_next != 0) == LRV && (p->use_rigidity != 0) == RIGV) hipLaunchKernelGGL((k_band_update_mw<2, NWV, 8, LRV, RIGV>), dim3(n), dim3(64 * NWV), (size_t) h * sizeof(int), b->stream, b->d_desc, k, wnew, h, stride); else
-#define CASE(LRV, RIGV) CASE_NW(8, LRV, RIGV) CASE_NW(16, LRV, RIGV)
-        K_LR_RIG_FORMS(CASE) return no_form("k_band_update_mw");
-#undef CASE
-#undef CASE_NW
-    } else {
-        ProfScope ps("band_update", b->stream, 0);
-        CENSUS(LQRHIP_CENSUS_BAND_GENERIC);
-        hipLaunchKernelGGL(k_band_update, dim3(n), dim3(64), 0, b->stream, b->d_desc, k, wnew, h, stride, leftright_next);
-    }
-    {
-        // rows the band kernel handed over (flags[FLAG_OVF_ROW] .. h): the keep rule over the full width
-        ProfScope ps("dp_update", b->stream, 0);
-        if ((rc = launch_dp<true>(b, k, s.dp, rigm, wnew, h, leftright_next))) return rc;
-    }
-    HIPCK(hipGetLastError());
-    return 0;
-}
-
 extern "C" int lqrhip_seam_log_reserve(LqrHipBatch *b, int n_seams, int h)
 {
     int rc;
@@ -1548,10 +1550,8 @@ extern "C" int lqrhip_vs_commit(LqrHipBatch *b, int w0, int h0, int wc0, int n_s
 {
     int rc;
     if ((rc = batch_upload(b))) return rc;
-    size_t lds = ((size_t) n_seams + wc0) * sizeof(int);
-    // (unreachable while the host refuses frames wider than LQRHIP_MAX_FRAME_WIDTH, host/lqr_carver.c: a session carves at most wc0 - 1
-    // seams, so n_seams + wc0 <= 2 * 16384 - 1 ints = 128 KB)
-    if (lds > 150 * 1024) { g_err = "vs_commit: session too large for LDS"; return LQRHIP_EARG; }
+    size_t lds = vsc_lds(n_seams, wc0);
+    if (lds > VSC_LDS_MAX) { g_err = "vs_commit: session too large for LDS"; return LQRHIP_EARG; }
     if (lds_needs_attr(lds)) {
         HIPCK(hipFuncSetAttribute((const void *) k_vs_commit, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
         CENSUS(LQRHIP_CENSUS_LDS_ATTR_COMMIT);
@@ -1583,7 +1583,7 @@ extern "C" int lqrhip_session_check(LqrHipBatch *b, int h, int wc0, int n_seams,
     int rc;
     if (!g_selfcheck || n_seams < 1) return 0;
     if ((rc = batch_upload(b))) return rc;
-    hipLaunchKernelGGL(k_seam_check, dim3((h + 255) / 256, (unsigned) b->cs.size()), dim3(256), 0, b->stream, b->d_desc, h, wc0, n_seams, delta_x, g_dev_err);
+    hipLaunchKernelGGL(k_seam_check, dim3(tiles_of(h, 256), (unsigned) b->cs.size()), dim3(256), 0, b->stream, b->d_desc, h, wc0, n_seams, delta_x, g_dev_err);
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -1600,7 +1600,7 @@ extern "C" int lqrhip_session_rollback(LqrHipBatch *b, int w0, int h0, int first
     int rc;
     if ((rc = batch_upload(b))) return rc;
     const size_t n = (size_t) w0 * h0;
-    hipLaunchKernelGGL(k_vs_rollback, dim3((unsigned) std::min<size_t>((n + 255) / 256, 4096), (unsigned) b->cs.size()), dim3(256), 0, b->stream, b->d_desc, n, first_level, finish ? w0 : 0);
+    hipLaunchKernelGGL(k_vs_rollback, dim3((unsigned) std::min<size_t>(blocks_of(n, 256), 4096), (unsigned) b->cs.size()), dim3(256), 0, b->stream, b->d_desc, n, first_level, finish ? w0 : 0);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(b->stream));
     for (auto *c : b->cs) drop_catchup(c);
@@ -1663,7 +1663,7 @@ static int inflate_stage(LqrHipBatch *b, int w0, int h0, int l, int max_level, c
         if ((rc = pj.add(c, vs, nvs, (size_t) w1 * h0))) return rc;
     }
     if ((rc = pj.stage(b->stream, false))) return rc;
-    const size_t lds = (size_t) ((l - max_level + 1 + 31) / 32 + 1) * sizeof(unsigned);      // one bit per level of the session (the fused self-check)
+    const size_t lds = inflate_lds(l, max_level);       // one bit per level of the session (the fused self-check)
     if (pj.n_narrow)
         hipLaunchKernelGGL(k_inflate<false>, dim3(h0, (unsigned) pj.n_narrow), dim3(256), lds, b->stream, pj.d_dev.get(), w0, w1, l, max_level, g_selfcheck ? g_dev_err : (int *) nullptr);
     if (pj.n_wide())
@@ -1707,15 +1707,14 @@ extern "C" int lqrhip_vmap_stage(const int *map, int on_device, int width, int h
         if ((rc = h2d_staged(d, map, n * sizeof(int32_t)))) return rc;
         src = d;
     }
-    const size_t words = (size_t) (depth + 31) / 32;
     if (orientation) {
         if ((rc = m->own.alloc(n, "&vmap_t"))) return rc;
-        const size_t lds = VT_LINES * words * sizeof(unsigned);
-        if (lds > 56 * 1024) HIPCK(hipFuncSetAttribute((const void *) k_vmap_check_t, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-        hipLaunchKernelGGL(k_vmap_check_t, dim3((width + VT_LINES - 1) / VT_LINES), dim3(256), lds, g_stream0, src, m->own.get(), width, height, depth, g_dev_err);
+        const size_t lds = vmap_check_t_lds(depth);
+        if (vmap_t_needs_attr(lds)) HIPCK(hipFuncSetAttribute((const void *) k_vmap_check_t, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+        hipLaunchKernelGGL(k_vmap_check_t, dim3(vmap_t_blocks(width)), dim3(256), lds, g_stream0, src, m->own.get(), width, height, depth, g_dev_err);
         m->plane = m->own;
     } else {
-        hipLaunchKernelGGL(k_vmap_check, dim3(height), dim3(256), words * sizeof(unsigned), g_stream0, src, width, depth, g_dev_err);
+        hipLaunchKernelGGL(k_vmap_check, dim3(height), dim3(256), vmap_check_lds(depth), g_stream0, src, width, depth, g_dev_err);
         m->plane = src;
     }
     HIPCK(hipGetLastError());
@@ -1794,9 +1793,9 @@ extern "C" int lqrhip_transpose(LqrHipBatch *b, int w, int h)
     }
     if ((rc = pj.stage(b->stream, true))) return rc;
     if (pj.n_narrow)
-        hipLaunchKernelGGL(k_transpose, dim3((w + 31) / 32, (h + 31) / 32, (unsigned) pj.n_narrow), dim3(32, 8), 0, b->stream, pj.d_dev.get(), w, h);
+        hipLaunchKernelGGL(k_transpose, dim3(tiles_of(w, 32), tiles_of(h, 32), (unsigned) pj.n_narrow), dim3(32, 8), 0, b->stream, pj.d_dev.get(), w, h);
     if (pj.n_wide())
-        hipLaunchKernelGGL(k_transpose_px, dim3((w + 31) / 32, (h + 31) / 32, (unsigned) pj.n_wide()), dim3(32, 8), 0, b->stream, pj.d_wide(), w, h);
+        hipLaunchKernelGGL(k_transpose_px, dim3(tiles_of(w, 32), tiles_of(h, 32), (unsigned) pj.n_wide()), dim3(32, 8), 0, b->stream, pj.d_wide(), w, h);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(b->stream));
     return st.kept();
@@ -1896,7 +1895,7 @@ extern "C" int lqrhip_read_sizes(LqrHipCarver *c, int w0, int h0, int transposed
         if (transposed) {
             int wmax = 0;
             for (int k = ch.first; k < ch.first + ch.count; k++) wmax = std::max(wmax, width_of(k));
-            const dim3 grid((wmax + 31) / 32, (h0 + 31) / 32, (unsigned) ch.count);
+            const dim3 grid(tiles_of(wmax, 32), tiles_of(h0, 32), (unsigned) ch.count);
 #define LAUNCH_TS(WIDE) hipLaunchKernelGGL(k_transpose_sizes<WIDE>, grid, dim3(256), 0, g_stream0, (const SizeJob *) (d_jobs + n + ch.first), h0, (int) bytes)
             if (bytes > 4) LAUNCH_TS(true); else LAUNCH_TS(false);
 #undef LAUNCH_TS
@@ -1954,7 +1953,7 @@ static int forward_launch_init(const LqrHipCarver *c0, const FwdJob *d_jobs, int
 {
     DeepRead rd = deep_read(c0);
     rd.luma = luma != 0;
-    const dim3 grid((L + 255) / 256, H, (unsigned) n);
+    const dim3 grid(tiles_of(L, 256), H, (unsigned) n);
 #define CASE(D) if (c0->depth == D) hipLaunchKernelGGL(k_fwd_init<D>, grid, dim3(256), 0, g_stream0, d_jobs, L, H, c0->w0, strided, rd, w_start, orientation); else
     K_FWD_INIT_FORMS(CASE) return no_form("k_fwd_init");
 #undef CASE
@@ -1988,7 +1987,7 @@ extern "C" int lqrhip_forward_begin(LqrHipCarver *const *cs, int n, int depth, i
     std::unique_ptr<LqrHipForward> f(new LqrHipForward());
     f->n = n; f->L = L; f->H = H; f->depth = depth; f->orientation = orientation;
     f->pxt = L <= FWD_THREADS ? 1 : L <= 2 * FWD_THREADS ? 2 : L <= 4 * FWD_THREADS ? 4 : L <= 8 * FWD_THREADS ? 8 : 16;
-    f->lds = (size_t) 2 * L * sizeof(float);
+    f->lds = fwd_lds(L);
     const size_t px = (size_t) L * H;
     f->img.resize(n);
     for (int i = 0; i < n; i++) {
@@ -2192,7 +2191,7 @@ extern "C" int lqrhip_carver_reset(LqrHipCarver *c, const void *device_rgb, int 
         // the other); the engine's own streaming copy (k_copy16, the one that measures the HBM ceiling) takes ~10
         const size_t bytes = n * px_bytes(c), n16 = bytes / 16;
         if (n16 && !(((uintptr_t) device_rgb | (uintptr_t) c->rgb0.get()) & 15)) {
-            hipLaunchKernelGGL(k_copy16, dim3((unsigned) ((n16 + 255) / 256)), dim3(256), 0, g_stream0, (const u32x4 *) device_rgb, (u32x4 *) c->rgb0.get(), n16);
+            hipLaunchKernelGGL(k_copy16, dim3((unsigned) blocks_of(n16, 256)), dim3(256), 0, g_stream0, (const u32x4 *) device_rgb, (u32x4 *) c->rgb0.get(), n16);
             HIPCK(hipGetLastError());
             if (bytes & 15) HIPCK(hipMemcpyAsync(c->rgb0 + n16 * 16, (const uint8_t *) device_rgb + n16 * 16, bytes & 15, hipMemcpyDeviceToDevice, g_stream0));
         } else {
@@ -2229,7 +2228,7 @@ extern "C" int lqrhip_carver_reset_batch(LqrHipCarver **cs, const void *const *d
     size_t most = vs_bytes;             // the longest plane of the jobs collected
     auto flush = [&]() -> int {
         if (!nj) return 0;
-        const unsigned blocks = (unsigned) std::min<size_t>((most / 16 + 255) / 256 + 1, 4096);
+        const unsigned blocks = (unsigned) std::min<size_t>(blocks_of(most / 16, 256) + 1, 4096);
         hipLaunchKernelGGL(k_reset_jobs, dim3(blocks, (unsigned) nj), dim3(256), 0, g_stream0, jobs, vs_bytes);
         nj = 0; most = vs_bytes;
         HIPCK(hipGetLastError());
@@ -2320,7 +2319,7 @@ extern "C" int lqrhip_copy_bandwidth(unsigned long long bytes, int iters, double
     const size_t n16 = bytes / 16;
     HIPCK(hipMemsetAsync(a, 1, bytes, g_stream0));
     HIPCK(hipEventCreate(&e0.e)); HIPCK(hipEventCreate(&e1.e));
-    const dim3 grid((unsigned) ((n16 + 255) / 256));
+    const dim3 grid((unsigned) blocks_of(n16, 256));
     hipLaunchKernelGGL(k_copy16, grid, dim3(256), 0, g_stream0, (const u32x4 *) a, (u32x4 *) b, n16);     // warm-up
     HIPCK(hipEventRecord(e0.e, g_stream0));
     for (int i = 0; i < iters; i++) hipLaunchKernelGGL(k_copy16, grid, dim3(256), 0, g_stream0, (const u32x4 *) a, (u32x4 *) b, n16);
@@ -2370,7 +2369,7 @@ extern "C" int lqrhip_vmap_to_rgba(const int *vmap, int w, int h, int depth, con
     uint32_t *dout = tmp.get<uint32_t>(n, "&dout", rc);
     if (rc) return rc;
     HIPCK(hipMemcpyAsync(dv, vmap, n * sizeof(int32_t), hipMemcpyHostToDevice, g_stream0));
-    hipLaunchKernelGGL(k_vmap_ramp, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, g_stream0, dv, dout, n, depth, col_start[0], col_start[1],
+    hipLaunchKernelGGL(k_vmap_ramp, dim3((unsigned) blocks_of(n, 256)), dim3(256), 0, g_stream0, dv, dout, n, depth, col_start[0], col_start[1],
                        col_start[2], col_end[0], col_end[1], col_end[2]);
     HIPCK(hipGetLastError());
     HIPCK(hipMemcpyAsync(out_rgba, dout, n * 4, hipMemcpyDeviceToHost, g_stream0));
