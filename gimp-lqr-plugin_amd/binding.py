@@ -4,6 +4,8 @@ interface gimp-lqr-plugin's src/render.c and src/io_functions.c consume.
 `engine_api()` binds the MI355X engine (liblqr-hip.so, next to this file).  `Api(path, prefix)`
 binds any other library exporting the same ABI (the tests bind their CPU oracle and, where one
 exists, a genuine liblqr-1 this way -- nothing in this package knows about either).
+An Api may carry `absent`, a set of names its library does not export: the bind_* helpers of the
+later surfaces leave those out instead of failing.
 
 Call order in `Carver.configure` mirrors the reference's render_init_carver
 (src/render.c:220-248); read-out mirrors write_carver_to_layer (src/io_functions.c:155-164).
@@ -125,10 +127,12 @@ def bind_coldepth(api):
     """add COLDEPTH_SYMBOLS to a bound Api (the engine, or a genuine liblqr-1); returns it"""
     if not getattr(api, "has_coldepth", False):
         for name, (res, args) in COLDEPTH_SYMBOLS.items():
+            if name in getattr(api, "absent", ()):
+                continue
             fn = getattr(api.lib, api.prefix + name)      # AttributeError = missing export
             fn.restype, fn.argtypes = res, args
             setattr(api, name, fn)
-        api.has_coldepth = True
+        api.has_coldepth = hasattr(api, "lqr_carver_new_ext")      # (an Api whose `absent` covers the surface has none of it)
     return api
 
 
@@ -183,12 +187,12 @@ def bind_masks(api):
     bind_coldepth(api)
     if not getattr(api, "has_masks", False):
         for name, (res, args) in MASK_SYMBOLS.items():
-            if name.startswith("lqrx_") and not api.has_ext:
+            if (name.startswith("lqrx_") and not api.has_ext) or name in getattr(api, "absent", ()):
                 continue
             fn = getattr(api.lib, api.prefix + name)      # AttributeError = missing export
             fn.restype, fn.argtypes = res, args
             setattr(api, name, fn)
-        if api.has_ext:
+        if api.has_ext and "lqrhip_debug_mask_flushes" not in getattr(api, "absent", ()):
             api.lqrhip_debug_mask_flushes = api.lib.lqrhip_debug_mask_flushes
             api.lqrhip_debug_mask_flushes.restype, api.lqrhip_debug_mask_flushes.argtypes = C.c_ulonglong, []
         api.has_masks = True
@@ -212,7 +216,7 @@ def bind_energy(api):
     bind_coldepth(api)
     if not getattr(api, "has_energy", False):
         for name, (res, args) in ENERGY_SYMBOLS.items():
-            if name.startswith("lqrx_") and not api.has_ext:
+            if (name.startswith("lqrx_") and not api.has_ext) or name in getattr(api, "absent", ()):
                 continue
             fn = getattr(api.lib, api.prefix + name)      # AttributeError = missing export
             fn.restype, fn.argtypes = res, args

@@ -57,6 +57,10 @@
  *      lqr_carver_init lays the frame out as the first columns of the inflated layout instead of the visible
  *      pixels; it finds the further seams there, writes their levels over others, and the map it dumps
  *      afterwards holds levels twice and lacks others (tests/golden/vmap/, init_after_load_h and _v).
+ *      "What the carver that made the map gives" holds for what a map carries.  Two things it does not carry: which side
+ *      wins ties (it survives flattening and changes at every side switch; a new carver starts on the left), and the
+ *      rigidity table, which liblqr rescales at every transposition and a new carver computes afresh.  With side-switch
+ *      frequency 0 and rigidity 0 the new carver continues exactly as the old one (tests/sequence_cases.py, "reopen").
  *   6. A map dumped from a carver that was carved down to ONE column carries liblqr's finish_vsmap mark, a
  *      level above the depth in the column that is left.  The mark means what 0 means at every size the map
  *      covers; item 1 refuses it as any value above depth.  Clear it (set it to 0) before loading such a map.

@@ -40,7 +40,8 @@
  * way has been transposed --, attached carvers laid out with it).  The map passes the same validation as any caller's.  Unlike
  * lqr_vmap_load it ALSO ACCEPTS AN INITIALISED CARVER.  That state is the one lqr_vmap.h, item 5, describes (lqr_carver_init after a
  * load): the sizes the map covers are served from the map, and a later lqr_carver_resize beyond them continues with liblqr's backward
- * seams, found on the frame the forward seams leave and stacked on top of them -- a warm start.
+ * seams, found on the frame the forward seams leave and stacked on top of them -- a warm start.  (The tie side and the rigidity
+ * table are the carver's own, as they stand: lqr_vmap.h item 5 says what that means for a comparison with a new carver.)
  *
  * lqrx_carver_resize_forward(r, w1, h1) is lqr_carver_resize with forward seams: in the carver's resize order, a direction whose size
  * does not change is skipped; otherwise load_forward(|change|, that direction) and then lqr_carver_resize to the new size, shrinking

@@ -55,6 +55,8 @@
 
 #include "oracle_rename.h"
 #include "../include/lqr.h"
+#include "../include/lqr_masks.h"
+#include "../include/lqr_energy.h"
 
 #define MAXI(a, b) ((a) > (b) ? (a) : (b))
 #define MINI(a, b) ((a) < (b) ? (a) : (b))
@@ -416,9 +418,10 @@ static LqrRetVal flatten_one(LqrCarver *r)
 
     new_rgb = (guchar *) malloc((size_t) r->w * r->h * r->channels);
     if (!new_rgb) return LQR_NOMEM;
+    /* (a bias can precede lqr_carver_init, lqr_masks.h: the plane follows the layout whether or not the carver is active) */
+    if (r->bias && !(new_bias = (float *) malloc((size_t) r->w * r->h * sizeof(float)))) return LQR_NOMEM;
+    if (r->rigidity_mask && !(new_rig = (float *) malloc((size_t) r->w * r->h * sizeof(float)))) return LQR_NOMEM;
     if (r->active) {
-        if (r->bias && !(new_bias = (float *) malloc((size_t) r->w * r->h * sizeof(float)))) return LQR_NOMEM;
-        if (r->rigidity_mask && !(new_rig = (float *) malloc((size_t) r->w * r->h * sizeof(float)))) return LQR_NOMEM;
         r->m = (float *) malloc((size_t) r->w * r->h * sizeof(float));
         r->least = (int *) malloc((size_t) r->w * r->h * sizeof(int));
         if (!r->m || !r->least) return LQR_NOMEM;
@@ -493,10 +496,8 @@ static LqrRetVal transpose_carver(LqrCarver *r)
 
     new_rgb = (guchar *) malloc((size_t) r->w0 * r->h0 * r->channels);
     if (!new_rgb) return LQR_NOMEM;
-    if (r->active) {
-        if (r->bias && !(new_bias = (float *) malloc((size_t) r->w0 * r->h0 * sizeof(float)))) return LQR_NOMEM;
-        if (r->rigidity_mask && !(new_rig = (float *) malloc((size_t) r->w0 * r->h0 * sizeof(float)))) return LQR_NOMEM;
-    }
+    if (r->bias && !(new_bias = (float *) malloc((size_t) r->w0 * r->h0 * sizeof(float)))) return LQR_NOMEM;
+    if (r->rigidity_mask && !(new_rig = (float *) malloc((size_t) r->w0 * r->h0 * sizeof(float)))) return LQR_NOMEM;
     for (x = 0; x < r->w; x++) {
         for (y = 0; y < r->h; y++) {
             z0 = y * r->w0 + x;
@@ -576,13 +577,23 @@ static double mask_value(const guchar *px, int channels, int *sum_out)
     return v;
 }
 
+/* the 8-bit bias mask onto a carver that has been prepared (flat) */
+static LqrRetVal bias_rgb_area(LqrCarver *r, guchar *rgb, gint bias_factor, gint channels,
+                               gint width, gint height, gint x_off, gint y_off);
+
 LqrRetVal lqr_carver_bias_add_rgb_area(LqrCarver *r, guchar *rgb, gint bias_factor, gint channels,
                                        gint width, gint height, gint x_off, gint y_off)
+{
+    LQR_CATCH(mask_prepare(r));
+    return bias_rgb_area(r, rgb, bias_factor, channels, width, height, x_off, y_off);
+}
+
+static LqrRetVal bias_rgb_area(LqrCarver *r, guchar *rgb, gint bias_factor, gint channels,
+                               gint width, gint height, gint x_off, gint y_off)
 {
     int x, y, x0, y0, x1, y1, x2, y2, wt, ht, sum, xc, yc;
     int has_alpha = (channels == 2 || channels >= 4);
     int cc = channels - (has_alpha ? 1 : 0);
-    LQR_CATCH(mask_prepare(r));
     if (bias_factor == 0) return LQR_OK;
     if (!r->bias) {
         r->bias = (float *) calloc((size_t) r->w0 * r->h0, sizeof(float));
@@ -634,6 +645,121 @@ LqrRetVal lqr_carver_rigmask_add_rgb_area(LqrCarver *r, guchar *rgb, gint channe
     }
     return LQR_OK;
 }
+
+/* ======================= computed masks (include/lqr_masks.h) ============ */
+/* liblqr 0.4.1's gdouble planes, single values and clears, pinned to tests/golden/masks/ by tests/test_oracle_later_calls.py.
+ * Every operation is rounded to its C type.  Two places side with the header, not with liblqr, because liblqr is not memory-safe
+ * there: an _xy call outside the image returns LQR_ERROR (liblqr writes outside its plane), and the bias forms on an attached carver
+ * return LQR_ERROR (liblqr keeps a plane nothing reads, and may flatten the attached carver alone).  The offsets of a carver in
+ * orientation 1 are applied in image orientation, as the rgb forms above apply them (lqr_masks.h, "Orientation 1"). */
+static int needs_flatten(const LqrCarver *r)
+{
+    return r->w != r->w0 || r->w_start != r->w0 || r->h != r->h0 || r->h_start != r->h0;
+}
+
+/* the bias forms are served before lqr_carver_init: the plane belongs to the base layout */
+static LqrRetVal bias_prepare(LqrCarver *r)
+{
+    if (r->root) return LQR_ERROR;
+    if (needs_flatten(r)) LQR_CATCH(lqr_carver_flatten(r));
+    return LQR_OK;
+}
+
+static LqrRetVal plane_ensure(LqrCarver *r, float **plane)
+{
+    if (!*plane && !(*plane = (float *) calloc((size_t) r->w0 * r->h0, sizeof(float)))) return LQR_NOMEM;
+    return LQR_OK;
+}
+
+static LqrRetVal mask_area_f(LqrCarver *r, const gdouble *buffer, int is_rig, int bias_factor, int width, int height, int x_off, int y_off)
+{
+    int x, y, x0, y0, x1, y1, x2, y2, wt, ht, xc, yc;
+    if (!is_rig && bias_factor == 0) return LQR_OK;             /* before anything else: no flattening either */
+    LQR_CATCH(is_rig ? mask_prepare(r) : bias_prepare(r));
+    LQR_CATCH(plane_ensure(r, is_rig ? &r->rigidity_mask : &r->bias));
+    wt = r->transposed ? r->h : r->w;
+    ht = r->transposed ? r->w : r->h;
+    x0 = MINI(0, x_off); y0 = MINI(0, y_off);
+    x1 = MAXI(0, x_off); y1 = MAXI(0, y_off);
+    x2 = MINI(wt, width + x_off); y2 = MINI(ht, height + y_off);
+    for (y = 0; y < y2 - y1; y++) {
+        for (x = 0; x < x2 - x1; x++) {
+            gdouble v = buffer[(size_t) (y - y0) * width + (x - x0)];
+            xc = r->transposed ? y + y1 : x + x1;
+            yc = r->transposed ? x + x1 : y + y1;
+            if (is_rig) r->rigidity_mask[(size_t) yc * r->w0 + xc] = (gfloat) v;
+            else r->bias[(size_t) yc * r->w0 + xc] += (gfloat) ((gdouble) bias_factor * v / 2);
+        }
+    }
+    if (!is_rig) r->nrg_uptodate = 0;
+    return LQR_OK;
+}
+
+LqrRetVal lqr_carver_bias_add_area(LqrCarver *r, gdouble *buffer, gint bias_factor, gint width, gint height, gint x_off, gint y_off)
+{
+    return mask_area_f(r, buffer, 0, bias_factor, width, height, x_off, y_off);
+}
+LqrRetVal lqr_carver_bias_add(LqrCarver *r, gdouble *buffer, gint bias_factor)
+{
+    return mask_area_f(r, buffer, 0, bias_factor, lqr_carver_get_width(r), lqr_carver_get_height(r), 0, 0);
+}
+LqrRetVal lqr_carver_rigmask_add_area(LqrCarver *r, gdouble *buffer, gint width, gint height, gint x_off, gint y_off)
+{
+    return mask_area_f(r, buffer, 1, 0, width, height, x_off, y_off);
+}
+/* (the mask is taken to have the carver's current size, as the header documents it; liblqr's own reading of a carver that is not
+ * flat or lies in orientation 1 runs past the mask's end) */
+LqrRetVal lqr_carver_rigmask_add(LqrCarver *r, gdouble *buffer)
+{
+    return mask_area_f(r, buffer, 1, 0, lqr_carver_get_width(r), lqr_carver_get_height(r), 0, 0);
+}
+
+/* the two 8-bit forms at the carver's size: the bias one is served before lqr_carver_init, the _area form of lqr.h is not */
+LqrRetVal lqr_carver_bias_add_rgb(LqrCarver *r, guchar *rgb, gint bias_factor, gint channels)
+{
+    if (bias_factor == 0) return LQR_OK;
+    LQR_CATCH(bias_prepare(r));
+    return bias_rgb_area(r, rgb, bias_factor, channels, lqr_carver_get_width(r), lqr_carver_get_height(r), 0, 0);
+}
+LqrRetVal lqr_carver_rigmask_add_rgb(LqrCarver *r, guchar *rgb, gint channels)
+{
+    return lqr_carver_rigmask_add_rgb_area(r, rgb, channels, lqr_carver_get_width(r), lqr_carver_get_height(r), 0, 0);
+}
+
+static LqrRetVal mask_xy(LqrCarver *r, int is_rig, gdouble v, int x, int y)
+{
+    float **plane = is_rig ? &r->rigidity_mask : &r->bias;
+    size_t z;
+    LQR_CATCH(is_rig ? mask_prepare(r) : bias_prepare(r));
+    if (x < 0 || y < 0 || x >= lqr_carver_get_width(r) || y >= lqr_carver_get_height(r)) return LQR_ERROR;
+    LQR_CATCH(plane_ensure(r, plane));
+    z = r->transposed ? (size_t) x * r->w0 + y : (size_t) y * r->w0 + x;
+    if (is_rig) (*plane)[z] += (gfloat) v;              /* it adds: liblqr 0.4.1's lqr_carver_rigmask_add_xy does */
+    else { (*plane)[z] += (gfloat) v / 2; r->nrg_uptodate = 0; }
+    return LQR_OK;
+}
+LqrRetVal lqr_carver_bias_add_xy(LqrCarver *r, gdouble bias, gint x, gint y)
+{
+    if (bias == 0) return LQR_OK;
+    return mask_xy(r, 0, bias, x, y);
+}
+LqrRetVal lqr_carver_rigmask_add_xy(LqrCarver *r, gdouble rigidity, gint x, gint y) { return mask_xy(r, 1, rigidity, x, y); }
+
+void lqr_carver_bias_clear(LqrCarver *r) { free(r->bias); r->bias = NULL; r->nrg_uptodate = 0; }
+void lqr_carver_rigmask_clear(LqrCarver *r) { free(r->rigidity_mask); r->rigidity_mask = NULL; }
+
+/* test hooks: the plane of a FLAT carver in image orientation, zeros where there is none */
+static LqrRetVal plane_read(LqrCarver *r, const float *plane, gfloat *out)
+{
+    int x, y, W = lqr_carver_get_width(r), H = lqr_carver_get_height(r);
+    if (needs_flatten(r)) return LQR_ERROR;
+    for (y = 0; y < H; y++)
+        for (x = 0; x < W; x++)
+            out[(size_t) y * W + x] = !plane ? 0 : r->transposed ? plane[(size_t) x * r->w0 + y] : plane[(size_t) y * r->w0 + x];
+    return LQR_OK;
+}
+LqrRetVal lqrx_carver_get_bias(LqrCarver *r, gfloat *out) { return plane_read(r, r->bias, out); }
+LqrRetVal lqrx_carver_get_rigmask(LqrCarver *r, gfloat *out) { return plane_read(r, r->rigidity_mask, out); }
 
 /* ======================= energy (E3, E4, E6) ============================= */
 /* brightness in double: mean of colour channels / 255 (or Rec.709 luma),
@@ -1270,6 +1396,28 @@ LqrRetVal lqrx_carver_get_energy(LqrCarver *r, gfloat *buffer)
     LQR_CATCH(build_emap(r));
     for (y = 0; y < r->h; y++)
         for (x = 0; x < r->w; x++) buffer[(size_t) y * r->w + x] = r->en[r->raw[y][x]];
+    return LQR_OK;
+}
+
+/* ======================= energy read-out (include/lqr_energy.h) ========== */
+/* liblqr 0.4.1's lqr_carver_get_true_energy, pinned to tests/golden/energy/ by tests/test_oracle_later_calls.py: the carver is
+ * prepared as a resize prepares it for seams of `orientation` (flattened when it is not at the width its map was built for;
+ * transposed, and left that way, when it lies the other way), the energy is built in that frame and written in IMAGE orientation.
+ * Served before lqr_carver_init.  The normalised form and the picture are tests/energy_cases.py's normalised() / picture() of this
+ * plane.  As lqr_energy.h has it, an attached carver returns LQR_ERROR (liblqr would re-lay it alone). */
+LqrRetVal lqr_carver_get_true_energy(LqrCarver *r, gfloat *buffer, gint orientation)
+{
+    int x, y, W, H;
+    if (!r || !buffer || (orientation != 0 && orientation != 1) || r->root) return LQR_ERROR;
+    LQR_CATCH(init_energy_related(r));
+    if (r->w != r->w_start - r->max_level + 1) LQR_CATCH(lqr_carver_flatten(r));
+    if (orientation != r->transposed) LQR_CATCH(transpose_carver(r));
+    LQR_CATCH(build_emap(r));
+    W = lqr_carver_get_width(r);
+    H = lqr_carver_get_height(r);
+    for (y = 0; y < H; y++)
+        for (x = 0; x < W; x++)
+            buffer[(size_t) y * W + x] = r->en[orientation ? r->raw[x][y] : r->raw[y][x]];
     return LQR_OK;
 }
 
