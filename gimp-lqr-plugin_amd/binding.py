@@ -326,6 +326,30 @@ def bind_forward(api):
     return api
 
 
+# include_ext/lqr_static.h: static seams for a clip -- the frames folded into one energy plane (to device or host memory), the seam map
+# found on it, the map loaded into every frame, and the batch resize made of the two.  The engine's own, as the forward calls are
+_F = C.c_float
+STATIC_SYMBOLS = {
+    "lqrx_carvers_static_energy_device": (_I, [C.POINTER(_P), _I, _I, _F, _P]),
+    "lqrx_carvers_static_energy": (_I, [C.POINTER(_P), _I, _I, _F, _P]),
+    "lqrx_carvers_static_map": (_P, [C.POINTER(_P), _I, _I, _I, _F, _I, _F]),
+    "lqrx_carvers_load_static": (_I, [C.POINTER(_P), _I, _I, _I, _F, _I, _F]),
+    "lqrx_carvers_resize_static": (_I, [C.POINTER(_P), _I, _I, _I, _F, _I, _F]),
+}
+
+
+def bind_static(api):
+    """add STATIC_SYMBOLS (and what they compose: the forward hooks, seam maps, sizes) to a bound Api (the engine); returns it"""
+    bind_sizes(bind_forward(api))
+    if not getattr(api, "has_static", False):
+        for name, (res, args) in STATIC_SYMBOLS.items():
+            fn = getattr(api.lib, api.prefix + name)      # AttributeError = missing export
+            fn.restype, fn.argtypes = res, args
+            setattr(api, name, fn)
+        api.has_static = True
+    return api
+
+
 def _vmap_new(api, m):
     """a LqrVMap around a malloc'd copy of m["data"] (h x w int32, image orientation), which the map owns"""
     data = np.ascontiguousarray(m["data"], dtype=np.int32)
@@ -389,6 +413,11 @@ def engine_sizes_api():
 def engine_forward_api():
     """the engine with the colour-depth, seam-map loading and forward-energy surfaces bound"""
     return bind_forward(bind_coldepth(engine_api()))
+
+
+def engine_static_api():
+    """the engine with everything the static-seam calls compose bound: depths, types, masks, energies, maps, sizes, forward hooks"""
+    return bind_static(bind_energy(bind_masks(bind_imagetype(bind_coldepth(engine_api())))))
 
 
 def engine_control_api():
@@ -1057,3 +1086,46 @@ def forward_maps_device(carvers, tensors, depth, orientation):
     arr = (C.c_void_p * len(carvers))(*[c.p for c in carvers])
     ptrs = (C.c_void_p * len(carvers))(*[t.data_ptr() for t in tensors])
     return a.lqrx_carver_forward_maps_device(arr, len(carvers), int(depth), int(orientation), ptrs)
+
+
+def _frames(carvers):
+    return (C.c_void_p * len(carvers))(*[c.p for c in carvers])
+
+
+def static_energy(carvers, orientation, alpha, guard=0):
+    """lqrx_carvers_static_energy: (LqrRetVal, h x w float32 in image orientation, the `guard` bytes after it -- 0xA5 when intact)"""
+    a = bind_static(carvers[0].api)
+    w, h = a.lqr_carver_get_width(carvers[0].p), a.lqr_carver_get_height(carvers[0].p)
+    buf = np.full(w * h * 4 + guard, 0xa5, np.uint8)
+    ret = a.lqrx_carvers_static_energy(_frames(carvers), len(carvers), int(orientation), float(alpha), buf.ctypes.data)
+    return ret, buf[:w * h * 4].view(np.float32).reshape(h, w).copy(), buf[w * h * 4:].copy()
+
+
+def static_energy_device(carvers, tensor, orientation, alpha):
+    """lqrx_carvers_static_energy_device into a contiguous float32 torch tensor on the device; the LqrRetVal"""
+    a = bind_static(carvers[0].api)
+    assert tensor.is_cuda and tensor.is_contiguous() and tensor.dtype == torch.float32
+    assert tensor.numel() >= a.lqr_carver_get_width(carvers[0].p) * a.lqr_carver_get_height(carvers[0].p)
+    torch.cuda.current_stream().synchronize()          # the engine writes the buffer on a stream of its own
+    return a.lqrx_carvers_static_energy_device(_frames(carvers), len(carvers), int(orientation), float(alpha), tensor.data_ptr())
+
+
+def static_map(carvers, depth, orientation, alpha, delta_x=1, rigidity=0.0):
+    """lqrx_carvers_static_map: the dict vmap_dump returns, or None where the call returned NULL"""
+    a = bind_static(carvers[0].api)
+    v = a.lqrx_carvers_static_map(_frames(carvers), len(carvers), int(depth), int(orientation), float(alpha), int(delta_x), float(rigidity))
+    if not v:
+        return None
+    d = carvers[0]._vmap_to_dict(v)
+    a.lqr_vmap_destroy(v)
+    return d
+
+
+def load_static(carvers, depth, orientation, alpha, delta_x=1, rigidity=0.0):
+    a = bind_static(carvers[0].api)
+    return a.lqrx_carvers_load_static(_frames(carvers), len(carvers), int(depth), int(orientation), float(alpha), int(delta_x), float(rigidity))
+
+
+def resize_static(carvers, w1, h1, alpha, delta_x=1, rigidity=0.0):
+    a = bind_static(carvers[0].api)
+    return a.lqrx_carvers_resize_static(_frames(carvers), len(carvers), int(w1), int(h1), float(alpha), int(delta_x), float(rigidity))

@@ -14,6 +14,7 @@
 //   k_energy_out.hip energy read-outs (lqr_energy.h) k_energy_range (squash, min / max per workgroup), k_energy_out (normalise, expand to pixels, image orientation)
 //   k_sizes.hip      many sizes in one pass (lqr_sizes.h) k_compact_sizes (up to 64 levels ranked from one load of a row), k_transpose_sizes (a width per job)
 //   k_forward.hip    forward-energy seam maps (include_ext/lqr_forward.h) k_fwd_init (I, P, positions from the base layouts), k_fwd_seam (sweep, pick, walk: one workgroup per image), k_fwd_remove
+//   k_static.hip     static seams for a clip (include_ext/lqr_static.h) k_static_fold (up to 16 frames a launch into the running S, T, I_prev planes; the last group mixes E)
 //   lqr_shim.hip     the lqrhip_* C ABI of include/lqr_hip.h: allocation cache, batches, the per-seam launch sequence
 //   lqr_plan.h       which form of each stage that sequence runs (plain C++17, no HIP: also compiled alone by tests/test_plan.py)
 //   lqr_beside.h     k_carve_v's side bound, work-list entries and their readiness (plain C++17, no HIP: also compiled alone by tests/test_backtrack_beside.py)
@@ -578,4 +579,14 @@ struct FwdJob {
     int8_t *choice;         // the parent each pixel of the last sweep chose: -1, 0, 1
     int32_t *seam;          // the last seam: a column per line
     int32_t *map;           // the result, image orientation
+};
+// static seams for a clip (k_static.hip, include_ext/lqr_static.h).  A workgroup of STATIC_THREADS folds a tile of STATIC_TILE x STATIC_TILE image pixels
+// (the size k_energy_out writes) over the STATIC_GROUP frames of a launch
+#define STATIC_TILE 64
+#define STATIC_THREADS 512          // 8 rows of the tile per thread (256 threads with 16 rows each need twice the registers: DESIGN.md 3.8 has the counts)
+#define STATIC_GROUP 16
+// one frame of a clip: where its pixels and bias lie (the carver's base layout; bias0 null: no bias plane)
+struct StaticFrame {
+    const uint8_t *rgb0;
+    const float *bias0;
 };

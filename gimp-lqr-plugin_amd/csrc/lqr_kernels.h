@@ -114,6 +114,15 @@ template <int DEPTH> __global__ __launch_bounds__(256) void k_fwd_init(const Fwd
 template <int PXT> __global__ __launch_bounds__(FWD_THREADS) void k_fwd_seam(const FwdJob *jobs, int wc, int L, int H);
 __global__ __launch_bounds__(FWD_REMOVE_THREADS) void k_fwd_remove(const FwdJob *jobs, int wc, int L, int H, int level, int orientation);
 
+// k_static.hip (static seams for a clip, include_ext/lqr_static.h).  X(NRG, DEPTH, PACKED): NRG 0 / 1 / 2 / 6 (luma is DeepRead.luma, as on the value
+// plane: plane_nrg in lqr_shim.hip), DEPTH the LqrColDepth, PACKED 8-bit grey / RGB (+ alpha) through px_bright.  Grid: tiles across x tiles down
+#define K_STATIC_FOLD_FORMS(X) X(0, 0, true) X(1, 0, true) X(2, 0, true) X(6, 0, true) X(0, 0, false) X(1, 0, false) X(2, 0, false) X(6, 0, false) \
+    X(0, 1, false) X(1, 1, false) X(2, 1, false) X(6, 1, false) X(0, 2, false) X(1, 2, false) X(2, 2, false) X(6, 2, false) \
+    X(0, 3, false) X(1, 3, false) X(2, 3, false) X(6, 3, false)
+template <int NRG, int DEPTH, bool PACKED>
+__global__ __launch_bounds__(STATIC_THREADS) void k_static_fold(const StaticFrame *frames, int count, int first, int W, int H, int transposed, int orientation, DeepRead rd,
+                                                     float alpha, float *s_plane, float *t_plane, float *i_plane, float *e_out);
+
 // k_masks.hip (computed masks, include/lqr_masks.h: T = float or double)
 template <class T> __global__ __launch_bounds__(256) void k_mask_add_f(float *plane, int w0, const T *mask, int mw, int x0, int y0, int x1, int y1, int nx, int ny,
                                                                        int transposed, int is_rig, int bias_factor);

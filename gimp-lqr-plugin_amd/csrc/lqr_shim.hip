@@ -2070,6 +2070,97 @@ extern "C" int lqrhip_forward_intensity(LqrHipCarver *c, int orientation, int tr
     return 0;
 }
 
+// ---- include_ext/lqr_static.h: the frames of a clip folded into one energy plane (kernel in k_static.hip) -----------------------------------
+// A fold owns, through its Scratch, the table of frame pointers, the running planes S, T and I_prev (clips of more than STATIC_GROUP
+// frames only) and the plane E unless the caller gave device memory for it: all taken in lqrhip_static_begin before anything is
+// launched.  It runs on g_stream0, reads the carvers' base layouts and changes nothing of theirs.
+struct __attribute__((visibility("hidden"))) LqrHipStatic {
+    Scratch tmp{g_stream0};
+    std::vector<StaticFrame> frames;        // (read by the copy to d_frames)
+    StaticFrame *d_frames = nullptr;
+    float *s = nullptr, *t = nullptr, *ip = nullptr, *e = nullptr;
+    int n = 0, W = 0, H = 0, transposed = 0, orientation = 0, nrg = 0, depth = 0, next = 0;
+    bool packed = false;
+    float alpha = 0.0f;
+    DeepRead rd{};
+};
+extern "C" int lqrhip_static_begin(LqrHipCarver *const *cs, int n, int orientation, int transposed, int nrg_func, float alpha, void *device_energy,
+                                   LqrHipStatic **out)
+{
+    if (out) *out = nullptr;
+    if (!cs || !out || n < 1 || n > LQRHIP_STATIC_MAX_FRAMES || (orientation != 0 && orientation != 1) || !(alpha >= 0.0f && alpha <= 1.0f)) {
+        g_err = "static energy: arguments";
+        return LQRHIP_EARG;
+    }
+    const LqrHipCarver *c0 = cs[0];
+    for (int i = 0; i < n; i++) {
+        const LqrHipCarver *c = cs[i];
+        if (!c || c->root || c->w0 != c0->w0 || c->h0 != c0->h0 || c->ch != c0->ch || c->depth != c0->depth || c->mode != c0->mode ||
+            c->alpha != c0->alpha || c->black != c0->black) {
+            g_err = "static energy: root carvers of one shape and pixel kind";
+            return LQRHIP_EARG;
+        }
+    }
+    int rc;
+    for (int i = 0; i < n; i++)
+        if ((rc = batch_sync_of(cs[i]))) return rc;     // whatever still writes the base layouts
+    std::unique_ptr<LqrHipStatic> st(new LqrHipStatic());
+    st->n = n; st->transposed = transposed != 0; st->orientation = orientation; st->alpha = alpha;
+    st->W = transposed ? c0->h0 : c0->w0; st->H = transposed ? c0->w0 : c0->h0;
+    const int nrg = nrg_index(nrg_func);
+    st->nrg = plane_nrg(true, nrg);
+    st->rd = deep_read(c0);
+    st->rd.luma = nrg >= 3 && nrg <= 5;
+    st->depth = c0->depth;
+    st->packed = !reads_value(c0);
+    const size_t px = (size_t) st->W * st->H;
+    st->d_frames = st->tmp.get<StaticFrame>((size_t) n, "&static_frames", rc);
+    if (rc) return rc;
+    if (n > STATIC_GROUP) {
+        if (!(st->s = st->tmp.get<float>(px, "&static_s", rc))) return rc;
+        if (!(st->t = st->tmp.get<float>(px, "&static_t", rc))) return rc;
+        if (!(st->ip = st->tmp.get<float>(px, "&static_i", rc))) return rc;
+    }
+    st->e = (float *) device_energy;
+    if (!st->e && !(st->e = st->tmp.get<float>(px, "&static_e", rc))) return rc;
+    for (int i = 0; i < n; i++) st->frames.push_back(StaticFrame{cs[i]->rgb0, cs[i]->bias0});
+    // -- everything is allocated
+    HIPCK(hipMemcpyAsync(st->d_frames, st->frames.data(), (size_t) n * sizeof(StaticFrame), hipMemcpyHostToDevice, g_stream0));
+    *out = st.release();
+    return 0;
+}
+extern "C" int lqrhip_static_groups(const LqrHipStatic *st) { return st ? tiles_of(st->n, STATIC_GROUP) : 0; }
+// the next group of frames: one launch
+extern "C" int lqrhip_static_fold(LqrHipStatic *st)
+{
+    if (!st || st->next >= st->n) { g_err = "static energy: no frames left to fold"; return LQRHIP_EARG; }
+    const int first = st->next, count = std::min(STATIC_GROUP, st->n - first);
+    const bool last = first + count == st->n;
+    const dim3 grid(tiles_of(st->W, STATIC_TILE), tiles_of(st->H, STATIC_TILE));
+#define CASE(N, D, P) if (st->nrg == N && st->depth == D && st->packed == P) \
+        hipLaunchKernelGGL((k_static_fold<N, D, P>), grid, dim3(STATIC_THREADS), 0, g_stream0, (const StaticFrame *) st->d_frames + first, count, first, st->W, st->H, \
+                           st->transposed, st->orientation, st->rd, st->alpha, st->s, st->t, st->ip, last ? st->e : (float *) nullptr); else
+    K_STATIC_FOLD_FORMS(CASE) return no_form("k_static_fold");
+#undef CASE
+    CENSUS(LQRHIP_CENSUS_STATIC_FOLD);
+    HIPCK(hipGetLastError());
+    st->next = first + count;
+    return 0;
+}
+// waits for the fold; host_energy non-null: E, width x height floats, copied there.  0: E is complete
+extern "C" int lqrhip_static_finish(LqrHipStatic *st, float *host_energy)
+{
+    if (!st || st->next != st->n) { g_err = "static energy: the fold is not complete"; return LQRHIP_EARG; }
+    HIPCK(hipStreamSynchronize(g_stream0));
+    int rc = check_dev_error();
+    if (rc) return rc;
+    if (host_energy && (rc = d2h_staged(host_energy, st->e, (size_t) st->W * st->H * sizeof(float)))) return rc;
+    st->tmp.done();
+    return 0;
+}
+extern "C" const float *lqrhip_static_energy(const LqrHipStatic *st) { return st ? st->e : nullptr; }
+extern "C" void lqrhip_static_release(LqrHipStatic *st) { delete st; }
+
 extern "C" int lqrhip_mask_line_max(const unsigned char *mask, int channels, int width, int height, int a0, int b0, int n_lines,
                                     int line_len, int direction)
 {

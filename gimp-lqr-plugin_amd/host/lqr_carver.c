@@ -33,6 +33,7 @@
 #include "../../include/lqr_control.h"
 #include "../../include/lqr_sizes.h"
 #include "../../include_ext/lqr_forward.h"
+#include "../../include_ext/lqr_static.h"
 #include "../../include/lqr_hip.h"
 #include "lqr_mask_queue.h"
 #include "lqr_sched.h"
@@ -1267,6 +1268,177 @@ int lqrhip_read_forward_intensity(const void *carver, int orientation, float *ou
     if (!r || r->root || !out || !lqr_geom_is_flat(&r->geo)) return LQRHIP_EARG;
     return lqrhip_forward_intensity(r->dev, orientation, r->geo.transposed,
                                     r->nrg_func >= LQR_EF_LUMA_GRAD_NORM && r->nrg_func <= LQR_EF_LUMA_GRAD_XABS, out);
+}
+
+/* ======================= static seams for a clip (lqr_static.h) ========== */
+/* The up-front checks and the composition: the fold runs in k_static.hip behind lqrhip_static_*, the seams are found by an LQR_EF_NULL
+ * carver of this file's own API, and the map is loaded by group_vmap_load_entered like any other. */
+
+/* what refuses a call before any device work.  depth 0: an energy call, which has no depth, delta_x or line length to refuse */
+static LqrRetVal static_check(LqrCarver *const *rs, int n, int depth, int orientation, float alpha, int delta_x, int with_map, const char *who)
+{
+    int i, L;
+    const char *why = NULL;
+    if (!rs) why = "NULL frames";
+    else if (n < 1 || n > LQRHIP_STATIC_MAX_FRAMES) why = "1 .. 65535 frames";
+    else if (orientation != 0 && orientation != 1) why = "orientation is 0 or 1";
+    else if (!(alpha >= 0.0f && alpha <= 1.0f)) why = "alpha lies in [0, 1]";
+    else if (with_map && (delta_x < 0 || delta_x > LQRHIP_MAX_DELTA)) why = "delta_x is 0 .. 16, what lqr_carver_init takes";
+    for (i = 0; !why && i < n; i++) {
+        if (!rs[i]) why = "NULL frame";
+        else if (rs[i]->root) why = "an attached carver follows its root";
+        else if (i && !same_config(rs[0], rs[i])) why = "the frames are not of one configuration";
+    }
+    if (why) { fprintf(stderr, "liblqr-hip: %s refused: %s\n", who, why); return LQR_ERROR; }
+    if (!with_map) return LQR_OK;
+    L = orientation ? lqr_carver_get_height(rs[0]) : lqr_carver_get_width(rs[0]);
+    if (depth < 1 || depth >= L || L > LQRHIP_MAX_FRAME_WIDTH) {
+        fprintf(stderr, "liblqr-hip: %s refused: depth %d on lines of %d (0 < depth < line length <= %d)\n", who, depth, L, LQRHIP_MAX_FRAME_WIDTH);
+        return LQR_ERROR;
+    }
+    return LQR_OK;
+}
+
+static int roots_cancelled(LqrCarver *const *rs, int n)
+{
+    int i;
+    for (i = 0; i < n; i++)
+        if (lqr_state_check(&rs[i]->state)) return 1;
+    return 0;
+}
+
+/* Inside the call (roots_enter): flatten what is not flat, then the fold.  E goes to device_energy (device memory) if that is given
+ * and to host_energy if that is; with neither the fold keeps it.  On LQR_OK *out holds the finished fold, which the caller releases */
+static LqrRetVal static_fold_entered(LqrCarver **rs, int n, int orientation, float alpha, float *device_energy, float *host_energy, LqrHipStatic **out)
+{
+    LqrHipCarver **ds;
+    LqrHipStatic *st = NULL;
+    LqrRetVal ret;
+    int i, groups;
+    *out = NULL;
+    if (roots_cancelled(rs, n)) return LQR_USRCANCEL;
+    for (i = 0; i < n; i++) LQR_CATCH(mask_queue_flush(rs[i]));
+    if (!lqr_geom_is_flat(&rs[0]->geo)) {
+        Group g;
+        LQR_CATCH(group_open(&g, rs, n));
+        ret = group_flatten(&g);
+        if (ret != LQR_OK) { int k; for (k = 0; k < g.nb; k++) lqrhip_batch_abort(g.b[k]); }
+        group_close(&g);
+        LQR_CATCH(ret);
+    }
+    ds = (LqrHipCarver **) malloc((size_t) n * sizeof *ds);
+    if (!ds) return LQR_NOMEM;
+    for (i = 0; i < n; i++) ds[i] = rs[i]->dev;
+    ret = hip_ret(lqrhip_static_begin(ds, n, orientation, rs[0]->geo.transposed, rs[0]->nrg_func, alpha, device_energy, &st));
+    free(ds);
+    groups = ret == LQR_OK ? lqrhip_static_groups(st) : 0;
+    for (i = 0; ret == LQR_OK && i < groups; i++) {
+        if (roots_cancelled(rs, n)) ret = LQR_USRCANCEL;
+        else ret = hip_ret(lqrhip_static_fold(st));
+    }
+    if (ret == LQR_OK) ret = hip_ret(lqrhip_static_finish(st, host_energy));
+    if (ret != LQR_OK) { lqrhip_static_release(st); return ret; }
+    *out = st;
+    return LQR_OK;
+}
+
+static LqrRetVal static_energy(LqrCarver **rs, int n, int orientation, float alpha, float *device_energy, float *host_energy, const char *who)
+{
+    LqrHipStatic *st;
+    LqrRetVal ret;
+    LQR_CATCH(static_check(rs, n, 0, orientation, alpha, 0, 0, who));
+    if (!device_energy && !host_energy) { fprintf(stderr, "liblqr-hip: %s refused: NULL energy\n", who); return LQR_ERROR; }
+    LQR_CATCH(roots_enter(rs, n, LQR_STATE_RESIZING));
+    ret = static_fold_entered(rs, n, orientation, alpha, device_energy, host_energy, &st);
+    if (ret == LQR_OK) lqrhip_static_release(st);
+    roots_leave(rs, n);
+    return ret;
+}
+LqrRetVal lqrx_carvers_static_energy_device(LqrCarver **frames, gint n, gint orientation, gfloat alpha, gfloat *device_energy)
+{
+    return static_energy(frames, n, orientation, alpha, device_energy, NULL, "lqrx_carvers_static_energy_device");
+}
+LqrRetVal lqrx_carvers_static_energy(LqrCarver **frames, gint n, gint orientation, gfloat alpha, gfloat *energy)
+{
+    return static_energy(frames, n, orientation, alpha, NULL, energy, "lqrx_carvers_static_energy");
+}
+
+/* Inside the call: the fold, then the key carver -- an LQR_EF_NULL carver on a plane of zeros whose bias plane is E -- carved by `depth`
+ * seams, its map dumped.  The key carver is destroyed on every path.  (Its resize is a call of its own and is not interrupted.) */
+static LqrRetVal static_map_entered(LqrCarver **rs, int n, int depth, int orientation, float alpha, int delta_x, float rigidity, LqrVMap **out)
+{
+    LqrHipStatic *st;
+    LqrCarver *key;
+    guchar *zeros;
+    LqrRetVal ret;
+    const int w = lqr_carver_get_width(rs[0]), h = lqr_carver_get_height(rs[0]);
+    *out = NULL;
+    LQR_CATCH(static_fold_entered(rs, n, orientation, alpha, NULL, NULL, &st));
+    zeros = (guchar *) calloc((size_t) w * h, 1);
+    key = zeros ? lqr_carver_new(zeros, w, h, 1) : NULL;        /* (the carver owns `zeros` from here) */
+    if (!key) { free(zeros); lqrhip_static_release(st); return LQR_NOMEM; }
+    ret = lqr_carver_set_energy_function_builtin(key, LQR_EF_NULL);
+    if (ret == LQR_OK) ret = lqrx_carver_bias_add_area_device(key, lqrhip_static_energy(st), LQR_COLDEPTH_32F, 2, w, h, 0, 0);
+    lqrhip_static_release(st);          /* (the bias plane holds E now) */
+    if (ret == LQR_OK) ret = lqr_carver_init(key, delta_x, rigidity);
+    if (ret == LQR_OK && roots_cancelled(rs, n)) ret = LQR_USRCANCEL;
+    if (ret == LQR_OK) ret = lqr_carver_resize(key, orientation ? w : w - depth, orientation ? h - depth : h);
+    if (ret == LQR_OK && roots_cancelled(rs, n)) ret = LQR_USRCANCEL;
+    if (ret == LQR_OK && !(*out = lqr_vmap_dump(key))) ret = LQR_NOMEM;
+    lqr_carver_destroy(key);
+    return ret;
+}
+
+LqrVMap *lqrx_carvers_static_map(LqrCarver **frames, gint n, gint depth, gint orientation, gfloat alpha, gint delta_x, gfloat rigidity)
+{
+    LqrVMap *v = NULL;
+    if (static_check(frames, n, depth, orientation, alpha, delta_x, 1, "lqrx_carvers_static_map") != LQR_OK) return NULL;
+    if (roots_enter(frames, n, LQR_STATE_RESIZING) != LQR_OK) return NULL;
+    (void) static_map_entered(frames, n, depth, orientation, alpha, delta_x, rigidity, &v);
+    roots_leave(frames, n);
+    return v;
+}
+
+LqrRetVal lqrx_carvers_load_static(LqrCarver **frames, gint n, gint depth, gint orientation, gfloat alpha, gint delta_x, gfloat rigidity)
+{
+    LqrVMap *v;
+    LqrRetVal ret;
+    LQR_CATCH(static_check(frames, n, depth, orientation, alpha, delta_x, 1, "lqrx_carvers_load_static"));
+    LQR_CATCH(roots_enter(frames, n, LQR_STATE_RESIZING));
+    ret = static_map_entered(frames, n, depth, orientation, alpha, delta_x, rigidity, &v);
+    if (ret == LQR_OK) {
+        /* (the key carver's map travels through host memory: lqr_static.h) */
+        ret = group_vmap_load_entered(frames, n, v->buffer, 0, v->width, v->height, v->depth, v->orientation);
+        lqr_vmap_destroy(v);
+    }
+    roots_leave(frames, n);
+    return ret;
+}
+
+LqrRetVal lqrx_carvers_resize_static(LqrCarver **frames, gint n, gint w1, gint h1, gfloat alpha, gint delta_x, gfloat rigidity)
+{
+    int w, h, dir, k;
+    LQR_CATCH(static_check(frames, n, 0, 0, alpha, delta_x, 0, "lqrx_carvers_resize_static"));
+    w = lqr_carver_get_width(frames[0]); h = lqr_carver_get_height(frames[0]);
+    /* both directions are decided before either changes anything: no line has |change| seams, no carved frame is wider than the engine's */
+    if (delta_x < 0 || delta_x > LQRHIP_MAX_DELTA || w1 < 1 || h1 < 1 || abs(w1 - w) >= w || abs(h1 - h) >= h || (w1 != w && w > LQRHIP_MAX_FRAME_WIDTH) ||
+        (h1 != h && h > LQRHIP_MAX_FRAME_WIDTH)) {
+        fprintf(stderr, "liblqr-hip: lqrx_carvers_resize_static refused: %d x %d to %d x %d, delta_x %d (a change below the line length, lines of at "
+                "most %d, delta_x 0 .. %d)\n", w, h, w1, h1, delta_x, LQRHIP_MAX_FRAME_WIDTH, LQRHIP_MAX_DELTA);
+        return LQR_ERROR;
+    }
+    /* the state word is entered here too (the calls below enter it for themselves): a resize to the size the frames have skips both
+     * directions, and must still refuse a frame that is marked cancelled or inside another call */
+    LQR_CATCH(roots_enter(frames, n, LQR_STATE_RESIZING));
+    roots_leave(frames, n);
+    for (k = 0; k < 2; k++) {
+        dir = (frames[0]->resize_order == LQR_RES_ORDER_HOR) ? k : 1 - k;       /* 0: the width */
+        w = lqr_carver_get_width(frames[0]); h = lqr_carver_get_height(frames[0]);
+        if ((dir ? h1 - h : w1 - w) == 0) continue;
+        LQR_CATCH(lqrx_carvers_load_static(frames, n, abs(dir ? h1 - h : w1 - w), dir, alpha, delta_x, rigidity));
+        LQR_CATCH(lqrx_carver_resize_batch(frames, n, dir ? w : w1, dir ? h1 : h));
+    }
+    return LQR_OK;
 }
 
 /* ======================= resize (E10) ==================================== */

@@ -293,6 +293,26 @@ unsigned long long lqrhip_forward_launches(int reset);
 int lqrhip_forward_intensity(LqrHipCarver *c, int orientation, int transposed, int luma, float *out);
 /* (host/lqr_carver.c) the same for a LqrCarver, which must be flat: what tests/test_forward_gpu.py compares with the model's I */
 int lqrhip_read_forward_intensity(const void *carver, int orientation, float *out);
+/* lqr_static.h: the frames of a clip -- n FLAT root carvers of one shape and pixel kind (the host has flattened them), lying `transposed`
+ * or not -- folded into the energy plane E of static seams, width x height floats in IMAGE orientation, as seams of `orientation` see it
+ * (nrg_func: the frames' LqrEnergyFuncBuiltinType; alpha in [0, 1]).
+ *   lqrhip_static_begin    checks and allocates EVERYTHING the fold needs (the table of frame pointers, the running planes of a clip of
+ *                          more than 16 frames, and E unless device_energy names the caller's device memory): LQRHIP_ENOMEM has launched
+ *                          nothing and given every block back
+ *   lqrhip_static_groups   the launches the fold takes: one per 16 frames
+ *   lqrhip_static_fold     enqueues the next group (k_static_fold; the last one writes E); the host looks for a cancel between them
+ *   lqrhip_static_finish   waits for the fold; host_energy non-NULL: E is copied there.  0: E is complete
+ *   lqrhip_static_energy   E in device memory, valid until the release
+ *   lqrhip_static_release  waits for whatever is still queued and gives the blocks back (at any point, also instead of finish) */
+#define LQRHIP_STATIC_MAX_FRAMES 65535
+typedef struct LqrHipStatic LqrHipStatic;
+int lqrhip_static_begin(LqrHipCarver *const *cs, int n, int orientation, int transposed, int nrg_func, float alpha, void *device_energy,
+                        LqrHipStatic **out);
+int lqrhip_static_groups(const LqrHipStatic *st);
+int lqrhip_static_fold(LqrHipStatic *st);
+int lqrhip_static_finish(LqrHipStatic *st, float *host_energy);
+const float *lqrhip_static_energy(const LqrHipStatic *st);
+void lqrhip_static_release(LqrHipStatic *st);
 int lqrhip_device_sync(void);
 /* free / total device memory in bytes (hipMemGetInfo) and the bytes the shim's allocation cache holds */
 int lqrhip_mem_info(unsigned long long *free_bytes, unsigned long long *total_bytes, unsigned long long *cached_bytes);
@@ -402,6 +422,7 @@ enum {
     LQRHIP_CENSUS_LDS_ATTR_COMMIT = 28, /* k_vs_commit launches with more than 64 KB of dynamic LDS */
     LQRHIP_CENSUS_COMPACT_SIZES = 29,   /* lqrhip_read_sizes: k_compact_sizes, one launch per chunk of sizes */
     LQRHIP_CENSUS_TRANSPOSE_SIZES = 30, /*     k_transpose_sizes, likewise (a carver that lies transposed) */
+    LQRHIP_CENSUS_STATIC_FOLD = 31,     /* lqrhip_static_fold: k_static_fold, one launch per group of 16 frames (lqr_static.h) */
     LQRHIP_CENSUS_SLOTS = 32
 };
 int lqrhip_launch_census(unsigned long long *out, int n, int reset);
