@@ -350,6 +350,31 @@ def bind_static(api):
     return api
 
 
+# include_ext/lqr_clipforward.h: forward-energy seams for a clip -- one seam map from the forward costs of all frames (into device memory
+# or as a caller-owned LqrVMap), the map loaded into every frame from device memory, and the batch resize made of the two
+CLIPFORWARD_SYMBOLS = {
+    "lqrx_clip_forward_map_device": (_I, [C.POINTER(_P), _I, _I, _I, _F, _P]),
+    "lqrx_clip_forward_map": (_P, [C.POINTER(_P), _I, _I, _I, _F]),
+    "lqrx_clip_load_forward": (_I, [C.POINTER(_P), _I, _I, _I, _F]),
+    "lqrx_clip_resize_forward": (_I, [C.POINTER(_P), _I, _I, _I, _F]),
+}
+
+
+def bind_clipforward(api):
+    """add CLIPFORWARD_SYMBOLS (and what they compose: the forward hooks, seam maps, sizes) and the build's launch counter to a bound
+    Api (the engine); returns it"""
+    bind_sizes(bind_forward(api))
+    if not getattr(api, "has_clipforward", False):
+        for name, (res, args) in CLIPFORWARD_SYMBOLS.items():
+            fn = getattr(api.lib, api.prefix + name)      # AttributeError = missing export
+            fn.restype, fn.argtypes = res, args
+            setattr(api, name, fn)
+        api.lqrhip_clipfwd_launches = api.lib.lqrhip_clipfwd_launches
+        api.lqrhip_clipfwd_launches.restype, api.lqrhip_clipfwd_launches.argtypes = C.c_ulonglong, [_I]
+        api.has_clipforward = True
+    return api
+
+
 def _vmap_new(api, m):
     """a LqrVMap around a malloc'd copy of m["data"] (h x w int32, image orientation), which the map owns"""
     data = np.ascontiguousarray(m["data"], dtype=np.int32)
@@ -418,6 +443,11 @@ def engine_forward_api():
 def engine_static_api():
     """the engine with everything the static-seam calls compose bound: depths, types, masks, energies, maps, sizes, forward hooks"""
     return bind_static(bind_energy(bind_masks(bind_imagetype(bind_coldepth(engine_api())))))
+
+
+def engine_clipforward_api():
+    """the engine with everything the clip's forward calls compose bound: depths, types, masks, energies, maps, sizes, forward hooks"""
+    return bind_clipforward(bind_energy(bind_masks(bind_imagetype(bind_coldepth(engine_api())))))
 
 
 def engine_control_api():
@@ -1129,3 +1159,33 @@ def load_static(carvers, depth, orientation, alpha, delta_x=1, rigidity=0.0):
 def resize_static(carvers, w1, h1, alpha, delta_x=1, rigidity=0.0):
     a = bind_static(carvers[0].api)
     return a.lqrx_carvers_resize_static(_frames(carvers), len(carvers), int(w1), int(h1), float(alpha), int(delta_x), float(rigidity))
+
+
+def clip_forward_map(carvers, depth, orientation, temporal):
+    """lqrx_clip_forward_map: the dict vmap_dump returns, or None where the call returned NULL"""
+    a = bind_clipforward(carvers[0].api)
+    v = a.lqrx_clip_forward_map(_frames(carvers), len(carvers), int(depth), int(orientation), float(temporal))
+    if not v:
+        return None
+    d = carvers[0]._vmap_to_dict(v)
+    a.lqr_vmap_destroy(v)
+    return d
+
+
+def clip_forward_map_device(carvers, tensor, depth, orientation, temporal):
+    """lqrx_clip_forward_map_device into a contiguous h x w int32 torch tensor on the device; the LqrRetVal"""
+    a = bind_clipforward(carvers[0].api)
+    assert tensor.is_cuda and tensor.is_contiguous() and tensor.dtype == torch.int32
+    assert tensor.numel() >= a.lqr_carver_get_width(carvers[0].p) * a.lqr_carver_get_height(carvers[0].p)
+    torch.cuda.current_stream().synchronize()          # the engine writes the buffer on a stream of its own
+    return a.lqrx_clip_forward_map_device(_frames(carvers), len(carvers), int(depth), int(orientation), float(temporal), tensor.data_ptr())
+
+
+def clip_load_forward(carvers, depth, orientation, temporal):
+    a = bind_clipforward(carvers[0].api)
+    return a.lqrx_clip_load_forward(_frames(carvers), len(carvers), int(depth), int(orientation), float(temporal))
+
+
+def clip_resize_forward(carvers, w1, h1, temporal):
+    a = bind_clipforward(carvers[0].api)
+    return a.lqrx_clip_resize_forward(_frames(carvers), len(carvers), int(w1), int(h1), float(temporal))

@@ -15,6 +15,7 @@
 //   k_sizes.hip      many sizes in one pass (lqr_sizes.h) k_compact_sizes (up to 64 levels ranked from one load of a row), k_transpose_sizes (a width per job)
 //   k_forward.hip    forward-energy seam maps (include_ext/lqr_forward.h) k_fwd_init (I, P, positions from the base layouts), k_fwd_seam (sweep, pick, walk: one workgroup per image), k_fwd_remove
 //   k_static.hip     static seams for a clip (include_ext/lqr_static.h) k_static_fold (up to 16 frames a launch into the running S, T, I_prev planes; the last group mixes E)
+//   k_clipfwd.hip    forward-energy seams for a clip (include_ext/lqr_clipforward.h) k_clip_fold (the frames' costs folded once), k_clip_seam (sweep, pick, walk over the folded costs), k_clip_remove, k_clip_refresh
 //   lqr_shim.hip     the lqrhip_* C ABI of include/lqr_hip.h: allocation cache, batches, the per-seam launch sequence
 //   lqr_plan.h       which form of each stage that sequence runs (plain C++17, no HIP: also compiled alone by tests/test_plan.py)
 //   lqr_beside.h     k_carve_v's side bound, work-list entries and their readiness (plain C++17, no HIP: also compiled alone by tests/test_backtrack_beside.py)
@@ -580,6 +581,12 @@ struct FwdJob {
     int32_t *seam;          // the last seam: a column per line
     int32_t *map;           // the result, image orientation
 };
+// forward-energy seams for a clip (k_clipfwd.hip, include_ext/lqr_clipforward.h).  The fold takes CLIPFWD_GROUP frames a launch, a thread of
+// CLIPFWD_FOLD_THREADS per pixel of a line; the sweep, the walk and the removal are sized as the forward build's (FWD_*); the refresh has one
+// workgroup of CLIPFWD_REFRESH_THREADS per line, a thread taking the frames tid + k * CLIPFWD_REFRESH_THREADS
+#define CLIPFWD_GROUP 16
+#define CLIPFWD_FOLD_THREADS 256
+#define CLIPFWD_REFRESH_THREADS 256
 // static seams for a clip (k_static.hip, include_ext/lqr_static.h).  A workgroup of STATIC_THREADS folds a tile of STATIC_TILE x STATIC_TILE image pixels
 // (the size k_energy_out writes) over the STATIC_GROUP frames of a launch
 #define STATIC_TILE 64

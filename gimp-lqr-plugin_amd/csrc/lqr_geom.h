@@ -163,3 +163,17 @@ constexpr size_t sweep_lds(int w) { return (size_t) 2 * sweep_wpad(w) * sizeof(f
 // k_fwd_seam: M of two rows of L floats, row parity p at p * L
 constexpr size_t fwd_lds(int L) { return (size_t) 2 * L * sizeof(float); }
 constexpr int fwd_row_off(int parity, int L) { return parity * L; }         // (k_fwd_seam keeps its own text: its stream differs otherwise)
+
+// ---- k_clipfwd.hip: forward-energy seams for a clip -----------------------------------------------------------------------------------
+// The I planes of the n frames, H lines of L floats each, lie one after the other in one block: frame t starts at clip_frame_off(t, px),
+// px = L * H.  The costs of a pixel lie side by side, CLIP_COST_FLOATS floats from clip_cost_off(y, x, L): CU, CL, CR, then Q (while the
+// fold runs: T).  The sweep's two rows of M are k_fwd_seam's (fwd_lds, fwd_row_off).  The refresh folds CLIP_REFRESH_VALUES maxima (CU, CL,
+// CR of two columns) of each of its waves through LDS: wave v's at clip_refresh_off(v)
+constexpr int CLIP_COST_FLOATS = 4, CLIP_REFRESH_VALUES = 6;
+constexpr size_t clip_intensity_elems(int n, size_t px) { return (size_t) n * px; }
+constexpr size_t clip_frame_off(int t, size_t px) { return (size_t) t * px; }
+constexpr size_t clip_cost_elems(size_t px) { return px * CLIP_COST_FLOATS; }
+constexpr size_t clip_cost_off(int y, int x, int L) { return ((size_t) y * L + x) * CLIP_COST_FLOATS; }
+constexpr int clip_fold_groups(int n, int group) { return tiles_of(n, group); }
+constexpr int clip_refresh_off(int wave) { return wave * CLIP_REFRESH_VALUES; }
+constexpr size_t clip_refresh_lds_elems(int threads) { return (size_t) (threads / 64) * CLIP_REFRESH_VALUES; }

@@ -114,6 +114,17 @@ template <int DEPTH> __global__ __launch_bounds__(256) void k_fwd_init(const Fwd
 template <int PXT> __global__ __launch_bounds__(FWD_THREADS) void k_fwd_seam(const FwdJob *jobs, int wc, int L, int H);
 __global__ __launch_bounds__(FWD_REMOVE_THREADS) void k_fwd_remove(const FwdJob *jobs, int wc, int L, int H, int level, int orientation);
 
+// k_clipfwd.hip (forward-energy seams for a clip, include_ext/lqr_clipforward.h).  The I planes of the n frames lie one after the other in
+// `in` (frame t at clip_frame_off(t, px)); `cost` holds CU, CL, CR and Q of a pixel side by side (clip_cost_off).  X(PXT) of the seam kernel:
+// pixels per thread.  Grids: the fold a workgroup per CLIPFWD_FOLD_THREADS pixels of a line x H; the seam kernel one workgroup; the removal
+// and the refresh one workgroup per line
+#define K_CLIP_SEAM_FORMS(X) X(1) X(2) X(4) X(8) X(16)
+__global__ __launch_bounds__(CLIPFWD_FOLD_THREADS) void k_clip_fold(const FwdJob *jobs, const float *in, int first, int count, int last, int L, int H, int fw0, int strided,
+                                                                   int w_start, float temporal, float *cost, float *pm);
+template <int PXT> __global__ __launch_bounds__(FWD_THREADS) void k_clip_seam(const float *cost, int8_t *choice, int32_t *seam, int wc, int L, int H);
+__global__ __launch_bounds__(FWD_REMOVE_THREADS) void k_clip_remove(float *cost, uint16_t *pos, const int32_t *seam, int32_t *map, int wc, int L, int H, int level, int orientation);
+__global__ __launch_bounds__(CLIPFWD_REFRESH_THREADS) void k_clip_refresh(const float *in, int n, float *cost, const uint16_t *pos, const int32_t *seam, int wn, int L, int H);
+
 // k_static.hip (static seams for a clip, include_ext/lqr_static.h).  X(NRG, DEPTH, PACKED): NRG 0 / 1 / 2 / 6 (luma is DeepRead.luma, as on the value
 // plane: plane_nrg in lqr_shim.hip), DEPTH the LqrColDepth, PACKED 8-bit grey / RGB (+ alpha) through px_bright.  Grid: tiles across x tiles down
 #define K_STATIC_FOLD_FORMS(X) X(0, 0, true) X(1, 0, true) X(2, 0, true) X(6, 0, true) X(0, 0, false) X(1, 0, false) X(2, 0, false) X(6, 0, false) \

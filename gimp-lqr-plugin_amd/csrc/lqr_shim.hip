@@ -1949,7 +1949,8 @@ static FwdJob forward_job(const LqrHipCarver *c, const LqrHipForward::Planes &pl
     return FwdJob{c->rgb0, c->bias0, pl.in, pl.p, pl.pos, pl.choice, pl.seam, map};
 }
 // the one-off pass for n jobs of carvers that read like c0
-static int forward_launch_init(const LqrHipCarver *c0, const FwdJob *d_jobs, int n, int L, int H, int strided, int luma, int w_start, int orientation)
+static int forward_launch_init(const LqrHipCarver *c0, const FwdJob *d_jobs, int n, int L, int H, int strided, int luma, int w_start, int orientation,
+                               std::atomic<unsigned long long> &launches = g_forward_launches)
 {
     DeepRead rd = deep_read(c0);
     rd.luma = luma != 0;
@@ -1957,7 +1958,7 @@ static int forward_launch_init(const LqrHipCarver *c0, const FwdJob *d_jobs, int
 #define CASE(D) if (c0->depth == D) hipLaunchKernelGGL(k_fwd_init<D>, grid, dim3(256), 0, g_stream0, d_jobs, L, H, c0->w0, strided, rd, w_start, orientation); else
     K_FWD_INIT_FORMS(CASE) return no_form("k_fwd_init");
 #undef CASE
-    g_forward_launches.fetch_add(1, std::memory_order_relaxed);
+    launches.fetch_add(1, std::memory_order_relaxed);
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -2160,6 +2161,150 @@ extern "C" int lqrhip_static_finish(LqrHipStatic *st, float *host_energy)
 }
 extern "C" const float *lqrhip_static_energy(const LqrHipStatic *st) { return st ? st->e : nullptr; }
 extern "C" void lqrhip_static_release(LqrHipStatic *st) { delete st; }
+
+// ---- include_ext/lqr_clipforward.h: one forward-energy seam map from all frames of a clip (kernels in k_clipfwd.hip) -------------------------
+// A build owns, through its one Scratch, the I planes of the n frames (one block, frame after frame), the costs, Pm while the fold runs
+// (frames with a bias plane only), the positions, the choices, the seam, the map unless the caller gave one, and the job table: all taken
+// in lqrhip_clipfwd_begin before anything is launched.  It runs on g_stream0; the two events are the ends of the last two slices.
+struct __attribute__((visibility("hidden"))) LqrHipClipFwd {
+    Scratch tmp{g_stream0};
+    std::vector<FwdJob> jobs;               // (read by the copy to d_jobs)
+    FwdJob *d_jobs = nullptr;
+    float *in = nullptr, *cost = nullptr, *pm = nullptr;
+    uint16_t *pos = nullptr;
+    int8_t *choice = nullptr;
+    int32_t *seam = nullptr, *map = nullptr;
+    hipEvent_t slice_end[2] = {nullptr, nullptr};
+    hipEvent_t fold_ends[2] = {nullptr, nullptr};       // around the fold's launches (lqrhip_clipfwd_fold_ms)
+    int slices = 0, next_seam = 0;
+    int n = 0, L = 0, H = 0, depth = 0, orientation = 0, pxt = 0;
+    size_t lds = 0;
+    ~LqrHipClipFwd()
+    {
+        if (g_stream0) (void) hipStreamSynchronize(g_stream0);      // the blocks go back to the pool when tmp is destroyed
+        tmp.done();
+        for (hipEvent_t e : {slice_end[0], slice_end[1], fold_ends[0], fold_ends[1]})
+            if (e) (void) hipEventDestroy(e);
+        (void) hipGetLastError();
+    }
+};
+// (atomic, relaxed: a second thread may poll the hook while a build counts, lqr_hip.h)
+static std::atomic<unsigned long long> g_clipfwd_launches{0};
+extern "C" unsigned long long lqrhip_clipfwd_launches(int reset)
+{
+    return reset ? g_clipfwd_launches.exchange(0, std::memory_order_relaxed) : g_clipfwd_launches.load(std::memory_order_relaxed);
+}
+// the device time between the first and the last launch of the last finished build's fold, in ms (bench hook, lqr_hip.h)
+static std::atomic<double> g_clipfwd_fold_ms{0.0};
+extern "C" double lqrhip_clipfwd_fold_ms(void) { return g_clipfwd_fold_ms.load(std::memory_order_relaxed); }
+extern "C" int lqrhip_clipfwd_begin(LqrHipCarver *const *cs, int n, int depth, int orientation, int transposed, int luma, int w_start, float temporal,
+                                    void *device_map, LqrHipClipFwd **out)
+{
+    if (out) *out = nullptr;
+    if (!cs || !out || n < 1 || n > LQRHIP_FORWARD_MAX_LINES || (orientation != 0 && orientation != 1) || w_start < 1 ||
+        !(temporal >= 0.0f && temporal <= 3.402823466e38f)) {
+        g_err = "clip forward map: arguments";
+        return LQRHIP_EARG;
+    }
+    const LqrHipCarver *c0 = cs[0];
+    for (int i = 0; i < n; i++) {
+        const LqrHipCarver *c = cs[i];
+        if (!c || c->root || c->w0 != c0->w0 || c->h0 != c0->h0 || c->ch != c0->ch || c->depth != c0->depth || c->mode != c0->mode ||
+            c->alpha != c0->alpha || c->black != c0->black || !c->bias0 != !c0->bias0) {
+            g_err = "clip forward map: root carvers of one shape and pixel kind";
+            return LQRHIP_EARG;
+        }
+    }
+    const int strided = (transposed != 0) != (orientation != 0);
+    const int L = strided ? c0->h0 : c0->w0, H = strided ? c0->w0 : c0->h0;
+    if (depth < 1 || depth >= L || L > FWD_THREADS * FWD_MAX_PXT || L > LQRHIP_MAX_FRAME_WIDTH || H > LQRHIP_FORWARD_MAX_LINES) {
+        g_err = "clip forward map: 0 < depth < line length <= " + std::to_string(LQRHIP_MAX_FRAME_WIDTH) + ", at most " + std::to_string(LQRHIP_FORWARD_MAX_LINES) + " lines";
+        return LQRHIP_EARG;
+    }
+    int rc;
+    for (int i = 0; i < n; i++)
+        if ((rc = batch_sync_of(cs[i]))) return rc;     // whatever still writes the base layouts
+    std::unique_ptr<LqrHipClipFwd> f(new LqrHipClipFwd());
+    f->n = n; f->L = L; f->H = H; f->depth = depth; f->orientation = orientation;
+    f->pxt = L <= FWD_THREADS ? 1 : L <= 2 * FWD_THREADS ? 2 : L <= 4 * FWD_THREADS ? 4 : L <= 8 * FWD_THREADS ? 8 : 16;
+    f->lds = fwd_lds(L);
+    const size_t px = (size_t) L * H;
+    if (!(f->in = f->tmp.get<float>(clip_intensity_elems(n, px), "&clip_in", rc))) return rc;
+    if (!(f->cost = f->tmp.get<float>(clip_cost_elems(px), "&clip_cost", rc))) return rc;
+    if (c0->bias0 && !(f->pm = f->tmp.get<float>(px, "&clip_pm", rc))) return rc;
+    if (!(f->pos = f->tmp.get<uint16_t>(px, "&clip_pos", rc))) return rc;
+    if (!(f->choice = f->tmp.get<int8_t>(px, "&clip_choice", rc))) return rc;
+    if (!(f->seam = f->tmp.get<int32_t>((size_t) H, "&clip_seam", rc))) return rc;
+    f->map = (int32_t *) device_map;
+    if (!f->map && !(f->map = f->tmp.get<int32_t>(px, "&clip_map", rc))) return rc;
+    if (!(f->d_jobs = f->tmp.get<FwdJob>((size_t) n, "&clip_jobs", rc))) return rc;
+    // k_fwd_init's jobs: every frame its own I plane; no P plane (the fold divides the bias itself); the positions and the cleared map
+    // are the clip's, which every frame's pass writes alike
+    for (int i = 0; i < n; i++)
+        f->jobs.push_back(FwdJob{cs[i]->rgb0, cs[i]->bias0, f->in + clip_frame_off(i, px), nullptr, f->pos, nullptr, nullptr, f->map});
+    for (hipEvent_t &e : f->slice_end) HIPCK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (hipEvent_t &e : f->fold_ends) HIPCK(hipEventCreate(&e));
+    if (lds_needs_attr(f->lds)) {
+#define CASE(P) if (f->pxt == P) HIPCK(hipFuncSetAttribute((const void *) k_clip_seam<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) f->lds)); else
+        K_CLIP_SEAM_FORMS(CASE) return no_form("k_clip_seam");
+#undef CASE
+    }
+    // -- everything is allocated: the first launch
+    HIPCK(hipMemcpyAsync(f->d_jobs, f->jobs.data(), (size_t) n * sizeof(FwdJob), hipMemcpyHostToDevice, g_stream0));
+    if ((rc = forward_launch_init(c0, f->d_jobs, n, L, H, strided, luma, w_start, orientation, g_clipfwd_launches))) return rc;
+    const dim3 grid(tiles_of(L, CLIPFWD_FOLD_THREADS), H);
+    HIPCK(hipEventRecord(f->fold_ends[0], g_stream0));
+    for (int g = 0; g < clip_fold_groups(n, CLIPFWD_GROUP); g++) {
+        const int first = g * CLIPFWD_GROUP, count = std::min(CLIPFWD_GROUP, n - first);
+        hipLaunchKernelGGL(k_clip_fold, grid, dim3(CLIPFWD_FOLD_THREADS), 0, g_stream0, (const FwdJob *) f->d_jobs, (const float *) f->in, first, count,
+                           first + count == n ? 1 : 0, L, H, c0->w0, strided, w_start, temporal, f->cost, f->pm);
+        g_clipfwd_launches.fetch_add(1, std::memory_order_relaxed);
+        HIPCK(hipGetLastError());
+    }
+    HIPCK(hipEventRecord(f->fold_ends[1], g_stream0));
+    *out = f.release();
+    return 0;
+}
+extern "C" int lqrhip_clipfwd_seams(LqrHipClipFwd *f, int first_seam, int n_seams)
+{
+    if (!f || first_seam != f->next_seam || n_seams < 1 || first_seam + n_seams > f->depth) { g_err = "clip forward map: seams out of order or range"; return LQRHIP_EARG; }
+    for (int s = first_seam; s < first_seam + n_seams; s++) {
+        const int wc = f->L - s;
+#define CASE(P) if (f->pxt == P) hipLaunchKernelGGL(k_clip_seam<P>, dim3(1), dim3(FWD_THREADS), f->lds, g_stream0, (const float *) f->cost, f->choice, f->seam, wc, f->L, f->H); else
+        K_CLIP_SEAM_FORMS(CASE) return no_form("k_clip_seam");
+#undef CASE
+        hipLaunchKernelGGL(k_clip_remove, dim3((unsigned) f->H), dim3(FWD_REMOVE_THREADS), 0, g_stream0, f->cost, f->pos, (const int32_t *) f->seam, f->map, wc, f->L, f->H,
+                           s + 1, f->orientation);
+        g_clipfwd_launches.fetch_add(2, std::memory_order_relaxed);
+        if (s + 1 < f->depth) {         // (after the last seam nobody reads the costs)
+            hipLaunchKernelGGL(k_clip_refresh, dim3((unsigned) f->H), dim3(CLIPFWD_REFRESH_THREADS), 0, g_stream0, (const float *) f->in, f->n, f->cost,
+                               (const uint16_t *) f->pos, (const int32_t *) f->seam, wc - 1, f->L, f->H);
+            g_clipfwd_launches.fetch_add(1, std::memory_order_relaxed);
+        }
+        HIPCK(hipGetLastError());
+    }
+    f->next_seam = first_seam + n_seams;
+    HIPCK(hipEventRecord(f->slice_end[f->slices & 1], g_stream0));
+    if (f->slices > 0) HIPCK(hipEventSynchronize(f->slice_end[(f->slices - 1) & 1]));
+    f->slices++;
+    return 0;
+}
+extern "C" int lqrhip_clipfwd_finish(LqrHipClipFwd *f)
+{
+    if (!f || f->next_seam != f->depth) { g_err = "clip forward map: the build is not complete"; return LQRHIP_EARG; }
+    HIPCK(hipStreamSynchronize(g_stream0));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, f->fold_ends[0], f->fold_ends[1]) == hipSuccess) g_clipfwd_fold_ms.store(ms, std::memory_order_relaxed);
+    (void) hipGetLastError();
+    return check_dev_error();
+}
+extern "C" const int *lqrhip_clipfwd_map(const LqrHipClipFwd *f) { return f ? (const int *) f->map : nullptr; }
+extern "C" int lqrhip_clipfwd_read_map(LqrHipClipFwd *f, int *out)
+{
+    if (!f || !out) return LQRHIP_EARG;
+    return d2h_staged(out, f->map, (size_t) f->L * f->H * sizeof(int32_t));
+}
+extern "C" void lqrhip_clipfwd_release(LqrHipClipFwd *f) { delete f; }
 
 extern "C" int lqrhip_mask_line_max(const unsigned char *mask, int channels, int width, int height, int a0, int b0, int n_lines,
                                     int line_len, int direction)

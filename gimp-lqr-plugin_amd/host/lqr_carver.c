@@ -34,6 +34,7 @@
 #include "../../include/lqr_sizes.h"
 #include "../../include_ext/lqr_forward.h"
 #include "../../include_ext/lqr_static.h"
+#include "../../include_ext/lqr_clipforward.h"
 #include "../../include/lqr_hip.h"
 #include "lqr_mask_queue.h"
 #include "lqr_sched.h"
@@ -1436,6 +1437,150 @@ LqrRetVal lqrx_carvers_resize_static(LqrCarver **frames, gint n, gint w1, gint h
         w = lqr_carver_get_width(frames[0]); h = lqr_carver_get_height(frames[0]);
         if ((dir ? h1 - h : w1 - w) == 0) continue;
         LQR_CATCH(lqrx_carvers_load_static(frames, n, abs(dir ? h1 - h : w1 - w), dir, alpha, delta_x, rigidity));
+        LQR_CATCH(lqrx_carver_resize_batch(frames, n, dir ? w : w1, dir ? h1 : h));
+    }
+    return LQR_OK;
+}
+
+/* ======================= forward-energy seams for a clip (lqr_clipforward.h) ========== */
+/* The up-front checks and the composition: the seams are found by k_clipfwd.hip behind lqrhip_clipfwd_*, in the slices of a forward build
+ * (FWD_SLICE_SEAMS), and the map goes from the build's device memory to group_vmap_load_entered like any caller's. */
+
+/* what refuses a call before any device work.  with_map 0: the resize call, which decides depths and line lengths itself */
+static LqrRetVal clipfwd_check(LqrCarver *const *rs, int n, int with_map, int depth, int orientation, float temporal, const char *who, int *len)
+{
+    int i, L, H;
+    const char *why = NULL;
+    if (!rs) why = "NULL frames";
+    else if (n < 1 || n > LQRHIP_FORWARD_MAX_LINES) why = "1 .. 65535 frames";
+    else if (orientation != 0 && orientation != 1) why = "orientation is 0 or 1";
+    else if (!(temporal >= 0.0f && isfinite(temporal))) why = "temporal is a finite number >= 0";
+    for (i = 0; !why && i < n; i++) {
+        if (!rs[i]) why = "NULL frame";
+        else if (rs[i]->root) why = "an attached carver follows its root";
+        else if (i && !same_config(rs[0], rs[i])) why = "the frames are not of one configuration";
+    }
+    if (why) { fprintf(stderr, "liblqr-hip: %s refused: %s\n", who, why); return LQR_ERROR; }
+    if (!with_map) return LQR_OK;
+    L = orientation ? lqr_carver_get_height(rs[0]) : lqr_carver_get_width(rs[0]);
+    H = orientation ? lqr_carver_get_width(rs[0]) : lqr_carver_get_height(rs[0]);
+    if (depth < 1 || depth >= L || L > LQRHIP_MAX_FRAME_WIDTH || H > LQRHIP_FORWARD_MAX_LINES) {
+        fprintf(stderr, "liblqr-hip: %s refused: depth %d on %d lines of %d (0 < depth < line length <= %d, at most %d lines)\n", who, depth, H, L,
+                LQRHIP_MAX_FRAME_WIDTH, LQRHIP_FORWARD_MAX_LINES);
+        return LQR_ERROR;
+    }
+    *len = L;
+    return LQR_OK;
+}
+
+/* Inside the call (roots_enter): flatten what is not flat, then the build in slices, a check point in front of each.  device_map NULL:
+ * the build keeps the map.  On LQR_OK *out holds the finished build, which the caller releases; otherwise nothing is left */
+static LqrRetVal clipfwd_build_entered(LqrCarver **rs, int n, int depth, int orientation, float temporal, int L, gint *device_map, LqrHipClipFwd **out)
+{
+    LqrHipCarver **ds;
+    LqrHipClipFwd *f = NULL;
+    LqrRetVal ret;
+    int i, first;
+    *out = NULL;
+    for (i = 0; i < n; i++) LQR_CATCH(mask_queue_flush(rs[i]));
+    if (!lqr_geom_is_flat(&rs[0]->geo)) {
+        Group g;
+        LQR_CATCH(group_open(&g, rs, n));
+        ret = group_flatten(&g);
+        if (ret != LQR_OK) { int k; for (k = 0; k < g.nb; k++) lqrhip_batch_abort(g.b[k]); }
+        group_close(&g);
+        LQR_CATCH(ret);
+    }
+    if (roots_cancelled(rs, n)) return LQR_USRCANCEL;
+    ds = (LqrHipCarver **) malloc((size_t) n * sizeof *ds);
+    if (!ds) return LQR_NOMEM;
+    for (i = 0; i < n; i++) ds[i] = rs[i]->dev;
+    ret = hip_ret(lqrhip_clipfwd_begin(ds, n, depth, orientation, rs[0]->geo.transposed,
+                                       rs[0]->nrg_func >= LQR_EF_LUMA_GRAD_NORM && rs[0]->nrg_func <= LQR_EF_LUMA_GRAD_XABS, L, temporal, device_map, &f));
+    free(ds);
+    for (first = 0; ret == LQR_OK && first < depth; first += FWD_SLICE_SEAMS) {
+        if (roots_cancelled(rs, n)) ret = LQR_USRCANCEL;
+        else ret = hip_ret(lqrhip_clipfwd_seams(f, first, MINI(FWD_SLICE_SEAMS, depth - first)));
+    }
+    if (ret == LQR_OK && roots_cancelled(rs, n)) ret = LQR_USRCANCEL;
+    if (ret == LQR_OK) ret = hip_ret(lqrhip_clipfwd_finish(f));
+    if (ret != LQR_OK) { lqrhip_clipfwd_release(f); return ret; }
+    *out = f;
+    return LQR_OK;
+}
+
+LqrRetVal lqrx_clip_forward_map_device(LqrCarver **frames, gint n, gint depth, gint orientation, gfloat temporal, gint *device_map)
+{
+    LqrHipClipFwd *f;
+    LqrRetVal ret;
+    int L;
+    LQR_CATCH(clipfwd_check(frames, n, 1, depth, orientation, temporal, "lqrx_clip_forward_map_device", &L));
+    if (!device_map) { fprintf(stderr, "liblqr-hip: lqrx_clip_forward_map_device refused: NULL map\n"); return LQR_ERROR; }
+    LQR_CATCH(roots_enter(frames, n, LQR_STATE_RESIZING));
+    ret = clipfwd_build_entered(frames, n, depth, orientation, temporal, L, device_map, &f);
+    if (ret == LQR_OK) lqrhip_clipfwd_release(f);
+    roots_leave(frames, n);
+    return ret;
+}
+
+LqrVMap *lqrx_clip_forward_map(LqrCarver **frames, gint n, gint depth, gint orientation, gfloat temporal)
+{
+    LqrHipClipFwd *f;
+    LqrVMap *v = NULL;
+    gint *buffer;
+    int L, width, height;
+    if (clipfwd_check(frames, n, 1, depth, orientation, temporal, "lqrx_clip_forward_map", &L) != LQR_OK) return NULL;
+    if (roots_enter(frames, n, LQR_STATE_RESIZING) != LQR_OK) return NULL;
+    width = lqr_carver_get_width(frames[0]); height = lqr_carver_get_height(frames[0]);
+    buffer = (gint *) malloc((size_t) width * height * sizeof *buffer);
+    if (buffer && clipfwd_build_entered(frames, n, depth, orientation, temporal, L, NULL, &f) == LQR_OK) {
+        if (hip_ret(lqrhip_clipfwd_read_map(f, buffer)) == LQR_OK) v = lqr_vmap_new(buffer, width, height, depth, orientation);
+        lqrhip_clipfwd_release(f);
+    }
+    if (!v) free(buffer);
+    roots_leave(frames, n);
+    return v;
+}
+
+LqrRetVal lqrx_clip_load_forward(LqrCarver **frames, gint n, gint depth, gint orientation, gfloat temporal)
+{
+    LqrHipClipFwd *f;
+    LqrRetVal ret;
+    int L;
+    LQR_CATCH(clipfwd_check(frames, n, 1, depth, orientation, temporal, "lqrx_clip_load_forward", &L));
+    LQR_CATCH(roots_enter(frames, n, LQR_STATE_RESIZING));
+    ret = clipfwd_build_entered(frames, n, depth, orientation, temporal, L, NULL, &f);
+    if (ret == LQR_OK) {
+        /* (the map lies in the build's device memory until the load has committed: no trip through the host) */
+        ret = group_vmap_load_entered(frames, n, lqrhip_clipfwd_map(f), 1, lqr_carver_get_width(frames[0]), lqr_carver_get_height(frames[0]), depth, orientation);
+        lqrhip_clipfwd_release(f);
+    }
+    roots_leave(frames, n);
+    return ret;
+}
+
+LqrRetVal lqrx_clip_resize_forward(LqrCarver **frames, gint n, gint w1, gint h1, gfloat temporal)
+{
+    int w, h, dir, k;
+    LQR_CATCH(clipfwd_check(frames, n, 0, 0, 0, temporal, "lqrx_clip_resize_forward", &k));
+    w = lqr_carver_get_width(frames[0]); h = lqr_carver_get_height(frames[0]);
+    /* both directions are decided before either changes anything: no line has |change| seams, no frame is wider than the engine's, and
+     * the second direction's lines are as many as the first leaves (max(., .) covers both orders) */
+    if (w1 < 1 || h1 < 1 || abs(w1 - w) >= w || abs(h1 - h) >= h || (w1 != w && w > LQRHIP_MAX_FRAME_WIDTH) || (h1 != h && h > LQRHIP_MAX_FRAME_WIDTH) ||
+        (w1 != w && MAXI(h, h1) > LQRHIP_FORWARD_MAX_LINES) || (h1 != h && MAXI(w, w1) > LQRHIP_FORWARD_MAX_LINES)) {
+        fprintf(stderr, "liblqr-hip: lqrx_clip_resize_forward refused: %d x %d to %d x %d (a change below the line length, lines of at most %d, "
+                "at most %d of them)\n", w, h, w1, h1, LQRHIP_MAX_FRAME_WIDTH, LQRHIP_FORWARD_MAX_LINES);
+        return LQR_ERROR;
+    }
+    /* the state word is entered here too (the calls below enter it for themselves): a resize to the size the frames have skips both
+     * directions, and must still refuse a frame that is marked cancelled or inside another call */
+    LQR_CATCH(roots_enter(frames, n, LQR_STATE_RESIZING));
+    roots_leave(frames, n);
+    for (k = 0; k < 2; k++) {
+        dir = (frames[0]->resize_order == LQR_RES_ORDER_HOR) ? k : 1 - k;       /* 0: the width */
+        w = lqr_carver_get_width(frames[0]); h = lqr_carver_get_height(frames[0]);
+        if ((dir ? h1 - h : w1 - w) == 0) continue;
+        LQR_CATCH(lqrx_clip_load_forward(frames, n, abs(dir ? h1 - h : w1 - w), dir, temporal));
         LQR_CATCH(lqrx_carver_resize_batch(frames, n, dir ? w : w1, dir ? h1 : h));
     }
     return LQR_OK;

@@ -313,6 +313,30 @@ int lqrhip_static_fold(LqrHipStatic *st);
 int lqrhip_static_finish(LqrHipStatic *st, float *host_energy);
 const float *lqrhip_static_energy(const LqrHipStatic *st);
 void lqrhip_static_release(LqrHipStatic *st);
+/* lqr_clipforward.h: ONE forward-energy seam map from all n frames of a clip -- FLAT root carvers of one shape and pixel kind (the host has
+ * flattened them), lying `transposed` or not -- `depth` seams in the direction `orientation`.  luma, w_start: as lqrhip_forward_begin's;
+ * temporal: a finite float >= 0.  device_map: the caller's device memory, width x height ints in image orientation -- or NULL, and the
+ * build keeps a map of its own (lqrhip_clipfwd_map, lqrhip_clipfwd_read_map).  The family mirrors lqrhip_forward_*:
+ *   lqrhip_clipfwd_begin    checks, allocates EVERYTHING the build needs and enqueues the one-off passes (k_fwd_init for the I planes, one
+ *                           k_clip_fold per 16 frames): LQRHIP_ENOMEM has launched nothing and given every block back
+ *   lqrhip_clipfwd_seams    enqueues seams first_seam .. first_seam + n_seams - 1 (0-based, in order, every one once): at most three
+ *                           launches per seam whatever n is.  Returns once the slice BEFORE this one has completed
+ *   lqrhip_clipfwd_finish   waits for the build; 0: the map is complete
+ *   lqrhip_clipfwd_release  waits for whatever is still queued and gives the build's blocks back (at any point, also instead of finish)
+ * The build runs on the shim's own stream; it reads the carvers' base layouts and changes nothing of theirs.  Lines and frames: at most
+ * LQRHIP_FORWARD_MAX_LINES each.  lqrhip_clipfwd_launches: kernel launches of clip builds so far (test hook; atomic, MAY BE POLLED FROM
+ * ANOTHER THREAD while a build runs).  They are not counted by lqrhip_forward_launches or the launch census. */
+typedef struct LqrHipClipFwd LqrHipClipFwd;
+int lqrhip_clipfwd_begin(LqrHipCarver *const *cs, int n, int depth, int orientation, int transposed, int luma, int w_start, float temporal,
+                         void *device_map, LqrHipClipFwd **out);
+int lqrhip_clipfwd_seams(LqrHipClipFwd *f, int first_seam, int n_seams);
+int lqrhip_clipfwd_finish(LqrHipClipFwd *f);
+const int *lqrhip_clipfwd_map(const LqrHipClipFwd *f);             /* the map, device memory (after finish) */
+int lqrhip_clipfwd_read_map(LqrHipClipFwd *f, int *out);          /* ... copied to host memory */
+void lqrhip_clipfwd_release(LqrHipClipFwd *f);
+unsigned long long lqrhip_clipfwd_launches(int reset);
+/* bench hook: the device time the fold of the last FINISHED build took (k_clip_fold's launches, first to last), in ms */
+double lqrhip_clipfwd_fold_ms(void);
 int lqrhip_device_sync(void);
 /* free / total device memory in bytes (hipMemGetInfo) and the bytes the shim's allocation cache holds */
 int lqrhip_mem_info(unsigned long long *free_bytes, unsigned long long *total_bytes, unsigned long long *cached_bytes);
