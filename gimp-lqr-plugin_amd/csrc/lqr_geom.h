@@ -89,6 +89,11 @@ constexpr int lv_epoch(int launches) { return 1 + (launches % ((1 << LV_EPOCH_BI
 struct LvBlock { int image, slot; };
 constexpr unsigned lv_grid(size_t n, int P) { return (unsigned) (8 * ((n + 7) / 8) * P); }
 constexpr LvBlock lv_block(int b, int P) { return LvBlock{((b >> 3) / P) * 8 + (b & 7), (b >> 3) % P}; }
+// k_band_levels2 (k_levels2.hip): a workgroup is two slots of one image, s and s + ceil(P / 2) (the second is missing in the last workgroup
+// of an odd P); an image's ceil(P / 2) workgroups share b mod 8 as above.  lv2_block gives the image and the FIRST slot
+constexpr int lv2_pairs(int P) { return (P + 1) / 2; }
+constexpr unsigned lv2_grid(size_t n, int P) { return (unsigned) (8 * ((n + 7) / 8) * lv2_pairs(P)); }
+constexpr LvBlock lv2_block(int b, int P) { return LvBlock{((b >> 3) / lv2_pairs(P)) * 8 + (b & 7), (b >> 3) % lv2_pairs(P)}; }
 
 // ---- k_carve_e / k_carve_u / k_carve_v (k_carve.hip), k_emap_update: grids ------------------------------------------------------
 // k_carve_u: one dimension, the energy role's n * bb_energy_entries(h) workgroups first (image by image), then the carve role's

@@ -84,6 +84,13 @@ __global__ __launch_bounds__(64 * DPP_W) void k_dp_tile_p(DevCarver *cs, DpK p, 
 template <bool LR, bool RIG, int DELTA, bool RIGM>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_band_levels(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long long *exch, int epoch, int *dev_err, int P, int n_img);
 
+// k_levels2.hip: two slots of an image per workgroup.  X(LR, RIG): delta_x 1, no rigidity mask; one residency class of its own
+#define K_BAND_LEVELS2_FORMS(X) X(false, false) X(false, true) X(true, false) X(true, true)
+template <bool LR, bool RIG>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_band_levels2(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long long *exch, int epoch, int *dev_err, int P, int n_img);
+void lqr_levels2_debug(int v);                                  // lqrhip_band_levels_debug's switches for this family's device global
+int lqr_levels2_stats(unsigned long long *out, int reset);      // adds this family's event counters to out[0 .. 8)
+
 // k_oneoff.hip
 __global__ __launch_bounds__(256) void k_vs_commit(const DevCarver *cs, int w0, int h0, int wc0, int n_seams, int first_level, int finish);
 template <bool DEEP> __global__ __launch_bounds__(256) void k_inflate(const InflateDev *jobs, int w0, int w1, int l, int max_level, int *dev_err);

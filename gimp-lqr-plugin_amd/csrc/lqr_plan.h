@@ -53,6 +53,7 @@ struct PlanKnobs {
     int backtrack_beside = -1;      // k_carve_v (the backtrack as a role of the carve's launch too): -1 automatic (plan_backtrack_beside); 0 never; 1 wherever a form exists
     int update_mode = -1;           // lqrhip_set_update_mode
     int band_levels = -1;           // k_band_levels: -1 automatic; 0 never; n: n slots per image
+    int levels_wg_slots = -1;       // slots per workgroup of the level kernel: -1 automatic (plan_levels_wg_slots); 1: one (k_band_levels); 2: two (k_band_levels2) wherever a form exists
     int dpp_limit = -1;             // -1: the occupancy-derived bounds; >= 0: at most that many workgroups for a spinning grid
     int dpp_px = 0;                 // 2, 3 or 4 pins the persistent sweep's geometry code (0 = by batch size)
     int sub_batches = 0;            // streams of a group; 0: automatic (plan_streams)
@@ -64,6 +65,7 @@ struct PlanKnobs {
 // and the HIP runtime's GPU_MAX_HW_QUEUES (0: not set)
 struct PlanDevice {
     int wgs_plain = 0, wgs_general = 0, wgs_px4 = 0, wgs_levels = 0;
+    int wgs_levels2 = 0;            // k_band_levels2's 256-thread workgroups
     int n_cu = 0, hw_queues = 0;
 };
 // What a batch is
@@ -100,6 +102,7 @@ struct StepPlan {
     bool full = false;              // dp is a full DP (after a side switch), not an update
     int band = -1;                  // LQRHIP_CENSUS_BAND_* in front of dp (a _SWEEP_UPDATE then); -1: dp alone (the tiled update, a full DP)
     int levels_P = 0;               // k_band_levels: slots per image
+    int levels_wg_slots = 1;        // ... and per workgroup: 2 is k_band_levels2 (counted under _BAND_LEVELS too)
     DpPlan dp;                      // form -1: nothing is left to update (liblqr's finish_vsmap case)
 };
 
@@ -213,6 +216,25 @@ static inline int plan_levels_P(const PlanKnobs &k, const PlanDevice &d, const P
     const int P = std::min({LV_PMAX, per_batch / std::max(b.images, 1), want});
     return P >= (k.band_levels > 0 ? 1 : LV_AUTO_MIN) ? P : 0;
 }
+// Slots per workgroup of the level kernel, given its P slots per image: 2 is k_band_levels2 (k_levels2.hip), whose workgroup holds the
+// slots s and s + ceil(P / 2) of one image on four waves.  A form exists at delta_x 1 without a rigidity mask that matters, for P >= 2,
+// where spinning kernels are allowed (plan_levels_P gives no P otherwise) and the grid fits the family's own residency bound; the
+// knob at 2 takes it wherever it exists.  Automatic: a batch that has its stream to itself whose one-slot grid would put two workgroups
+// on some compute unit (group x P > n_cu); the two-slot grid is then at most one workgroup per unit.
+// Measured on one stream (profiles/levels_pair/README.md; 4K, 200 seams, parent / new): the level kernel 381.3 -> 368.7 us per launch at
+// 64 images; three alternating runs of 20 steps: 179.55 179.05 179.31 -> 177.39 177.04 177.22 ms per step (+1.2 %, the parent's spread
+// 0.5 ms).  Mseams*px/s in the order parent, new, new, parent: 8 images 178.0 k 178.7 k 178.4 k 179.0 k and 16: 322.0 321.7 320.5 321.2
+// (96 and 192 one-slot workgroups: the rule leaves them on k_band_levels, nothing moves), 32: 429.2 454.2 456.1 427.2 (384 -> 192
+// workgroups, +6.3 %), 48: 512.1 535.2 543.1 522.7 (480 -> 240, +2.4 .. 6.1 %).  Every size that takes the form gains, so the threshold
+// stays the reasoned one; 22 .. 31 images (12 slots: 264 .. 372 one-slot workgroups) were not run.  Sub-batches on sibling streams keep
+// the one-slot kernel: round 6 measured two slots per workgroup at -18 % under the sibling streams' carves.
+static inline int plan_levels_wg_slots(const PlanKnobs &k, const PlanDevice &d, const PlanBatch &b, int delta, bool general, int P)
+{
+    if (k.levels_wg_slots == 1 || !b.spin || delta != 1 || general || P < 2) return 1;
+    if ((size_t) lv2_grid((size_t) b.images, P) > (size_t) (plan_limit(k, d.wgs_levels2) / std::max(b.shared_n, 1))) return 1;
+    if (k.levels_wg_slots == 2) return 2;
+    return !b.shared && b.group() * (size_t) P > (size_t) d.n_cu ? 2 : 1;
+}
 // How many images of frame width `w` (the direction being carved) one lock-step batch may hold and still run delta_x != 1 /
 // rigidity-mask carvers on the tiled kernels (k_dp_tile_p's general instantiations: one workgroup per 64 columns per image, all
 // co-resident).  Beyond it such a batch would fall to the one-wave-per-image band kernel (~30x slower), so the host carves larger
@@ -310,7 +332,7 @@ static inline StepPlan plan_seam_step(const PlanKnobs &k, const PlanDevice &d, c
                        plan_persistent_px(k, d, b, w, general, delta, b.images) != 0;
     // the level kernel is asked first: a positive P wins over the tiled update
     if (fast_delta && mode != 3 && (mode == 5 || levels_auto(k, delta, b.group(), plain))) s.levels_P = plan_levels_P(k, d, b, wnew, h, delta);
-    if (s.levels_P > 0) s.band = LQRHIP_CENSUS_BAND_LEVELS;
+    if (s.levels_P > 0) { s.band = LQRHIP_CENSUS_BAND_LEVELS; s.levels_wg_slots = plan_levels_wg_slots(k, d, b, delta, general, s.levels_P); }
     else if (tiled) {
         s.dp = plan_persistent(plan_persistent_px(k, d, b, wnew, general, delta, b.images), general, b.images);
         return s;

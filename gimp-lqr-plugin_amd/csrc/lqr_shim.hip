@@ -188,8 +188,8 @@ static void dpp_resident_workgroups(int dev)
 {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount <= 0) return;
-    enum { PX4, PLAIN, GENERAL, LEVELS, N_CLASSES };
-    int per_cu[N_CLASSES] = {1 << 20, 1 << 20, 1 << 20, 1 << 20};
+    enum { PX4, PLAIN, GENERAL, LEVELS, LEVELS2, N_CLASSES };
+    int per_cu[N_CLASSES] = {1 << 20, 1 << 20, 1 << 20, 1 << 20, 1 << 20};
     auto q = [&](int cls, auto kern, int threads) {
         int n = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, threads, 0) != hipSuccess) { (void) hipGetLastError(); n = 0; }
@@ -201,6 +201,9 @@ static void dpp_resident_workgroups(int dev)
 #define QUERY(...) q(LEVELS, k_band_levels<__VA_ARGS__>, 128);
     K_BAND_LEVELS_FORMS(QUERY)
 #undef QUERY
+#define QUERY(...) q(LEVELS2, k_band_levels2<__VA_ARGS__>, 256);
+    K_BAND_LEVELS2_FORMS(QUERY)
+#undef QUERY
     auto bound = [&](int blocks) { return std::max(0, blocks - 1) * prop.multiProcessorCount; };
     g_dev.n_cu = prop.multiProcessorCount;
     // the plain 2-px instantiations stage a whole 32-row block (193 VGPRs): their bound is lower, and a grid that is too large for
@@ -209,6 +212,7 @@ static void dpp_resident_workgroups(int dev)
     g_dev.wgs_plain = bound(std::min(per_cu[PX4], per_cu[PLAIN]));
     g_dev.wgs_general = bound(per_cu[GENERAL]);
     g_dev.wgs_levels = bound(per_cu[LEVELS]);
+    g_dev.wgs_levels2 = bound(per_cu[LEVELS2]);
 }
 
 // Large lock-step groups are carved on 4 streams, and those need hardware queues of their own: the HIP runtime's
@@ -1104,6 +1108,9 @@ extern "C" void lqrhip_set_dp_persistent_px(int px) { g_knobs.dpp_px = (px == 2 
 // (0 sends every full DP to k_dp_tile and every incremental update to a band kernel)
 extern "C" void lqrhip_set_dp_persistent_limit(int workgroups) { g_knobs.dpp_limit = workgroups; }
 extern "C" void lqrhip_set_band_levels(int slots) { g_knobs.band_levels = slots; }
+extern "C" void lqrhip_set_levels_wg_slots(int slots) { g_knobs.levels_wg_slots = slots == 1 || slots == 2 ? slots : -1; }
+static unsigned long long g_levels_pair_launches = 0;
+extern "C" unsigned long long lqrhip_levels_pair_launches(int reset) { const unsigned long long n = g_levels_pair_launches; if (reset) g_levels_pair_launches = 0; return n; }
 static PlanBatch plan_batch(const LqrHipBatch *b)
 {
     PlanBatch pb;
@@ -1297,7 +1304,7 @@ static int pay_catchup(LqrHipBatch *b)
     return 0;
 }
 
-static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr, int P, bool rigm)
+static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr, int P, int wg_slots, bool rigm)
 {
     LqrHipCarver *c0 = b->cs[0];
     const size_t n = b->cs.size();
@@ -1307,6 +1314,16 @@ static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr
     const dim3 grid(lv_grid(n, P));
     CENSUS(LQRHIP_CENSUS_BAND_LEVELS);
     const DpForm f = dp_form(k, lr, rigm);
+    if (wg_slots == 2) {            // two slots per workgroup (plan_levels_wg_slots: delta_x 1, no mask)
+        const dim3 grid2(lv2_grid(n, P));
+#define CASE(LR, RIG) if (f.lr == LR && f.rig == RIG && f.delta == 1 && !f.rigm) \
+        hipLaunchKernelGGL((k_band_levels2<LR, RIG>), grid2, dim3(256), 0, b->stream, b->d_desc, k, w, h, c0->stride, b->exch.get(), epoch, g_dev_err, P, (int) n); else
+        K_BAND_LEVELS2_FORMS(CASE) return no_form("k_band_levels2");
+#undef CASE
+        HIPCK(hipGetLastError());
+        g_levels_pair_launches++;
+        return 0;
+    }
 #define CASE(LR, RIG, DELTA, RIGM) if (f.lr == LR && f.rig == RIG && f.delta == DELTA && f.rigm == RIGM) \
         hipLaunchKernelGGL((k_band_levels<LR, RIG, DELTA, RIGM>), grid, dim3(128), 0, b->stream, b->d_desc, k, w, h, c0->stride, b->exch.get(), epoch, g_dev_err, P, (int) n); else
     K_BAND_LEVELS_FORMS(CASE) return no_form("k_band_levels");
@@ -1447,7 +1464,7 @@ static int launch_band(LqrHipBatch *b, const StepPlan &s, const StepVals &v)
     const DpK &k = v.k;
     if (s.band == LQRHIP_CENSUS_BAND_LEVELS) {
         ProfScope ps("band_levels", b->stream, 0);
-        if (int rc = launch_band_levels(b, k, wnew, h, leftright_next, s.levels_P, v.rigm)) return rc;
+        if (int rc = launch_band_levels(b, k, wnew, h, leftright_next, s.levels_P, s.levels_wg_slots, v.rigm)) return rc;
     } else if (s.band == LQRHIP_CENSUS_BAND_TW) {
         ProfScope ps("band_update", b->stream, 0);
         CENSUS(LQRHIP_CENSUS_BAND_TW);

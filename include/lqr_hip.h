@@ -415,6 +415,11 @@ int lqrhip_prof_get_union(const char *kernel, double *ms_union);
 int lqrhip_moved_bytes(unsigned long long *bytes, int reset);
 /* Test hook: slots (workgroups) per image of k_band_levels (-1 automatic, 0 never, n exactly n). */
 void lqrhip_set_band_levels(int slots);
+/* Test hook: slots per WORKGROUP of the level kernel: -1 automatic, 1 never two (k_band_levels), 2 two (k_band_levels2) wherever a form
+ * exists (delta_x 1, no rigidity mask that matters, at least 2 slots per image) and its grid is resident. */
+void lqrhip_set_levels_wg_slots(int slots);
+/* launches of k_band_levels2 since the last reset (they are counted under LQRHIP_CENSUS_BAND_LEVELS as well) */
+unsigned long long lqrhip_levels_pair_launches(int reset);
 /* k_band_levels' events since the last reset: [0] images stopped by THREE active tiles on one slot (a slot takes two, one per
  * wave; the full-width sweep took over), [1] synchronous (mispredicted or second-tile) loads, [2] tile-levels processed,
  * [3] slot-levels idle, [4] levels in which a slot had two tiles */
