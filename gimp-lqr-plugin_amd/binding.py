@@ -375,6 +375,31 @@ def bind_clipforward(api):
     return api
 
 
+# include_ext/lqr_remove.h: object removal -- the scan of the discard mask (which marked pixels are visible, the most in one line) and the
+# resize that carves until none is left.  The engine's own, as the forward calls are
+LQRX_REMOVE_MIN_STEP = 16
+LQRX_ORIENTATION_AUTO = -1
+REMOVE_SYMBOLS = {
+    "lqrx_carver_discard_scan": (_I, [_P, _I, _F, C.POINTER(_I), C.POINTER(_I)]),
+    "lqrx_carver_remove_discarded": (_I, [_P, _I, _F, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+}
+
+
+def bind_remove(api):
+    """add REMOVE_SYMBOLS (and the masks' surface, whose planes they read) and the scan's launch counter to a bound Api (the engine);
+    returns it"""
+    bind_masks(api)
+    if not getattr(api, "has_remove", False):
+        for name, (res, args) in REMOVE_SYMBOLS.items():
+            fn = getattr(api.lib, api.prefix + name)      # AttributeError = missing export
+            fn.restype, fn.argtypes = res, args
+            setattr(api, name, fn)
+        api.lqrhip_discard_launches = api.lib.lqrhip_discard_launches
+        api.lqrhip_discard_launches.restype, api.lqrhip_discard_launches.argtypes = None, [C.POINTER(C.c_ulonglong), _I]
+        api.has_remove = True
+    return api
+
+
 def _vmap_new(api, m):
     """a LqrVMap around a malloc'd copy of m["data"] (h x w int32, image orientation), which the map owns"""
     data = np.ascontiguousarray(m["data"], dtype=np.int32)
@@ -448,6 +473,11 @@ def engine_static_api():
 def engine_clipforward_api():
     """the engine with everything the clip's forward calls compose bound: depths, types, masks, energies, maps, sizes, forward hooks"""
     return bind_clipforward(bind_energy(bind_masks(bind_imagetype(bind_coldepth(engine_api())))))
+
+
+def engine_remove_api():
+    """the engine with everything a removal composes bound: depths, types, masks, seam maps, sizes, control, the two calls"""
+    return bind_remove(bind_control(bind_sizes(bind_vmap(bind_imagetype(bind_coldepth(engine_api()))))))
 
 
 def engine_control_api():
@@ -985,6 +1015,21 @@ class Carver:
         ret = a.lqrhip_read_forward_intensity(self.p, int(orientation), out.ctypes.data)
         assert ret == 0, ret
         return out
+
+    # -- object removal (include_ext/lqr_remove.h)
+    def discard_scan(self, orientation, strength=0.0):
+        """lqrx_carver_discard_scan: (LqrRetVal, marked, need)"""
+        marked, need = C.c_int(-1), C.c_int(-1)
+        ret = bind_remove(self.api).lqrx_carver_discard_scan(self.p, int(orientation), float(strength), C.byref(marked), C.byref(need))
+        return ret, marked.value, need.value
+
+    def remove_discarded(self, orientation, strength=0.0, max_seams=1 << 20, restore=False):
+        """lqrx_carver_remove_discarded: dict(ret, orientation_used, seams, left); the three are None where the call did not write them"""
+        o, seams, left = C.c_int(-9), C.c_int(-9), C.c_int(-9)
+        ret = bind_remove(self.api).lqrx_carver_remove_discarded(self.p, int(orientation), float(strength), int(max_seams), int(bool(restore)),
+                                                                 C.byref(o), C.byref(seams), C.byref(left))
+        val = lambda v: None if v.value == -9 else v.value
+        return dict(ret=ret, orientation_used=val(o), seams=val(seams), left=val(left))
 
     # -- many sizes in one pass (include/lqr_sizes.h)
     def size_range(self):

@@ -17,6 +17,7 @@
 //   k_forward.hip    forward-energy seam maps (include_ext/lqr_forward.h) k_fwd_init (I, P, positions from the base layouts), k_fwd_seam (sweep, pick, walk: one workgroup per image), k_fwd_remove
 //   k_static.hip     static seams for a clip (include_ext/lqr_static.h) k_static_fold (up to 16 frames a launch into the running S, T, I_prev planes; the last group mixes E)
 //   k_clipfwd.hip    forward-energy seams for a clip (include_ext/lqr_clipforward.h) k_clip_fold (the frames' costs folded once), k_clip_seam (sweep, pick, walk over the folded costs), k_clip_remove, k_clip_refresh
+//   k_discard.hip    the discard scan (include_ext/lqr_remove.h) k_discard_line (marked pixels still visible, a workgroup per base-layout row), k_discard_cross / k_discard_rank + k_discard_fold (lines across the rows)
 //   lqr_shim.hip     the lqrhip_* C ABI of include/lqr_hip.h: allocation cache, batches, the per-seam launch sequence
 //   lqr_plan.h       which form of each stage that sequence runs (plain C++17, no HIP: also compiled alone by tests/test_plan.py)
 //   lqr_beside.h     k_carve_v's side bound, work-list entries and their readiness (plain C++17, no HIP: also compiled alone by tests/test_backtrack_beside.py)

@@ -182,3 +182,23 @@ constexpr size_t clip_cost_off(int y, int x, int L) { return ((size_t) y * L + x
 constexpr int clip_fold_groups(int n, int group) { return tiles_of(n, group); }
 constexpr int clip_refresh_off(int wave) { return wave * CLIP_REFRESH_VALUES; }
 constexpr size_t clip_refresh_lds_elems(int threads) { return (size_t) (threads / 64) * CLIP_REFRESH_VALUES; }
+
+// ---- k_discard.hip: the discard scan (include_ext/lqr_remove.h) ------------------------------------------------------------------------
+// The result block: DISCARD_WORDS ints per scan -- marked pixels that are visible, the most of them in one line, the deepest level of a
+// marked pixel, one word unused (a scan's result is 16 bytes) -- the line scan's at discard_result_off(0), the cross scan's at (1).
+// The line scan: a workgroup per base-layout row, DISCARD_CHUNK columns at a time, four neighbouring columns per lane; the chunks of row y
+// start discard_lead(y, w0) columns in front of the row, so that a lane's four lie on a 16-byte boundary of the planes.
+// The cross scan: a workgroup takes DISCARD_ROWS base-layout rows of DISCARD_THREADS neighbouring columns, a column per lane, and leaves
+// every column's count at discard_partial_off(tile, x, w0); k_discard_fold, a lane per column, sums the tiles' counts.  That holds while
+// every pixel of the base layout is visible (level 1: a column of the layout is a column of the image).  Otherwise the ranked scan: a
+// workgroup per row, DISCARD_THREADS columns at a time, adds a marked pixel to the count of the image column it is shown in -- its rank
+// among the row's visible pixels -- in a block of discard_rank_elems(w) counts, w the visible width; the fold reads it as one tile.
+constexpr int DISCARD_THREADS = 256, DISCARD_CHUNK = 4 * DISCARD_THREADS, DISCARD_ROWS = 32, DISCARD_WORDS = 4;
+constexpr int discard_result_off(int cross) { return cross * DISCARD_WORDS; }
+constexpr size_t discard_result_elems() { return 2 * DISCARD_WORDS; }
+constexpr int discard_lead(size_t y, int w0) { return (int) ((y * (size_t) w0) & 3); }
+constexpr int discard_col_blocks(int w0) { return tiles_of(w0, DISCARD_THREADS); }
+constexpr int discard_row_tiles(int h0) { return tiles_of(h0, DISCARD_ROWS); }
+constexpr size_t discard_partial_elems(int w0, int h0) { return (size_t) discard_row_tiles(h0) * w0; }
+constexpr size_t discard_partial_off(int tile, int x, int w0) { return (size_t) tile * w0 + x; }
+constexpr size_t discard_rank_elems(int w) { return (size_t) w; }

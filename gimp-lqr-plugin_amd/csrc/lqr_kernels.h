@@ -141,6 +141,15 @@ template <int NRG, int DEPTH, bool PACKED>
 __global__ __launch_bounds__(STATIC_THREADS) void k_static_fold(const StaticFrame *frames, int count, int first, int W, int H, int transposed, int orientation, DeepRead rd,
                                                      float alpha, float *s_plane, float *t_plane, float *i_plane, float *e_out);
 
+// k_discard.hip (the discard scan, include_ext/lqr_remove.h).  One form each.  Grids (lqr_geom.h): the line scan a workgroup per base-layout
+// row, the ranked scan too; the cross scan discard_col_blocks(w0) x discard_row_tiles(h0); the fold discard_col_blocks(columns).  res: a scan's DISCARD_WORDS result words
+__global__ __launch_bounds__(DISCARD_THREADS) void k_discard_line(const float *bias, const int32_t *vs, int w0, float thr, int level, int depth, int *res);
+__global__ __launch_bounds__(DISCARD_THREADS) void k_discard_cross(const float *bias, const int32_t *vs, int w0, int h0, float thr, int level, int depth,
+                                                                 int *partial, int *res);
+__global__ __launch_bounds__(DISCARD_THREADS) void k_discard_rank(const float *bias, const int32_t *vs, int w0, int w, float thr, int level, int depth, int *col,
+                                                                int *res);
+__global__ __launch_bounds__(DISCARD_THREADS) void k_discard_fold(const int *partial, int w0, int tiles, int *res);
+
 // k_masks.hip (computed masks, include/lqr_masks.h: T = float or double)
 template <class T> __global__ __launch_bounds__(256) void k_mask_add_f(float *plane, int w0, const T *mask, int mw, int x0, int y0, int x1, int y1, int nx, int ny,
                                                                        int transposed, int is_rig, int bias_factor);

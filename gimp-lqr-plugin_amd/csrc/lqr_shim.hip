@@ -1928,6 +1928,74 @@ extern "C" int lqrhip_read_sizes(LqrHipCarver *c, int w0, int h0, int transposed
     return 0;
 }
 
+// ---- include_ext/lqr_remove.h: the discard scan (kernels in k_discard.hip) ------------------------------------------------------------------
+// One Scratch owns the result block and the cross scan's counts; both are taken before anything is launched.  The result words are
+// zeroed on the stream in front of the kernels, which fold into them with integer atomics, and reach the host through the staged read.
+static unsigned long long g_discard_launches[4];       // k_discard_line, k_discard_cross, k_discard_rank, k_discard_fold
+extern "C" void lqrhip_discard_launches(unsigned long long out4[4], int reset)
+{
+    if (out4) memcpy(out4, g_discard_launches, sizeof g_discard_launches);
+    if (reset) memset(g_discard_launches, 0, sizeof g_discard_launches);
+}
+extern "C" int lqrhip_discard_scan(LqrHipCarver *c, int w0, int h0, int w, int level, int depth, float strength, int which, int *out)
+{
+    if (!c || c->root || !out || w0 < 1 || h0 < 1 || w < 1 || w > w0 || level < 1 || depth < 0 || !(which & 3) || !(strength >= 0.0f) || c->w0 != w0 || c->h0 != h0) {
+        g_err = "discard scan: a root carver in its own base layout, a level, a strength >= 0 and a scan to run";
+        return LQRHIP_EARG;
+    }
+    int rc = batch_sync_of(c);
+    if (rc) return rc;
+    const bool line = which & LQRHIP_DISCARD_LINE, cross = which & LQRHIP_DISCARD_CROSS;
+    memset(out, 0, discard_result_elems() * sizeof(int));
+    if (!c->bias0) return 0;            // no plane: nothing is marked
+    Scratch tmp(g_stream0);
+    int *res = tmp.get<int>(discard_result_elems(), "&res", rc);
+    if (rc) return rc;
+    // the lines across the rows: a column of the layout is a column of the image only while nothing is hidden (level 1)
+    const bool ranked = cross && level > 1;
+    int *partial = nullptr;
+    if (cross) {
+        partial = tmp.get<int>(ranked ? discard_rank_elems(w) : discard_partial_elems(w0, h0), "&partial", rc);
+        if (rc) return rc;
+    }
+    HIPCK(hipMemsetAsync(res, 0, discard_result_elems() * sizeof(int), g_stream0));
+    if (ranked) HIPCK(hipMemsetAsync(partial, 0, discard_rank_elems(w) * sizeof(int), g_stream0));
+    const float thr = -strength;
+    const double plane_bytes = 8.0 * w0 * h0;         // bias0 and vs, once (lqrhip_prof_get: "discard_line", "discard_cross")
+    if (line) {
+        ProfScope ps("discard_line", g_stream0, plane_bytes);
+        hipLaunchKernelGGL(k_discard_line, dim3(h0), dim3(DISCARD_THREADS), 0, g_stream0, (const float *) c->bias0.get(), (const int32_t *) c->vs.get(), w0, thr, level,
+                           depth, res + discard_result_off(0));
+        g_discard_launches[0]++;
+        HIPCK(hipGetLastError());
+    }
+    if (ranked) {
+        ProfScope ps("discard_cross", g_stream0, plane_bytes);
+        hipLaunchKernelGGL(k_discard_rank, dim3(h0), dim3(DISCARD_THREADS), 0, g_stream0, (const float *) c->bias0.get(), (const int32_t *) c->vs.get(), w0, w, thr, level,
+                           depth, partial, res + discard_result_off(1));
+        g_discard_launches[2]++;
+        HIPCK(hipGetLastError());
+        hipLaunchKernelGGL(k_discard_fold, dim3(discard_col_blocks(w)), dim3(DISCARD_THREADS), 0, g_stream0, (const int *) partial, w, 1, res + discard_result_off(1));
+        g_discard_launches[3]++;
+        HIPCK(hipGetLastError());
+    } else if (cross) {
+        ProfScope ps("discard_cross", g_stream0, plane_bytes + 8.0 * discard_partial_elems(w0, h0));
+        hipLaunchKernelGGL(k_discard_cross, dim3(discard_col_blocks(w0), discard_row_tiles(h0)), dim3(DISCARD_THREADS), 0, g_stream0, (const float *) c->bias0.get(),
+                           (const int32_t *) c->vs.get(), w0, h0, thr, level, depth, partial, res + discard_result_off(1));
+        g_discard_launches[1]++;
+        HIPCK(hipGetLastError());
+        hipLaunchKernelGGL(k_discard_fold, dim3(discard_col_blocks(w0)), dim3(DISCARD_THREADS), 0, g_stream0, (const int *) partial, w0, discard_row_tiles(h0),
+                           res + discard_result_off(1));
+        g_discard_launches[3]++;
+        HIPCK(hipGetLastError());
+    }
+    // 16 bytes for one scan, 32 for both
+    const int first = line ? 0 : 1, count = line && cross ? 2 : 1;
+    if ((rc = d2h_staged(out + discard_result_off(first), res + discard_result_off(first), (size_t) count * DISCARD_WORDS * sizeof(int)))) return rc;
+    tmp.done();
+    return 0;
+}
+
 // ---- include_ext/lqr_forward.h: forward-energy seam maps (kernels in k_forward.hip) ---------------------------------------------------------
 // A build owns its planes -- per image I, P (with a bias plane), the positions, the choices, the seam, and the map unless the caller
 // gave one -- and the job table, all taken in lqrhip_forward_begin before anything is launched.  It runs on g_stream0; the two events

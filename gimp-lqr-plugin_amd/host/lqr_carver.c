@@ -35,6 +35,7 @@
 #include "../../include_ext/lqr_forward.h"
 #include "../../include_ext/lqr_static.h"
 #include "../../include_ext/lqr_clipforward.h"
+#include "../../include_ext/lqr_remove.h"
 #include "../../include/lqr_hip.h"
 #include "lqr_mask_queue.h"
 #include "lqr_sched.h"
@@ -1876,6 +1877,114 @@ static LqrRetVal read_sizes(LqrCarver *r, const gint *sizes, gint n, void *const
 
 LqrRetVal lqrx_carver_read_sizes_device(LqrCarver *r, const gint *sizes, gint n, void *const *device_out) { return read_sizes(r, sizes, n, device_out, 1); }
 LqrRetVal lqrx_carver_read_sizes(LqrCarver *r, const gint *sizes, gint n, void *const *host_out) { return read_sizes(r, sizes, n, host_out, 0); }
+
+/* ======================= object removal (lqr_remove.h) =================== */
+/* Only the checks and the composition live here: the scan is k_discard.hip's behind lqrhip_discard_scan, the rounds are
+ * group_resize_entered's, the flattening group_flatten's.  No seam logic of its own. */
+enum { DS_MARKED = 0, DS_NEED = 1, DS_DEEPEST = 2 };
+
+static int strength_refused(float strength) { return !isfinite(strength) || strength < 0; }
+
+/* The scan of r's base layout as it stands, for every orientation o whose bit is set in `which`: res[o] = {visible marked pixels, the
+ * most in one line, the deepest level of a marked pixel}.  The lines of orientation o are the base layout's rows where the carver lies
+ * that way, and run across them where it does not: the carver is not transposed for it */
+static LqrRetVal discard_scan_run(LqrCarver *r, int which, float strength, int res[2][3])
+{
+    const int t = r->geo.transposed ? 1 : 0;
+    int out[8], o;
+    memset(out, 0, sizeof out);
+    if (r->has_bias)
+        HIP_CATCH(lqrhip_discard_scan(r->dev, r->geo.w0, r->geo.h0, r->geo.w, r->geo.level, r->geo.w0 - r->geo.w_start, strength,
+                                      ((which >> t) & 1 ? LQRHIP_DISCARD_LINE : 0) | ((which >> (1 - t)) & 1 ? LQRHIP_DISCARD_CROSS : 0), out));
+    for (o = 0; o < 2; o++) memcpy(res[o], out + (o == t ? 0 : 4), 3 * sizeof(int));
+    return LQR_OK;
+}
+/* AUTO: the orientation with the smaller need, a tie goes to 0 */
+static int discard_pick(int orientation, int res[2][3])
+{
+    return orientation != LQRX_ORIENTATION_AUTO ? orientation : res[1][DS_NEED] < res[0][DS_NEED] ? 1 : 0;
+}
+
+/* a pure read, as read_sizes is: the geometry, the read-out cache and the state word are neither consulted nor changed */
+LqrRetVal lqrx_carver_discard_scan(LqrCarver *r, gint orientation, gfloat strength, gint *marked, gint *need)
+{
+    int res[2][3], o;
+    if (!r || r->root || orientation < LQRX_ORIENTATION_AUTO || orientation > 1 || strength_refused(strength)) return LQR_ERROR;
+    LQR_CATCH(mask_queue_flush(r));
+    LQR_CATCH(discard_scan_run(r, orientation == LQRX_ORIENTATION_AUTO ? 3 : 1 << orientation, strength, res));
+    o = discard_pick(orientation, res);
+    if (marked) *marked = res[o][DS_MARKED];
+    if (need) *need = res[o][DS_NEED];
+    return LQR_OK;
+}
+
+/* inside the call (roots_enter): the carver flattened, as lqr_carver_flatten does it */
+static LqrRetVal flatten_entered(LqrCarver *r)
+{
+    Group g;
+    LqrRetVal ret;
+    LQR_CATCH(group_open(&g, &r, 1));
+    ret = group_flatten(&g);
+    if (ret != LQR_OK) { int k; for (k = 0; k < g.nb; k++) lqrhip_batch_abort(g.b[k]); }
+    group_close(&g);
+    return ret;
+}
+
+static LqrRetVal remove_entered(LqrCarver *r, int orientation, float strength, int max_seams, int restore, gint *orientation_used, gint *seams,
+                                gint *left)
+{
+    int res[2][3], o, W0, H0, L0, cap, cur = 0, fin;
+    LQR_CATCH(mask_queue_flush(r));
+    if (!lqr_geom_is_flat(&r->geo)) LQR_CATCH(flatten_entered(r));
+    W0 = lqr_carver_get_width(r); H0 = lqr_carver_get_height(r);
+    LQR_CATCH(discard_scan_run(r, orientation == LQRX_ORIENTATION_AUTO ? 3 : 1 << orientation, strength, res));
+    o = discard_pick(orientation, res);
+    if (orientation_used) *orientation_used = o;
+    if (seams) *seams = 0;
+    if (left) *left = 0;
+    if (res[o][DS_NEED] == 0) return LQR_OK;
+    L0 = o ? H0 : W0;
+    cap = MINI(max_seams, L0 - 2);
+    while (res[o][DS_NEED] > 0 && cur < cap) {
+        if (lqr_state_check(&r->state)) return LQR_USRCANCEL;
+        cur += MINI(MAXI(res[o][DS_NEED], LQRX_REMOVE_MIN_STEP), cap - cur);
+        LQR_CATCH(group_resize_entered(&r, 1, o ? W0 : L0 - cur, o ? L0 - cur : H0));
+        LQR_CATCH(discard_scan_run(r, 1 << o, strength, res));
+    }
+    if (res[o][DS_NEED] == 0) {
+        fin = res[o][DS_DEEPEST];
+        if (fin < cur) LQR_CATCH(group_resize_entered(&r, 1, o ? W0 : L0 - fin, o ? L0 - fin : H0));      /* served from the map */
+        if (seams) *seams = fin;
+    } else {                    /* the cap was reached */
+        if (seams) *seams = cur;
+        if (left) *left = res[o][DS_MARKED];
+    }
+    if (restore) {              /* the plug-in's SCALEBACK_MODE_LQRBACK, render.c:320-329 */
+        if (lqr_state_check(&r->state)) return LQR_USRCANCEL;
+        LQR_CATCH(flatten_entered(r));
+        LQR_CATCH(group_resize_entered(&r, 1, W0, H0));
+    }
+    return LQR_OK;
+}
+
+LqrRetVal lqrx_carver_remove_discarded(LqrCarver *r, gint orientation, gfloat strength, gint max_seams, gint restore, gint *orientation_used,
+                                       gint *seams, gint *left)
+{
+    const char *why = NULL;
+    LqrRetVal ret;
+    if (!r) why = "NULL carver";
+    else if (r->root) why = "an attached carver follows its root";
+    else if (!r->active || !r->progress) why = "the carver is not initialised";
+    else if (orientation < LQRX_ORIENTATION_AUTO || orientation > 1) why = "the orientation is 0, 1 or LQRX_ORIENTATION_AUTO";
+    else if (strength_refused(strength)) why = "the strength is finite and >= 0";
+    else if (max_seams < 1) why = "max_seams is at least 1";
+    else if ((orientation != 1 && lqr_carver_get_width(r) < 3) || (orientation != 0 && lqr_carver_get_height(r) < 3)) why = "a line of fewer than 3 pixels";
+    if (why) { fprintf(stderr, "liblqr-hip: lqrx_carver_remove_discarded refused: %s\n", why); return LQR_ERROR; }
+    LQR_CATCH(roots_enter(&r, 1, LQR_STATE_RESIZING));
+    ret = remove_entered(r, orientation, strength, max_seams, restore, orientation_used, seams, left);
+    roots_leave(&r, 1);
+    return ret;
+}
 
 /* ======================= seam-map colour ramp (I5) ======================== */
 LqrRetVal lqrx_vmap_to_rgba(LqrVMap *v, const gdouble col_start[3], const gdouble col_end[3], guchar *out_rgba)

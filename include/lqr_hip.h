@@ -263,6 +263,19 @@ int lqrhip_read_visible_device(LqrHipCarver *c, int w0, int h0, int w, int level
  * scratch planes where the images do not go straight to the caller's device memory): LQRHIP_CENSUS_COMPACT_SIZES counts them.
  * Everything is allocated before anything is launched: LQRHIP_ENOMEM has written nothing.  Returns with the outputs written. */
 int lqrhip_read_sizes(LqrHipCarver *c, int w0, int h0, int transposed, const int *levels, int n, void *const *outs, int on_device);
+/* lqr_remove.h: the discard scan of a root carver's base layout (w0 x h0, w columns of a row visible) as it stands: nothing is flattened
+ * or transposed.  A pixel is marked when its bias is below -strength and visible when its level is 0 or at least `level`.  which:
+ * LQRHIP_DISCARD_LINE scans the lines that are the base layout's rows (k_discard_line), LQRHIP_DISCARD_CROSS those that run across
+ * them (k_discard_cross and k_discard_fold; on a carver that hides pixels, level > 1, k_discard_rank: a column of the image is a rank
+ * among a row's visible pixels), or both.  out: 8 ints -- the line scan's {visible marked pixels, the most of them in one line, the
+ * deepest level of a marked pixel less `depth` (lqr_vmap_dump's numbering; 0: none has one), 0}, then the cross scan's; the words of
+ * a scan not asked for are 0, and all of them for a carver without a bias plane.  One pass over bias0 and vs per scan; 16 bytes per
+ * scan come back.  Everything is allocated before anything is launched.  lqrhip_discard_launches: launches of the four kernels
+ * (line, cross, rank, fold) since the last reset -- a test hook; lqrhip_launch_census has no slot left for them */
+#define LQRHIP_DISCARD_LINE 1
+#define LQRHIP_DISCARD_CROSS 2
+int lqrhip_discard_scan(LqrHipCarver *c, int w0, int h0, int w, int level, int depth, float strength, int which, int *out);
+void lqrhip_discard_launches(unsigned long long out4[4], int reset);
 /* lqr_forward.h: forward-energy seam maps of n FLAT root carvers of one shape and pixel kind (the host has flattened them), `depth` seams
  * in the direction `orientation` (0: the width changes).  transposed: the carvers lie transposed (their base layout's rows are image
  * columns); luma: the value read is luma; w_start: what the bias is divided by.  device_maps: n maps in device memory, width x height
