@@ -30,7 +30,9 @@
 //     Columns whose tile was not active in level L come from memory (nothing changed there).  Level L's results are
 //     stored only after the partner wave has passed that barrier: every slot has then CONSUMED its inputs of level L, so
 //     in place is safe (a slot's halo columns are its neighbours' own columns); inputs of later levels are rows nobody
-//     writes before those levels' own barriers.
+//     writes before those levels' own barriers.  k_band_levels2 (LV_TRACK) writes of an interior tile only what changed: the
+//     rows on which the keep rule changed an own pixel, from the lanes that changed any (the rest holds what was loaded from
+//     the same addresses; store_rows 0 writes everything, lqrhip_set_levels_store).
 //   * no reserve tiles, no requests, no edge watches, no inactive forwarding: the only spin is the level barrier.
 //   * every word and granule is published TWICE: the write-through copy above (visible from every XCD: the protocol rests on it
 //     alone) and a "near" copy at + near_off written with a plain store, which stays in the writer's L2.  An image's slots are
@@ -45,7 +47,8 @@
 // The kernel's body is k_levels_body.inc: k_band_levels2 (k_levels2.hip, two slots of an image per workgroup) includes the same text.
 // ---------------------------------------------------------------------------
 // [0] images stopped by three active tiles on one slot, [1] synchronous (mispredicted or second-tile) loads, [2] tile-levels
-// processed, [3] slot-levels idle, [4] levels in which a slot had two tiles
+// processed, [3] slot-levels idle, [4] levels in which a slot had two tiles, [5] rows of processed tile-levels written back, [6] rows
+// not written because no own pixel changed on them
 __device__ unsigned long long g_lv_stats[8];
 #ifdef LQR_TIMING
 // per slot of image 0 and wave: cycles in [0] barrier poll (wait_level), [1] active set + tile choice, [2] waiting for the partner's poll,
@@ -61,7 +64,7 @@ __device__ int g_lv_dbg;               // experiment switches (lqrhip_band_level
 // row dp_row, the others dp_row_g, exactly as k_dp_tile_p's general instantiations do.
 template <bool LR, bool RIG, int DELTA, bool RIGM>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void k_band_levels(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long long *exch, int epoch, int *dev_err, int P, int n_img)
+void k_band_levels(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long long *exch, int epoch, int *dev_err, int P, int n_img, int store_rows)
 {
 // (what the body leaves to the family, k_levels_body.inc: here a workgroup is one slot)
 #define LV_NT 128
@@ -73,6 +76,9 @@ void k_band_levels(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long
 #define LV_INIT_FLAGS if (tid == 0) { s_fail = 0; s_polled = -1; }
 #define LV_AFTER_SETUP
 #define LV_LEVEL_END asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+// (no change tracking in this family: three more instructions per row are what the groups it serves -- 8 and 16 images, where the row wave
+// is the critical path -- lose by, 74.8 -> 76.8 and 84.6 -> 86.7 ms per step; store_rows is ignored, every row is written, counter 6 stays 0)
+#define LV_TRACK 0
 #define LV_DBG g_lv_dbg
 #define LV_STATS g_lv_stats
 #define LV_TIME g_lv_time
@@ -82,16 +88,22 @@ void k_band_levels(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long
 
 // (the switches and the counters are both families': k_levels2.hip keeps its own device globals)
 extern "C" void lqrhip_band_levels_debug(int v) { if (lqrhip_init() < 0) return; (void) hipMemcpyToSymbol(HIP_SYMBOL(g_lv_dbg), &v, sizeof v); lqr_levels2_debug(v); }
+// Entries 5 and 6 (rows written back, rows skipped) are reported only while lqrhip_set_levels_store is pinned: left to itself the hook
+// differs between the families, and their event counters are compared as a whole (tests/test_levels_pair_gpu.py)
+static int g_lv_report_rows = 0;
+void lqr_levels_report_rows(int on) { g_lv_report_rows = on; }
 extern "C" int lqrhip_band_levels_stats(unsigned long long *out, int reset)
 {
     if (lqrhip_init() < 0) return -1;          // the symbol of the device the library selected (LOCAL_RANK), not device 0's
     (void) hipDeviceSynchronize();
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lv_stats), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
     if (reset) { unsigned long long z[8] = {0}; (void) hipMemcpyToSymbol(HIP_SYMBOL(g_lv_stats), z, sizeof z); }
-    return lqr_levels2_stats(out, reset);
+    const int rc = lqr_levels2_stats(out, reset);
+    if (!g_lv_report_rows) out[5] = out[6] = 0;
+    return rc;
 }
 
 // ---- the instantiations the shim launches (lqr_kernels.h lists them)
-#define INST(...) template __global__ void k_band_levels<__VA_ARGS__>(DevCarver *, DpK, int, int, int, unsigned long long *, int, int *, int, int);
+#define INST(...) template __global__ void k_band_levels<__VA_ARGS__>(DevCarver *, DpK, int, int, int, unsigned long long *, int, int *, int, int, int);
 K_BAND_LEVELS_FORMS(INST)
 #undef INST

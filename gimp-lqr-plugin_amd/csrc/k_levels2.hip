@@ -27,7 +27,7 @@ __device__ int g_lv2_dbg;              // lqrhip_band_levels_debug's switches, a
 
 template <bool LR, bool RIG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void k_band_levels2(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long long *exch, int epoch, int *dev_err, int P, int n_img)
+void k_band_levels2(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long long *exch, int epoch, int *dev_err, int P, int n_img, int store_rows)
 {
     constexpr int DELTA = 1;
     constexpr bool RIGM = false;
@@ -42,6 +42,7 @@ void k_band_levels2(DevCarver *cs, DpK p, int w, int h, int stride, unsigned lon
 #define LV_INIT_FLAGS if (tid == 0) s_fail = 0; if ((tid & 127) == 0) LV_POLLED = -1;
 #define LV_AFTER_SETUP if (slot >= P) return;
 #define LV_LEVEL_END asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#define LV_TRACK 1
 #define LV_DBG g_lv2_dbg
 #define LV_STATS g_lv2_stats
 #define LV_TIME g_lv2_time
@@ -61,6 +62,6 @@ int lqr_levels2_stats(unsigned long long *out, int reset)
 }
 
 // ---- the instantiations the shim launches (lqr_kernels.h lists them)
-#define INST(...) template __global__ void k_band_levels2<__VA_ARGS__>(DevCarver *, DpK, int, int, int, unsigned long long *, int, int *, int, int);
+#define INST(...) template __global__ void k_band_levels2<__VA_ARGS__>(DevCarver *, DpK, int, int, int, unsigned long long *, int, int *, int, int, int);
 K_BAND_LEVELS2_FORMS(INST)
 #undef INST

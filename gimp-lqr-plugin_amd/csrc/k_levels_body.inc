@@ -9,10 +9,12 @@
 //   LV_INIT_FLAGS    clears s_fail and every slot's LV_POLLED
 //   LV_AFTER_SETUP   what the waves of a slot that does not exist do once the workgroup's tables stand
 //   LV_LEVEL_END     the hand-over that ends an iteration of the level loop: the workgroup's waves meet
+//   LV_TRACK         1: the row loop keeps which rows and lanes changed and store_u writes only those (store_rows); 0: every row, as ever
 //   LV_DBG, LV_STATS, LV_TIME    the translation unit's device globals (switches, event counters, the timing build's cycle counts)
     static_assert(DELTA >= 1 && DELTA <= LQR_FAST_MAX_DELTA && (DELTA <= 4 || RIG) && (RIG || !RIGM), "delta_x 1 .. 10 (5 .. 10: the rigidity form, with a zero table if there is none); a rigidity mask only matters with rigidity");
     constexpr int PX = 2, HALO = 32, OWN = LV_OWN, HL = 16, R = lv_rows(DELTA, RIGM), TILE = 128;
     static_assert(R * DELTA <= HALO, "a level's errors stay inside the halo");
+    static_assert(HL == 16 && R <= 32, "lv_own_or: the own lanes are two whole rows of 16 lanes; a level's rows fit one word");
     typedef LaneVec<2>::F FV;
     typedef LaneVec<2>::L LV;
     typedef GLOBAL_AS FV GFV;
@@ -163,8 +165,14 @@
     };
     float mp[PX] = {INF, INF};
     int acc_l0 = 0, acc_l1 = 0;                 // XOR of old and new m on the level's last row (pixel 0 / 1 of the lane)
+    // bit r: the keep rule changed a pixel of this lane on row r (ch[]: a pixel it leaves alone gets mc = mo and the back pointer it had,
+    // which is what the level's loads read from the very address its stores go to).  One VGPR, reduced over the own lanes once, after
+    // the rows (lv_own_or: the rows some own lane changed; a ballot: the own lanes that changed any row); store_u writes only those
+    // rows, from only those lanes, of an interior tile (store_rows, lqrhip_set_levels_store; 0: every row from every lane)
+    unsigned chg_rows = 0;
     auto batch_u = [&](int ybase) {
         const int nr = min(R, h - ybase);       // (the image's last level computes surplus rows from copies of its last row)
+        chg_rows = 0;
 #pragma unroll
         for (int r = 0; r < R; r++) {
             float mc[PX], e[PX], mo[PX];
@@ -187,6 +195,13 @@
 #pragma unroll
                 for (int k = 0; k < PX; k++) mc[k] = e[k];
                 lnew = 0;
+                if constexpr (LV_TRACK) chg_rows |= 1u;                  // (counted as changed whatever ch says)
+            }
+            if constexpr (LV_TRACK) {
+                // (two selects and one three-way OR: OR-ing the two compares first holds both scalar-register pairs for one more instruction)
+                unsigned b0 = ch[0] ? (1u << r) : 0u;
+                asm("" : "+v"(b0));
+                chg_rows |= b0 | (ch[1] ? (1u << r) : 0u);
             }
             if (r == R - 1) {
                 const int msk = (r < nr) ? -1 : 0;
@@ -198,16 +213,22 @@
             q_lo[r] = (LV) lnew;
         }
     };
-    auto store_u = [&](int ybase) {
+    // rows: bit r set = row r is written (wave-uniform; the rows past the image's end are never); lanes: the lanes that write (one
+    // condition around all the rows; ~0: every lane, those that own nothing to the spare row below the image, as k_dp_tile_p)
+    auto store_u = [&](int ybase, unsigned rows, unsigned long long lanes) {
         const bool own_ = is_own();
-        const unsigned inc = own_ ? (unsigned) stride : 0u, inc4 = inc * 4u;
-        unsigned so = own_ ? (unsigned) ybase * (unsigned) stride + (unsigned) x0 : (unsigned) h * (unsigned) stride + (unsigned) (PX * lane), so4 = so * 4u;
-        const int nr = min(R, h - ybase);
+        const unsigned inc = own_ ? (unsigned) stride : 0u;
+        const unsigned so0 = own_ ? (unsigned) ybase * (unsigned) stride + (unsigned) x0 : (unsigned) h * (unsigned) stride + (unsigned) (PX * lane);
+        if (__builtin_amdgcn_inverse_ballot_w64(lanes)) {
 #pragma unroll
-        for (int r = 0; r < R; r++, so += inc, so4 += inc4) {
-            if (r < nr) {
-                *(GFV *) ((gu8 *) c.m + so4) = q_mo[r];
-                *(GLV *) (c.least + so) = q_lo[r];
+            for (int r = 0; r < R; r++) {
+                if ((rows >> r) & 1u) {
+                    // (the row's offset worked out where it is written, one 24-bit multiply-add -- a stride is far below 2^24: as a
+                    // running sum a skipped row pays its two additions)
+                    const unsigned so = so0 + __umul24((unsigned) r, inc);
+                    *(GFV *) ((gu8 *) c.m + (so << 2)) = q_mo[r];
+                    *(GLV *) (c.least + so) = q_lo[r];
+                }
             }
         }
     };
@@ -270,6 +291,10 @@
     // there is one, else prefetches its own next level.  Iteration nblk only closes the last level.
     unsigned n_proc = 0, n_idle = 0, n_sync = 0, n_two = 0;             // (32 bits: scalar registers are what the row loop is short of)
     int hold_L = -1;                            // the level whose (unstored) results sit in this wave's registers
+    unsigned hold_rows = 0;                     // ... and its rows that an own lane changed (lv_own_or of chg_rows)
+    unsigned long long hold_lanes = 0;          // ... and its own lanes that changed a pixel on any row
+    unsigned n_rows = 0;                        // rows stored (low half) and rows skipped (high half): a wave has at most LV_MAX_LEVELS * 32 rows
+    static_assert(LV_MAX_LEVELS * 32 < (1 << 16), "two counts of rows in one word");
 #ifdef LQR_TIMING
     unsigned long long ltt[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long ltprev = __builtin_readcyclecounter();
@@ -329,7 +354,19 @@
         // ---- STORE: level L - 1 is final and every slot has consumed its inputs
         LTT(1);
         LJIT(3);
-        if (hold_L >= 0 && passed) { store_u(hold_L * R); hold_L = -1; }
+        if (hold_L >= 0 && passed) {
+            // a row that no own lane changed, and a lane that changed nothing on any row, hold what the loads read from these addresses: not
+            // written again (nor do the lanes that own nothing write to the spare row then).  A tile that reaches over the frame's border
+            // is written whole: its own lanes can hold pixels outside the frame (+inf, whatever stood there).
+            // (x0, and with it is_interior() and is_own(), must still be the HELD tile's here: set_tile runs only in LOAD, below STORE)
+            const bool part = LV_TRACK && store_rows && is_interior();
+            const int nr = min(R, h - hold_L * R);
+            const unsigned all = nr >= 32 ? ~0u : (1u << nr) - 1u;
+            const unsigned rows = (unsigned) __builtin_amdgcn_readfirstlane((int) (part ? hold_rows & all : all));      // (a scalar: the rows' branches are scalar ones)
+            n_rows += (unsigned) __builtin_popcount(rows) + ((unsigned) __builtin_popcount(all & ~rows) << 16);
+            store_u(hold_L * R, rows, uni64(part ? hold_lanes : ~0ull));
+            hold_L = -1;
+        }
         LTT(3);
         if (L == nblk) break;
         if (mine && passed && any_collision(A)) {
@@ -390,6 +427,7 @@
                     for (int k = 0; k < PX; k++) { q_e[r][k] = ik[k] ? q_e[r][k] : INF; q_mo[r][k] = ik[k] ? q_mo[r][k] : INF; }
             }
             batch_u(L * R);
+            if constexpr (LV_TRACK) { hold_rows = lv_own_or(chg_rows); hold_lanes = __ballot(own_lane && chg_rows != 0u); }
             LTT(6);
             hold_L = L;
             cur_full = false;                    // (the registers hold results now)
@@ -425,3 +463,4 @@
 #endif
     if (lane == 0) { atomicAdd(&LV_STATS[2], (unsigned long long) n_proc); atomicAdd(&LV_STATS[3], (unsigned long long) n_idle); if (n_two) atomicAdd(&LV_STATS[4], (unsigned long long) n_two); }
     if (lane == 0 && n_sync) atomicAdd(&LV_STATS[1], (unsigned long long) n_sync);
+    if (lane == 0 && n_rows) { atomicAdd(&LV_STATS[5], (unsigned long long) (n_rows & 0xffffu)); atomicAdd(&LV_STATS[6], (unsigned long long) (n_rows >> 16)); }

@@ -11,3 +11,4 @@
 #undef LV_STATS
 #undef LV_TIME
 #undef LV_LEVEL_END
+#undef LV_TRACK

@@ -82,12 +82,13 @@ __global__ __launch_bounds__(64 * DPP_W) void k_dp_tile_p(DevCarver *cs, DpK p, 
     K_BAND_LEVELS_FORMS_W(X, LR, 5) K_BAND_LEVELS_FORMS_W(X, LR, 6) K_BAND_LEVELS_FORMS_W(X, LR, 7) K_BAND_LEVELS_FORMS_W(X, LR, 8) K_BAND_LEVELS_FORMS_W(X, LR, 9) K_BAND_LEVELS_FORMS_W(X, LR, 10)
 #define K_BAND_LEVELS_FORMS(X) K_BAND_LEVELS_FORMS_LR(X, false) K_BAND_LEVELS_FORMS_LR(X, true)
 template <bool LR, bool RIG, int DELTA, bool RIGM>
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_band_levels(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long long *exch, int epoch, int *dev_err, int P, int n_img);
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_band_levels(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long long *exch, int epoch, int *dev_err, int P, int n_img, int store_rows);
 
 // k_levels2.hip: two slots of an image per workgroup.  X(LR, RIG): delta_x 1, no rigidity mask; one residency class of its own
 #define K_BAND_LEVELS2_FORMS(X) X(false, false) X(false, true) X(true, false) X(true, true)
 template <bool LR, bool RIG>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_band_levels2(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long long *exch, int epoch, int *dev_err, int P, int n_img);
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_band_levels2(DevCarver *cs, DpK p, int w, int h, int stride, unsigned long long *exch, int epoch, int *dev_err, int P, int n_img, int store_rows);
+void lqr_levels_report_rows(int on);                            // lqrhip_band_levels_stats reports entries 5 and 6 (k_levels.hip)
 void lqr_levels2_debug(int v);                                  // lqrhip_band_levels_debug's switches for this family's device global
 int lqr_levels2_stats(unsigned long long *out, int reset);      // adds this family's event counters to out[0 .. 8)
 

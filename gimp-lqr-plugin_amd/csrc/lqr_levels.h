@@ -21,7 +21,18 @@ __device__ __forceinline__ unsigned long long uni64(unsigned long long v)
 {
     return ((unsigned long long) (unsigned) __builtin_amdgcn_readfirstlane((int) (v >> 32)) << 32) | (unsigned) __builtin_amdgcn_readfirstlane((int) v);
 }
-struct LvMask {                       // a set of tiles (uniform over the wave); LV_MAX_TILES = 64: one word
+// the OR of v over a tile's own lanes 16 .. 47, as a scalar: a prefix OR inside each row of 16 lanes (DPP row_shr 1, 2, 4, 8; a lane
+// without a source reads 0), whose last lanes 31 and 47 then hold their rows' ORs
+__device__ __forceinline__ unsigned lv_own_or(unsigned v)
+{
+    int x = (int) v;
+    x |= __builtin_amdgcn_mov_dpp(x, 0x111, 0xf, 0xf, true);
+    x |= __builtin_amdgcn_mov_dpp(x, 0x112, 0xf, 0xf, true);
+    x |= __builtin_amdgcn_mov_dpp(x, 0x114, 0xf, 0xf, true);
+    x |= __builtin_amdgcn_mov_dpp(x, 0x118, 0xf, 0xf, true);
+    return (unsigned) (__builtin_amdgcn_readlane(x, 31) | __builtin_amdgcn_readlane(x, 47));
+}
+struct LvMask {                      // a set of tiles (uniform over the wave); LV_MAX_TILES = 64: one word
     unsigned long long lo;
     __device__ __forceinline__ void set(int t) { lo |= 1ull << t; }
     __device__ __forceinline__ bool has(int t) const { return t >= 0 && t < LV_MAX_TILES && ((lo >> t) & 1ull); }

@@ -54,6 +54,7 @@ struct PlanKnobs {
     int update_mode = -1;           // lqrhip_set_update_mode
     int band_levels = -1;           // k_band_levels: -1 automatic; 0 never; n: n slots per image
     int levels_wg_slots = -1;       // slots per workgroup of the level kernel: -1 automatic (plan_levels_wg_slots); 1: one (k_band_levels); 2: two (k_band_levels2) wherever a form exists
+    int levels_store = -1;          // what the level kernel writes back: -1 automatic (plan_levels_store); 0: every row of a level from every lane; 1: only the changed rows, from the own lanes that changed
     int dpp_limit = -1;             // -1: the occupancy-derived bounds; >= 0: at most that many workgroups for a spinning grid
     int dpp_px = 0;                 // 2, 3 or 4 pins the persistent sweep's geometry code (0 = by batch size)
     int sub_batches = 0;            // streams of a group; 0: automatic (plan_streams)
@@ -103,6 +104,7 @@ struct StepPlan {
     int band = -1;                  // LQRHIP_CENSUS_BAND_* in front of dp (a _SWEEP_UPDATE then); -1: dp alone (the tiled update, a full DP)
     int levels_P = 0;               // k_band_levels: slots per image
     int levels_wg_slots = 1;        // ... and per workgroup: 2 is k_band_levels2 (counted under _BAND_LEVELS too)
+    int levels_store = 0;           // ... and what it writes back: 0 every row from every lane, 1 the changed rows from the lanes that changed (plan_levels_store)
     DpPlan dp;                      // form -1: nothing is left to update (liblqr's finish_vsmap case)
 };
 
@@ -235,6 +237,18 @@ static inline int plan_levels_wg_slots(const PlanKnobs &k, const PlanDevice &d, 
     if (k.levels_wg_slots == 2) return 2;
     return !b.shared && b.group() * (size_t) P > (size_t) d.n_cu ? 2 : 1;
 }
+// What the level kernel writes back (its store_rows argument): 1 = of an interior tile only the rows on which the keep rule changed an
+// own pixel, from the own lanes that changed a pixel on any row of the level -- the rest holds what the level's loads read from the
+// same addresses, and the halo lanes do not write to the spare row -- 0 = every row of every processed tile-level from every lane, as
+// before.  Only k_band_levels2 has the form: keeping the change bits costs three instructions per row, which the groups the one-slot
+// family serves lose by (the row wave is their critical path).  The knob at 0 pins 0; otherwise 1 wherever the two-slot family runs.
+// Measured (profiles/levels_store/README.md; ms per step, parent / new): 64 images 189.2 187.6 189.5 / 182.0 185.1 185.5; Mseams*px/s
+// in the order parent, new, new, parent: 32 images 449.0 k 464.2 k 466.7 k 451.1 k, 48: 533.3 533.6 529.8 516.6; with the bits kept in
+// the one-slot family too 8 images 177.3 k 172.9 k 172.5 k 177.4 k and 16: 313.8 306.5 306.0 313.8, without them 181.0 180.6 and 318.3 318.0.
+static inline int plan_levels_store(const PlanKnobs &k, int wg_slots)
+{
+    return k.levels_store != 0 && wg_slots == 2 ? 1 : 0;
+}
 // How many images of frame width `w` (the direction being carved) one lock-step batch may hold and still run delta_x != 1 /
 // rigidity-mask carvers on the tiled kernels (k_dp_tile_p's general instantiations: one workgroup per 64 columns per image, all
 // co-resident).  Beyond it such a batch would fall to the one-wave-per-image band kernel (~30x slower), so the host carves larger
@@ -332,7 +346,7 @@ static inline StepPlan plan_seam_step(const PlanKnobs &k, const PlanDevice &d, c
                        plan_persistent_px(k, d, b, w, general, delta, b.images) != 0;
     // the level kernel is asked first: a positive P wins over the tiled update
     if (fast_delta && mode != 3 && (mode == 5 || levels_auto(k, delta, b.group(), plain))) s.levels_P = plan_levels_P(k, d, b, wnew, h, delta);
-    if (s.levels_P > 0) { s.band = LQRHIP_CENSUS_BAND_LEVELS; s.levels_wg_slots = plan_levels_wg_slots(k, d, b, delta, general, s.levels_P); }
+    if (s.levels_P > 0) { s.band = LQRHIP_CENSUS_BAND_LEVELS; s.levels_wg_slots = plan_levels_wg_slots(k, d, b, delta, general, s.levels_P); s.levels_store = plan_levels_store(k, s.levels_wg_slots); }
     else if (tiled) {
         s.dp = plan_persistent(plan_persistent_px(k, d, b, wnew, general, delta, b.images), general, b.images);
         return s;

@@ -1109,6 +1109,7 @@ extern "C" void lqrhip_set_dp_persistent_px(int px) { g_knobs.dpp_px = (px == 2 
 extern "C" void lqrhip_set_dp_persistent_limit(int workgroups) { g_knobs.dpp_limit = workgroups; }
 extern "C" void lqrhip_set_band_levels(int slots) { g_knobs.band_levels = slots; }
 extern "C" void lqrhip_set_levels_wg_slots(int slots) { g_knobs.levels_wg_slots = slots == 1 || slots == 2 ? slots : -1; }
+extern "C" void lqrhip_set_levels_store(int mode) { g_knobs.levels_store = mode == 0 || mode == 1 ? mode : -1; lqr_levels_report_rows(g_knobs.levels_store >= 0); }
 static unsigned long long g_levels_pair_launches = 0;
 extern "C" unsigned long long lqrhip_levels_pair_launches(int reset) { const unsigned long long n = g_levels_pair_launches; if (reset) g_levels_pair_launches = 0; return n; }
 static PlanBatch plan_batch(const LqrHipBatch *b)
@@ -1304,7 +1305,7 @@ static int pay_catchup(LqrHipBatch *b)
     return 0;
 }
 
-static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr, int P, int wg_slots, bool rigm)
+static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr, int P, int wg_slots, int store_rows, bool rigm)
 {
     LqrHipCarver *c0 = b->cs[0];
     const size_t n = b->cs.size();
@@ -1317,7 +1318,7 @@ static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr
     if (wg_slots == 2) {            // two slots per workgroup (plan_levels_wg_slots: delta_x 1, no mask)
         const dim3 grid2(lv2_grid(n, P));
 #define CASE(LR, RIG) if (f.lr == LR && f.rig == RIG && f.delta == 1 && !f.rigm) \
-        hipLaunchKernelGGL((k_band_levels2<LR, RIG>), grid2, dim3(256), 0, b->stream, b->d_desc, k, w, h, c0->stride, b->exch.get(), epoch, g_dev_err, P, (int) n); else
+        hipLaunchKernelGGL((k_band_levels2<LR, RIG>), grid2, dim3(256), 0, b->stream, b->d_desc, k, w, h, c0->stride, b->exch.get(), epoch, g_dev_err, P, (int) n, store_rows); else
         K_BAND_LEVELS2_FORMS(CASE) return no_form("k_band_levels2");
 #undef CASE
         HIPCK(hipGetLastError());
@@ -1325,7 +1326,7 @@ static int launch_band_levels(LqrHipBatch *b, const DpK &k, int w, int h, int lr
         return 0;
     }
 #define CASE(LR, RIG, DELTA, RIGM) if (f.lr == LR && f.rig == RIG && f.delta == DELTA && f.rigm == RIGM) \
-        hipLaunchKernelGGL((k_band_levels<LR, RIG, DELTA, RIGM>), grid, dim3(128), 0, b->stream, b->d_desc, k, w, h, c0->stride, b->exch.get(), epoch, g_dev_err, P, (int) n); else
+        hipLaunchKernelGGL((k_band_levels<LR, RIG, DELTA, RIGM>), grid, dim3(128), 0, b->stream, b->d_desc, k, w, h, c0->stride, b->exch.get(), epoch, g_dev_err, P, (int) n, store_rows); else
     K_BAND_LEVELS_FORMS(CASE) return no_form("k_band_levels");
 #undef CASE
     HIPCK(hipGetLastError());
@@ -1464,7 +1465,7 @@ static int launch_band(LqrHipBatch *b, const StepPlan &s, const StepVals &v)
     const DpK &k = v.k;
     if (s.band == LQRHIP_CENSUS_BAND_LEVELS) {
         ProfScope ps("band_levels", b->stream, 0);
-        if (int rc = launch_band_levels(b, k, wnew, h, leftright_next, s.levels_P, s.levels_wg_slots, v.rigm)) return rc;
+        if (int rc = launch_band_levels(b, k, wnew, h, leftright_next, s.levels_P, s.levels_wg_slots, s.levels_store, v.rigm)) return rc;
     } else if (s.band == LQRHIP_CENSUS_BAND_TW) {
         ProfScope ps("band_update", b->stream, 0);
         CENSUS(LQRHIP_CENSUS_BAND_TW);

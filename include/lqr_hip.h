@@ -431,11 +431,17 @@ void lqrhip_set_band_levels(int slots);
 /* Test hook: slots per WORKGROUP of the level kernel: -1 automatic, 1 never two (k_band_levels), 2 two (k_band_levels2) wherever a form
  * exists (delta_x 1, no rigidity mask that matters, at least 2 slots per image) and its grid is resident. */
 void lqrhip_set_levels_wg_slots(int slots);
+/* Test hook: what the level kernel writes back (k_band_levels2 only: k_band_levels ignores it and writes everything): 0 every row of every processed tile-level from every lane (the lanes
+ * that own nothing to the spare row), 1 of an interior tile only the rows on which an own pixel changed, and of those only from the
+ * own lanes that changed a pixel on any row of the level -- unchanged own lanes and all halo lanes are switched off (what is not
+ * written holds what was loaded from the same addresses), -1 automatic (plan_levels_store: 1 wherever k_band_levels2 runs). */
+void lqrhip_set_levels_store(int mode);
 /* launches of k_band_levels2 since the last reset (they are counted under LQRHIP_CENSUS_BAND_LEVELS as well) */
 unsigned long long lqrhip_levels_pair_launches(int reset);
 /* k_band_levels' events since the last reset: [0] images stopped by THREE active tiles on one slot (a slot takes two, one per
  * wave; the full-width sweep took over), [1] synchronous (mispredicted or second-tile) loads, [2] tile-levels processed,
- * [3] slot-levels idle, [4] levels in which a slot had two tiles */
+ * [3] slot-levels idle, [4] levels in which a slot had two tiles, [5] rows of processed tile-levels written back, [6] rows not written
+ * because no own pixel changed on them -- both counted only while lqrhip_set_levels_store is pinned to 0 or 1 */
 int lqrhip_band_levels_stats(unsigned long long *out8, int reset);
 /* Test hook: the launch census -- which FORM of each stage the shim launched since the last reset, counted on the host at the
  * launch sites (lqrhip_prof_get's names do not tell: "band_update" is four kernels, "dp_update" every sweep).  Copies the first
