@@ -37,18 +37,22 @@ struct G32 { u32x4 a[CG]; uint32_t edge; };     // 4-byte planes: en, m, rigidit
 struct G8 { uint32_t a[CG]; uint32_t edge; };   // the back-pointer bytes, 4 px per dword
 
 // ---- side 0: new[p] = old[p + 1] for p in [pv, pend); pend = physical end (exclusive) of the row after the carve.
-// Groups run left to right from `base`.
-__device__ __forceinline__ void ld_left_u32(const gu32 *row, int base, int pend, int lane, G32 &g)
+// Groups run left to right from `base`, which lies at or below `lo`, the first position of the job: a lane whose four elements
+// end below lo takes no part (none does while base is lo rounded down to a vector; with base rounded down to a line, up to 7).
+// LINE false: base is lo rounded down to a vector, nothing to test (k_carve, whose instructions tests/test_carve_beside_meta.py pins).
+template <bool LINE>
+__device__ __forceinline__ void ld_left_u32(const gu32 *row, int base, int lo, int pend, int lane, G32 &g)
 {
 #pragma unroll
     for (int u = 0; u < CG; u++) {
         const int x = base + u * 256 + lane * 4;
         // x <= pend: the chunk that starts at pend holds the old last element, which the lane before needs
-        g.a[u] = (x <= pend) ? __builtin_nontemporal_load((const GLOBAL_AS u32x4 *) (row + x)) : (u32x4) {0u, 0u, 0u, 0u};
+        g.a[u] = ((!LINE || x + 3 >= lo) && x <= pend) ? __builtin_nontemporal_load((const GLOBAL_AS u32x4 *) (row + x)) : (u32x4) {0u, 0u, 0u, 0u};
     }
     g.edge = (lane == 63 && base + CGPX <= pend) ? row[base + CGPX] : 0u;
 }
-__device__ __forceinline__ void st_left_u32(gu32 *row, int base, int pv, int pend, int lane, const G32 &g)
+template <bool LINE>
+__device__ __forceinline__ void st_left_u32(gu32 *row, int base, int lo, int pv, int pend, int lane, const G32 &g)
 {
 #pragma unroll
     for (int u = 0; u < CG; u++) {
@@ -56,7 +60,7 @@ __device__ __forceinline__ void st_left_u32(gu32 *row, int base, int pv, int pen
         const uint32_t first_next = (u < CG - 1) ? (uint32_t) __builtin_amdgcn_readlane((int) g.a[u < CG - 1 ? u + 1 : CG - 1].x, 0) : 0u;
         const uint32_t lane63 = (u < CG - 1) ? first_next : g.edge;
         const uint32_t nx = (uint32_t) __builtin_amdgcn_update_dpp((int) lane63, (int) g.a[u].x, DPP_WAVE_SHL1, 0xf, 0xf, false);
-        if (x < pend) {
+        if ((!LINE || x + 3 >= lo) && x < pend) {
             u32x4 o;
             o.x = (x >= pv) ? g.a[u].y : g.a[u].x;
             o.y = (x + 1 >= pv) ? g.a[u].z : g.a[u].y;
@@ -172,15 +176,17 @@ __device__ __forceinline__ int rebase_dx(int dx, int xx, int xo, int vprev, int 
 // ---- back pointers, side 0.  New frame column xx sits at physical org + xx and takes old column xx + (xx >= v).
 // Pixels left of the seam whose parent may lie right of the seam of the row above (xx >= start = min(v, vprev - delta))
 // are re-based too; bytes outside [start, wnew) are written back as loaded.
-__device__ __forceinline__ void ld_left_8(const gu32 *row32, int base, int pend, int lane, G8 &g)
+template <bool LINE>
+__device__ __forceinline__ void ld_left_8(const gu32 *row32, int base, int lo, int pend, int lane, G8 &g)
 {
 #pragma unroll
     for (int u = 0; u < CG; u++) {
         const int x = base + u * 256 + lane * 4;
-        g.a[u] = (x <= pend) ? __builtin_nontemporal_load(row32 + (x >> 2)) : 0u;
+        g.a[u] = ((!LINE || x + 3 >= lo) && x <= pend) ? __builtin_nontemporal_load(row32 + (x >> 2)) : 0u;
     }
     g.edge = (lane == 63 && base + CGPX <= pend) ? row32[(base + CGPX) >> 2] : 0u;
 }
+template <bool LINE>
 __device__ __forceinline__ void st_left_8(gu32 *row32, int base, int org, int start, int v, int vprev, int y, int wnew, int lane, const G8 &g)
 {
     const int pend = org + wnew;
@@ -190,7 +196,7 @@ __device__ __forceinline__ void st_left_8(gu32 *row32, int base, int org, int st
         const uint32_t first_next = (u < CG - 1) ? (uint32_t) __builtin_amdgcn_readlane((int) g.a[u < CG - 1 ? u + 1 : CG - 1], 0) : 0u;
         const uint32_t lane63 = (u < CG - 1) ? first_next : g.edge;
         const uint32_t nx = (uint32_t) __builtin_amdgcn_update_dpp((int) lane63, (int) g.a[u], DPP_WAVE_SHL1, 0xf, 0xf, false);
-        if (x < pend) {
+        if ((!LINE || x + 3 >= org + start) && x < pend) {
             const uint64_t both = ((uint64_t) nx << 32) | g.a[u];
             uint32_t o = 0;
 #pragma unroll
@@ -256,19 +262,25 @@ __device__ __forceinline__ void st_right_8(gu32 *row32, int gbase, int org, int 
 // PHYSICAL view, org / side = what k_vpath* published for this seam, w = the width before the carve.
 // BESIDE (k_carve_u, k_carve_v): the energy role of the same launch writes en[pa .. pb] of this row; h and radius are read for that interval only
 // SR (lqr_common.h): how seam_x is read -- SeamLive where the walk role of the same launch writes it (k_carve_v)
-template <bool BESIDE, class SR = SeamPlain>
-__device__ __forceinline__ void carve_row(const GCarver &c, int org, int side, int y, int w, int stride, int delta, int move_dp, int lane, int h = 0, int radius = 0, SR sr = SR())
+// line (plan_carve_line, lqr_plan.h): 1 = a row's groups start (side 0) / end (side 1) on a 32-element boundary, so that every
+// 1 KB access of a wave to a float plane covers 8 whole 128-byte lines (rows start on line boundaries: the planes' stride is a
+// multiple of 64 elements) and neighbouring chunks share none; 0 = on a 4-element boundary, the vector's alignment, as before: 9
+// lines in 15 of 16 cases.  Either way the same vectors are loaded and stored, each once; only which wave access takes them differs.
+// LINE false: there is no such argument, the vector's alignment at compile time (k_carve: the code it always had).
+template <bool BESIDE, bool LINE = true, class SR = SeamPlain>
+__device__ __forceinline__ void carve_row(const GCarver &c, int org, int side, int y, int w, int stride, int delta, int move_dp, int line, int lane, int h = 0, int radius = 0, SR sr = SR())
 {
-    const int wnew = w - 1;
+    const int wnew = w - 1, amask = LINE && line ? 31 : 3;
     int pa = 0x7fffffff, pb = -1;
     if (BESIDE) {
         int xmin, xmax;
         nrg_interval(c.seam_x, y, h, wnew, radius, xmin, xmax, sr);
         if (xmin <= xmax) { pa = org + side + xmin; pb = org + side + xmax; }
     }
-    const int v = sr(c.seam_x + y);
+    // (LINE: the seam's columns are uniform, and said so -- every bound of the row's job stays in scalar registers, which pays for the job's lower bound)
+    const int v = LINE ? __builtin_amdgcn_readfirstlane(sr(c.seam_x + y)) : sr(c.seam_x + y);
     const size_t ro = (size_t) y * stride;
-    const int vprev = y > 0 ? sr(c.seam_x + (y - 1)) : 0;
+    const int vprev = y > 0 ? (LINE ? __builtin_amdgcn_readfirstlane(sr(c.seam_x + (y - 1))) : sr(c.seam_x + (y - 1))) : 0;
     gu32 *en = (gu32 *) (c.en + ro), *mm = (gu32 *) (c.m + ro), *l32 = (gu32 *) (c.least + ro);
     gu32 *rg = c.rig ? (gu32 *) (c.rig + ro) : (gu32 *) nullptr;
     // pix and bias are NOT moved: they stay in the frame of `frozen epoch` and the energy
@@ -280,26 +292,28 @@ __device__ __forceinline__ void carve_row(const GCarver &c, int org, int side, i
         int x0 = 0, fq = -1;
         uint32_t fval = 0;
         if (BESIDE) fq = en_fix_left(en, pv, pend, pb, lane, x0, fval);
-        for (int base = (org + (move_dp ? start : v)) & ~3; base < pend; base += CGPX) {
+        const int lo = org + (move_dp ? start : v);
+        for (int base = lo & ~amask; base < pend; base += CGPX) {
             G32 E, M;
             G8 L;
-            ld_left_u32(en, base, pend, lane, E);
-            if (move_dp) { ld_left_u32(mm, base, pend, lane, M); ld_left_8(l32, base, pend, lane, L); }
-            if (BESIDE) st_left_en(en, base, x0, pend, lane, E); else st_left_u32(en, base, pv, pend, lane, E);
-            if (move_dp) { st_left_u32(mm, base, pv, pend, lane, M); st_left_8(l32, base, org, start, v, vprev, y, wnew, lane, L); }
+            ld_left_u32<LINE>(en, base, lo, pend, lane, E);
+            if (move_dp) { ld_left_u32<LINE>(mm, base, lo, pend, lane, M); ld_left_8<LINE>(l32, base, lo, pend, lane, L); }
+            if (BESIDE) st_left_en(en, base, x0, pend, lane, E); else st_left_u32<LINE>(en, base, lo, pv, pend, lane, E);      // (x0 >= pv >= lo)
+            if (move_dp) { st_left_u32<LINE>(mm, base, lo, pv, pend, lane, M); st_left_8<LINE>(l32, base, org, start, v, vprev, y, wnew, lane, L); }
         }
         if (BESIDE && fq >= 0) __builtin_nontemporal_store(fval, en + fq);
         if (rg)
-            for (int base = pv & ~3; base < pend; base += CGPX) { G32 R; ld_left_u32(rg, base, pend, lane, R); st_left_u32(rg, base, pv, pend, lane, R); }
+            for (int base = pv & ~amask; base < pend; base += CGPX) { G32 R; ld_left_u32<LINE>(rg, base, pv, pend, lane, R); st_left_u32<LINE>(rg, base, pv, pv, pend, lane, R); }
     } else {
         const int pv = org + v;
         const int end_l = (y > 0) ? min(wnew, max(v, vprev + delta)) : min(wnew, v);      // back pointers' job: new columns [0, end_l)
         const int ptop = org + 1 + max(end_l, 0);
-        const int top_u = (pv | 3) + 1;
+        // (the loads and stores of this side carry both bounds of the job already; the edge lane's group always holds a destination)
+        const int top_u = (pv | amask) + 1;
         int x0 = 0, x1 = 0, fq = -1;
         uint32_t fval = 0;
         if (BESIDE) fq = en_fix_right(en, org, pv, pa, lane, x0, x1, fval);
-        for (int top = move_dp ? max(top_u, (ptop + 3) & ~3) : top_u; top > org + 1; top -= CGPX) {
+        for (int top = move_dp ? max(top_u, (ptop + amask) & ~amask) : top_u; top > org + 1; top -= CGPX) {
             const int gbase = top - CGPX;
             G32 E, M;
             G8 L;
@@ -322,7 +336,7 @@ __global__ __launch_bounds__(256) void k_carve(const DevCarver *cs, int w, int h
     const int org = c.flags[FLAG_ORG_PREV], side = c.flags[FLAG_SIDE];      // published by k_vpath* for this seam
     const int lane = threadIdx.x & 63;
     if (blockIdx.x == 0 && threadIdx.x == 0) c.flags[FLAG_OVF_ROW] = h;       // the band kernels lower / overwrite it when they hand rows over to k_dp_sweep<UPDATE>
-    for (int y = blockIdx.x * 4 + (threadIdx.x >> 6); y < h; y += gridDim.x * 4) carve_row<false>(c, org, side, y, w, stride, delta, move_dp, lane);
+    for (int y = blockIdx.x * 4 + (threadIdx.x >> 6); y < h; y += gridDim.x * 4) carve_row<false, false>(c, org, side, y, w, stride, delta, move_dp, 0, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -336,7 +350,7 @@ __global__ __launch_bounds__(256) void k_carve(const DevCarver *cs, int w, int h
 // the two kernels (the carve's 96 registers and 5 waves per SIMD are what its bandwidth rests on).
 // ---------------------------------------------------------------------------
 template <int NRG>
-__global__ __launch_bounds__(256) void k_carve_e(const DevCarver *cs, DpK p, int w, int h, int stride, int move_dp, int k, int epoch)
+__global__ __launch_bounds__(256) void k_carve_e(const DevCarver *cs, DpK p, int w, int h, int stride, int move_dp, int k, int epoch, int line)
 {
     constexpr int NT = 12;
     constexpr bool luma = (NRG >= 3);
@@ -353,7 +367,7 @@ __global__ __launch_bounds__(256) void k_carve_e(const DevCarver *cs, DpK p, int
     const int wn = w - 1;                                        // the frame after the carve
     gf32 *en = c.en + org + side;                                // its logical view (the origin after this seam)
     for (int y = blockIdx.x * 4 + wv; y < h; y += gridDim.x * 4) {
-        carve_row<false>(c, org, side, y, w, stride, p.delta, move_dp, lane);
+        carve_row<false>(c, org, side, y, w, stride, p.delta, move_dp, line, lane);
         if (wn <= 1) continue;
         // ---- the energy of row y next to the seam (k_emap_update, one row)
         const int g = lane / NT, i = lane - g * NT, t = y - 1 + g;          // lanes 0 .. 35: sample i of row t
@@ -411,7 +425,7 @@ __global__ __launch_bounds__(256) void k_carve_e(const DevCarver *cs, DpK p, int
 // The branch is uniform over the workgroup.  delta_x <= 2 (12 samples per row), packed pixels; everything else keeps the two launches.
 // ---------------------------------------------------------------------------
 template <int NRG>
-__global__ __launch_bounds__(256) void k_carve_u(const DevCarver *cs, DpK p, int w, int h, int stride, int move_dp, int k, int epoch, int n)
+__global__ __launch_bounds__(256) void k_carve_u(const DevCarver *cs, DpK p, int w, int h, int stride, int move_dp, int k, int epoch, int n, int line)
 {
     // (cu_grid / cu_block in lqr_geom.h state this map and the test checks it there; here it stays in the kernel's own text: through the
     // function the instruction stream differs)
@@ -430,7 +444,7 @@ __global__ __launch_bounds__(256) void k_carve_u(const DevCarver *cs, DpK p, int
     const int org = c.flags[FLAG_ORG_PREV], side = c.flags[FLAG_SIDE];      // published by k_vpath* for this seam
     if (rb == 0 && threadIdx.x == 0) c.flags[FLAG_OVF_ROW] = h;
     const int y = rb * 4 + (threadIdx.x >> 6);
-    if (y < h) carve_row<true>(c, org, side, y, w, stride, p.delta, move_dp, threadIdx.x & 63, h, p.radius);
+    if (y < h) carve_row<true>(c, org, side, y, w, stride, p.delta, move_dp, line, threadIdx.x & 63, h, p.radius);
 }
 
 // ---------------------------------------------------------------------------
@@ -468,7 +482,7 @@ __device__ __forceinline__ void st_wt(gi32 *p, int v) { __hip_atomic_store(p, v,
 
 template <int NRG, int DELTA>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_carve_v(const DevCarver *cs, DpK p, int w, int h, int stride, int lr, int move_dp, int k, int epoch, int n,
-                                                 int moved_unit, unsigned tag, unsigned long long *list, unsigned long long *moved_bytes, int *dev_err)
+                                                 int moved_unit, unsigned tag, unsigned long long *list, unsigned long long *moved_bytes, int *dev_err, int line)
 {
     const int eblk = bb_energy_entries(h), rblk = bb_carve_entries(h);
     const unsigned total = (unsigned) n * (unsigned) (eblk + rblk);
@@ -593,17 +607,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
     // (the descriptor comes by vector loads: the row's plane pointers to scalar registers, or the three roles do not fit 96 VGPRs)
     c.en = uni_ptr(c.en); c.m = uni_ptr(c.m); c.least = uni_ptr(c.least); c.seam_x = uni_ptr(c.seam_x);
     const int y = e.index * 4 + (tid >> 6);
-    if (y < h) carve_row<true>(c, e.org, e.side, y, w, stride, DELTA, move_dp, tid & 63, h, p.radius, SeamLive());
+    if (y < h) carve_row<true, true>(c, e.org, e.side, y, w, stride, DELTA, move_dp, line, tid & 63, h, p.radius, SeamLive());
 }
 
 // ---- the instantiations the shim launches (lqr_kernels.h lists them)
 // (k_carve is not a template)
-#define INST(N) template __global__ void k_carve_u<N>(const DevCarver *, DpK, int, int, int, int, int, int, int);
+#define INST(N) template __global__ void k_carve_u<N>(const DevCarver *, DpK, int, int, int, int, int, int, int, int);
 K_CARVE_U_FORMS(INST)
 #undef INST
-#define INST(N, D) template __global__ void k_carve_v<N, D>(const DevCarver *, DpK, int, int, int, int, int, int, int, int, int, unsigned, unsigned long long *, unsigned long long *, int *);
+#define INST(N, D) template __global__ void k_carve_v<N, D>(const DevCarver *, DpK, int, int, int, int, int, int, int, int, int, unsigned, unsigned long long *, unsigned long long *, int *, int);
 K_CARVE_V_FORMS(INST)
 #undef INST
-#define INST(N) template __global__ void k_carve_e<N>(const DevCarver *, DpK, int, int, int, int, int, int);
+#define INST(N) template __global__ void k_carve_e<N>(const DevCarver *, DpK, int, int, int, int, int, int, int);
 K_CARVE_E_FORMS(INST)
 #undef INST

@@ -38,15 +38,15 @@ template <int DELTA> __global__ __launch_bounds__(VPATH_THREADS) void k_vp_solve
 // k_carve.hip
 __global__ __launch_bounds__(256) void k_carve(const DevCarver *cs, int w, int h, int stride, int delta, int move_dp);
 #define K_CARVE_E_FORMS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6)      // LqrEnergyFuncBuiltinType
-template <int NRG> __global__ __launch_bounds__(256) void k_carve_e(const DevCarver *cs, DpK p, int w, int h, int stride, int move_dp, int k, int epoch);
+template <int NRG> __global__ __launch_bounds__(256) void k_carve_e(const DevCarver *cs, DpK p, int w, int h, int stride, int move_dp, int k, int epoch, int line);
 #define K_CARVE_U_FORMS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6)      // LqrEnergyFuncBuiltinType; 12 samples per row (delta_x <= 2), packed pixels
-template <int NRG> __global__ __launch_bounds__(256) void k_carve_u(const DevCarver *cs, DpK p, int w, int h, int stride, int move_dp, int k, int epoch, int n);
+template <int NRG> __global__ __launch_bounds__(256) void k_carve_u(const DevCarver *cs, DpK p, int w, int h, int stride, int move_dp, int k, int epoch, int n, int line);
 // X(NRG, DELTA): the walk role has k_vpath1's forms for delta_x 1 and 2 (K_CARVE_V_DELTAS), the energy role K_CARVE_U_FORMS'
 #define K_CARVE_V_DELTAS(X) X(1) X(2)
 #define K_CARVE_V_FORMS(X) X(0, 1) X(1, 1) X(2, 1) X(3, 1) X(4, 1) X(5, 1) X(6, 1) X(0, 2) X(1, 2) X(2, 2) X(3, 2) X(4, 2) X(5, 2) X(6, 2)
 // (five waves per SIMD, the carve's occupancy: the three roles together must fit its 96 registers)
 template <int NRG, int DELTA> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_carve_v(const DevCarver *cs, DpK p, int w, int h, int stride, int lr, int move_dp, int k, int epoch, int n,
-                                                                                  int moved_unit, unsigned tag, unsigned long long *list, unsigned long long *moved_bytes, int *dev_err);
+                                                                                  int moved_unit, unsigned tag, unsigned long long *list, unsigned long long *moved_bytes, int *dev_err, int line);
 
 // k_band.hip
 #define K_DP_SWEEP_PXT_FORMS(X) X(1) X(2) X(4) X(8) X(16)       // each as <P, false, DP_THREADS>, <P, true, DP_THREADS> and <P, true, 256>

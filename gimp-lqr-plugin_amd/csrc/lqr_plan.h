@@ -54,6 +54,7 @@ struct PlanKnobs {
     int update_mode = -1;           // lqrhip_set_update_mode
     int band_levels = -1;           // k_band_levels: -1 automatic; 0 never; n: n slots per image
     int levels_wg_slots = -1;       // slots per workgroup of the level kernel: -1 automatic (plan_levels_wg_slots); 1: one (k_band_levels); 2: two (k_band_levels2) wherever a form exists
+    int carve_line = -1;            // where a row's groups of the carve start / end: -1 automatic (plan_carve_line: by the carve's form); 0: on a 16-byte vector; 1: on a 128-byte line of the float planes (32 elements)
     int levels_store = -1;          // what the level kernel writes back: -1 automatic (plan_levels_store); 0: every row of a level from every lane; 1: only the changed rows, from the own lanes that changed
     int dpp_limit = -1;             // -1: the occupancy-derived bounds; >= 0: at most that many workgroups for a spinning grid
     int dpp_px = 0;                 // 2, 3 or 4 pins the persistent sweep's geometry code (0 = by batch size)
@@ -98,6 +99,7 @@ struct StepPlan {
     int carve = 0;                  // LQRHIP_CENSUS_CARVE_E (the energy update fused in) or _CARVE
     bool energy_beside = false;     // _CARVE only: k_carve_u, the energy update as workgroups of the carve's launch (counted under _CARVE)
     bool backtrack_beside = false;  // energy_beside only: k_carve_v, the one-wave walk as a role of that launch too (no backtrack launch; counted under _VPATH1 and _CARVE)
+    int carve_line = 0;             // the carve's `line` argument, whichever form runs (plan_carve_line)
     bool catchup = false;           // the frozen planes lag too far: compact them before the energy update
     int eu_nt = 0;                  // k_emap_update's samples per row
     bool full = false;              // dp is a full DP (after a side switch), not an update
@@ -303,6 +305,19 @@ static inline bool plan_backtrack_beside(const PlanKnobs &k, const PlanBatch &b,
     return k.backtrack_beside > 0 || (!b.shared && b.group() >= (size_t) BACKTRACK_BESIDE_MIN);
 }
 
+// Where the groups of a carved row start (the side right of the seam moves) or end (the left side moves): 1 = on a 32-element boundary,
+// a 128-byte line of the float planes, 0 = on a 4-element boundary, the 16-byte vector (carve_row, k_carve.hip).  The same vectors are
+// loaded and stored either way; line-aligned, a wave's 1 KB access covers 8 whole lines instead of 9 in 15 cases of 16 and two
+// neighbouring chunks never request or partly write the same line.  A row costs one more group where the rounding pushes its moved
+// part across a 1024-element boundary.  The knob at 0 pins 0 and at 1 pins 1 (k_carve itself has no such argument: its instructions
+// are pinned); automatic: 1 for the launches that stream, k_carve_u and k_carve_v, 0 for k_carve_e -- the single images and small groups
+// it serves are a chain of short dependent launches, where the one row in thirty that gets a second group is the launch's tail.
+// Measured (profiles/carve_line/README.md): k_carve_v per launch at 64 x 4K, two traces each, parent 453.3 453.7, argument 0 453.5
+// 454.7, argument 1 440.9 441.3 us; 64 images, three alternating runs of 20 steps, parent 172.93 174.43 175.54, new 170.95 171.91
+// 172.85 ms per step.  With 1 for k_carve_e too, Mseams*px/s in the order parent, new, new, parent: fhd 15 462 15 322 15 322 15 524,
+// single4k 26 544 26 495 26 529 26 531.
+static inline int plan_carve_line(const PlanKnobs &k, int carve) { return k.carve_line >= 0 ? k.carve_line : carve == LQRHIP_CENSUS_CARVE ? 1 : 0; }
+
 // One seam of a lock-step batch: the frame is w wide before it; `lag` seams separate the frozen planes from the frame after it
 static inline StepPlan plan_seam_step(const PlanKnobs &k, const PlanDevice &d, const PlanBatch &b, int delta, bool use_rig, int w, int h, bool full_rebuild, int lag)
 {
@@ -326,6 +341,7 @@ static inline StepPlan plan_seam_step(const PlanKnobs &k, const PlanDevice &d, c
     // value-plane carvers: the two kernels
     s.carve = delta <= 2 && b.group() <= (size_t) k.carve_fused && wnew > 1 && !b.value ? LQRHIP_CENSUS_CARVE_E : LQRHIP_CENSUS_CARVE;
     s.energy_beside = s.carve == LQRHIP_CENSUS_CARVE && plan_carve_beside(k, b, delta, wnew);
+    s.carve_line = plan_carve_line(k, s.carve);
     s.catchup = lag > frozen_lag(b.images);
     s.backtrack_beside = plan_backtrack_beside(k, b, delta, h, s.energy_beside, s.backtrack, s.catchup);
     s.eu_nt = eu_samples(delta);

@@ -1109,6 +1109,7 @@ extern "C" void lqrhip_set_dp_persistent_px(int px) { g_knobs.dpp_px = (px == 2 
 extern "C" void lqrhip_set_dp_persistent_limit(int workgroups) { g_knobs.dpp_limit = workgroups; }
 extern "C" void lqrhip_set_band_levels(int slots) { g_knobs.band_levels = slots; }
 extern "C" void lqrhip_set_levels_wg_slots(int slots) { g_knobs.levels_wg_slots = slots == 1 || slots == 2 ? slots : -1; }
+extern "C" void lqrhip_set_carve_line(int mode) { g_knobs.carve_line = mode == 0 || mode == 1 ? mode : -1; }
 extern "C" void lqrhip_set_levels_store(int mode) { g_knobs.levels_store = mode == 0 || mode == 1 ? mode : -1; lqr_levels_report_rows(g_knobs.levels_store >= 0); }
 static unsigned long long g_levels_pair_launches = 0;
 extern "C" unsigned long long lqrhip_levels_pair_launches(int reset) { const unsigned long long n = g_levels_pair_launches; if (reset) g_levels_pair_launches = 0; return n; }
@@ -1394,7 +1395,7 @@ static int launch_carve(LqrHipBatch *b, const StepPlan &s, StepVals &v)
         ProfScope ps("carve", b->stream, bytes);
         CENSUS(LQRHIP_CENSUS_CARVE_E);
         if (!with_listed(K_CARVE_E_FORMS, nrg_index(v.k.nrg), [&](auto nrg) {
-                hipLaunchKernelGGL((k_carve_e<nrg>), dim3(bb_carve_entries(h), n), dim3(256), 0, b->stream, b->d_desc, v.k, w, h, stride, v.move_dp, v.log_index, v.epoch);
+                hipLaunchKernelGGL((k_carve_e<nrg>), dim3(bb_carve_entries(h), n), dim3(256), 0, b->stream, b->d_desc, v.k, w, h, stride, v.move_dp, v.log_index, v.epoch, s.carve_line);
             })) return no_form("k_carve_e");
     } else if (s.backtrack_beside) {
         // k_carve_v: the walks' workgroups first, then one consumer per entry of the work list the walks fill -- the carve's row-quads and
@@ -1419,7 +1420,7 @@ static int launch_carve(LqrHipBatch *b, const StepPlan &s, StepVals &v)
         with_listed(K_CARVE_U_FORMS, nrg_index(v.k.nrg), [&](auto nrg) {
             launched = with_listed(K_CARVE_V_DELTAS, v.k.delta, [&](auto delta) {
                 hipLaunchKernelGGL((k_carve_v<nrg, delta>), dim3(cv_grid(n, h)), dim3(256), 0, b->stream, b->d_desc, v.k, w, h, stride, v.lr_pick, v.move_dp, v.log_index, v.epoch,
-                                   (int) n, v.moved_unit, tag, b->wlist.get(), moved, g_dev_err);
+                                   (int) n, v.moved_unit, tag, b->wlist.get(), moved, g_dev_err, s.carve_line);
             });
         });
         if (!launched) return no_form("k_carve_v");
@@ -1430,7 +1431,7 @@ static int launch_carve(LqrHipBatch *b, const StepPlan &s, StepVals &v)
         CENSUS(LQRHIP_CENSUS_CARVE);
         g_carve_beside_launches++;
         if (!with_listed(K_CARVE_U_FORMS, nrg_index(v.k.nrg), [&](auto nrg) {
-                hipLaunchKernelGGL((k_carve_u<nrg>), dim3(cu_grid(n, h)), dim3(256), 0, b->stream, b->d_desc, v.k, w, h, stride, v.move_dp, v.log_index, v.epoch, (int) n);
+                hipLaunchKernelGGL((k_carve_u<nrg>), dim3(cu_grid(n, h)), dim3(256), 0, b->stream, b->d_desc, v.k, w, h, stride, v.move_dp, v.log_index, v.epoch, (int) n, s.carve_line);
             })) return no_form("k_carve_u");
     } else {
         ProfScope ps("carve", b->stream, bytes);

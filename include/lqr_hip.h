@@ -431,6 +431,11 @@ void lqrhip_set_band_levels(int slots);
 /* Test hook: slots per WORKGROUP of the level kernel: -1 automatic, 1 never two (k_band_levels), 2 two (k_band_levels2) wherever a form
  * exists (delta_x 1, no rigidity mask that matters, at least 2 slots per image) and its grid is resident. */
 void lqrhip_set_levels_wg_slots(int slots);
+/* Test hook: where the groups of a carved row start or end (k_carve_e, k_carve_u, k_carve_v; k_carve keeps 0 whatever this says): 0 on a
+ * 16-byte vector, as it used to be, 1 on a 32-element boundary -- a 128-byte line of the float planes -- so that a wave's accesses cover
+ * whole lines, -1 automatic (plan_carve_line: 1 for k_carve_u and k_carve_v, 0 for k_carve_e).  The same vectors are loaded and stored either way: same seams, planes, flags and
+ * moved bytes. */
+void lqrhip_set_carve_line(int mode);
 /* Test hook: what the level kernel writes back (k_band_levels2 only: k_band_levels ignores it and writes everything): 0 every row of every processed tile-level from every lane (the lanes
  * that own nothing to the spare row), 1 of an interior tile only the rows on which an own pixel changed, and of those only from the
  * own lanes that changed a pixel on any row of the level -- unchanged own lanes and all halo lanes are switched off (what is not
